@@ -8,12 +8,20 @@ with the framebuffer tiled across ranks (interleaved 8x8 tiles) and the
 finished tiles all-gathered over RCCL to assemble the frame on rank 0.
 Total work is fixed as N grows ("strong" scaling).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2..5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2..5] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
 --config selects another BASELINE.json workload (02562_raytracer_amd/configs.py);
 the default, 3, is the headline.  Prints ONE JSON line on rank 0.  See
 DESIGN.md "Measurement".
+
+A plain run sets up, warms up, times the K steps and prints the line: the
+headline figure, the step breakdown of the timed steps' own HIP events and the
+roofline fractions the committed PMC summary gives for that kernel time.  --full
+adds what takes runs of its own: the counting-instantiation step (traversal
+counters, algorithmic bytes, SIMD lane use) and the CPU baseline
+(--no-cpu-baseline leaves that one out of a --full run).  --dump-outputs DIR
+saves the last timed step's frame as DIR/<name>.npy.
 """
 import argparse
 import importlib
@@ -131,15 +139,18 @@ def roofline(key, kern_ms, alg_bytes, config, kernel):
     bounds it"); all three are given.
     The SURVEY 8(d) algorithmic bytes (reference layout) over the kernel time is a
     diagnostic ("algorithmic"): the bytes stay in L2/MALL, so against HBM it can
-    exceed 1 and is never reported as the HBM fraction."""
+    exceed 1 and is never reported as the HBM fraction; it needs the counting
+    step of a --full run (alg_bytes None without it)."""
     s = kern_ms / 1e3
     pmc = None
     if os.path.exists(PMC_SUMMARY):
         with open(PMC_SUMMARY) as f:
             pmc = json.load(f).get(key)
     sha = fatbin_sha16(LIB_FOR_SHA) if LIB_FOR_SHA else None
-    alg = {"bytes_per_launch": int(alg_bytes), "achieved": round(alg_bytes / s / 1e9, 1), "unit": "GB/s",
-           "l2_peak": L2_PEAK_GBS, "l2_frac": round(alg_bytes / s / 1e9 / L2_PEAK_GBS, 4)}
+    alg = None
+    if alg_bytes is not None:
+        alg = {"bytes_per_launch": int(alg_bytes), "achieved": round(alg_bytes / s / 1e9, 1), "unit": "GB/s",
+               "l2_peak": L2_PEAK_GBS, "l2_frac": round(alg_bytes / s / 1e9 / L2_PEAK_GBS, 4)}
     r = {"kernel": kernel, "kernel_ms": round(kern_ms, 3), "algorithmic": alg, "pmc": None, "traffic": None}
     r["fatbin_sha16"] = sha
     if pmc is None or (pmc.get("fatbin_sha16") and sha and pmc["fatbin_sha16"] != sha):
@@ -191,6 +202,29 @@ class DeviceAccel:
         return self.ctx.download_bvh()
 
 
+DUMP_BYTES_MAX = 64 * 1000 * 1000
+
+
+def dump_outputs(path, accum, ids):
+    """--dump-outputs: the last timed step's output as path/<name>.npy -- accum
+    (float32 RGBA radiance sums, one row per pixel) and ids (the primary-hit
+    triangle ids, float64: exact for any u32).  An output above 64 MB in all is
+    cut to a fixed, seeded sample of its pixels, whose row-major indices go to
+    pixels.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    accum = accum.reshape(-1, 4).astype(np.float32, copy=False)
+    ids = ids.reshape(-1).view(np.uint32).astype(np.float64)
+    n = ids.shape[0]
+    room = DUMP_BYTES_MAX - 3 * 128   # (the .npy headers)
+    if n * (16 + 8) > room:
+        keep = room // (16 + 8 + 8)
+        px = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        accum, ids = accum[px], ids[px]
+        np.save(os.path.join(path, "pixels.npy"), px.astype(np.float64))
+    np.save(os.path.join(path, "accum.npy"), accum)
+    np.save(os.path.join(path, "ids.npy"), ids)
+
+
 def all_reduce(dist, t, op):
     """In place on the device under RCCL; through host memory under gloo."""
     if dist.get_backend() == "nccl":
@@ -221,8 +255,14 @@ def main():
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--trav", default=None, choices=["BSP", "BVH"])
     ap.add_argument("--ntris", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own: the counting-instantiation step (traversal counters, "
+                         "algorithmic bytes, SIMD lane use) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves the last timed step's output (accum, ids: the frame, or with --rank-share "
+                         "the packed tiles) as DIR/<name>.npy, 64 MB at the most (a seeded pixel sample above that)")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--shade-threshold", type=lambda x: int(x, 0), default=None,
                     help="RT_OPT_SHADE_THRESHOLD: 0..64, or 0x10000 | hi << 8 | lo (a per-wave choice)")
     ap.add_argument("--waves-per-cu", type=int, default=None)
@@ -376,19 +416,21 @@ def main():
     step()
     counts = ctx.last_counts()
     progress("counted step done")
-    # counting instantiation: traversal counters for the algorithmic bytes
-    ctx.set_option(rt._ffi.RT_OPT_DETAIL_COUNTERS, 1)
-    step()
-    detail = ctx.last_counts()
-    ctx.set_option(rt._ffi.RT_OPT_DETAIL_COUNTERS, 0)
-    progress("counting-instantiation step done")
+    detail = None
+    if args.full:
+        # counting instantiation: traversal counters for the algorithmic bytes
+        ctx.set_option(rt._ffi.RT_OPT_DETAIL_COUNTERS, 1)
+        step()
+        detail = ctx.last_counts()
+        ctx.set_option(rt._ffi.RT_OPT_DETAIL_COUNTERS, 0)
+        progress("counting-instantiation step done")
     for _ in range(max(0, args.warmup - 1)):
         step()
         torch.cuda.synchronize(dev)
         progress("warm-up step done")
 
     rays = torch.tensor([counts["primary"] + counts["shadow"], counts["primary"], counts["shadow"],
-                         counts["bounce"], algorithmic_bytes(detail, trav)],
+                         counts["bounce"], algorithmic_bytes(detail, trav) if detail else 0],
                         dtype=torch.float64, device=dev)
     if use_dist:
         rays = all_reduce(dist, rays, dist.ReduceOp.SUM)
@@ -450,7 +492,7 @@ def main():
         # roofline of the dominant kernel (k_path<mode, traversal>): one launch on
         # one GPU -- rank 0's, with rank 0's own kernel time and the PMC summary of
         # rank 0's share (profiles/pmc_summary.json key _n<N>, measured with --rank-share N)
-        bytes_per_launch = rays[4] / (world if use_dist else 1) / max(1, launches_per_step)
+        bytes_per_launch = rays[4] / (world if use_dist else 1) / max(1, launches_per_step) if detail else None
         # the culling mode the kernel ran (RT_BSP_CULL_AUTO: its probe's choice, made in
         # the first warm-up step) picks the instantiation and the PMC summary
         names = {0: "off", 1: "certified", 2: "fast", 3: "silhouette"}
@@ -467,7 +509,7 @@ def main():
         roof["render_ms"] = round(render_ms, 3)
         roof["kernel_ms_max_over_ranks"] = round(kern_ms, 3)
         cpu = None
-        if not args.no_cpu_baseline and not use_dist and share == 1:
+        if args.full and not args.no_cpu_baseline and not use_dist and share == 1:
             cpu = cpu_baseline(wl, trav, mesh, accel, spp, W, H, args.cpu_budget)
         line = {
             "metric": METRIC, "value": round(value, 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,
@@ -505,20 +547,25 @@ def main():
                                  "host wall time of torch.distributed.gather (gloo)" if use_dist else None),
             },
             "rays_per_step": {"primary": int(rays[1]), "shadow": int(rays[2]), "bounce": int(rays[3])},
-            # this rank's counting step: every launch of one step summed (config 5
+            # this rank's counting step (--full): every launch of one step summed (config 5
             # at 1024 spp is 8 launches of 128 spp, roofline.launches_per_step)
             "traversal_per_step": {k: detail[k] for k in ("node_interior", "node_leaf", "bvh_pops", "tri_tests",
                                                             "tri_accepts", "trips", "lane_steps",
                                                             "leaf_lane_steps", "node_trips", "leaf_trips",
                                                             "exact_tests", "exact_nodes", "shade_passes",
                                                             "shade_lanes", "trav_cycles", "shade_cycles",
-                                                            "memwait_cycles", "subtree_culls")},
-            "simd_lane_util": round(detail["lane_steps"] / max(1, 64 * detail["trips"]), 4),
+                                                            "memwait_cycles", "subtree_culls")} if detail else None,
+            "simd_lane_util": round(detail["lane_steps"] / max(1, 64 * detail["trips"]), 4) if detail else None,
             "setup_s": round(setup_s, 3),
             # setup_s split: the synthetic mesh (generated on the host), the acceleration
             # structure's build + the uniforms (on the device unless --host-build)
             "setup_breakdown_s": {"mesh": round(t_mesh, 3), "accel": round(t_accel, 3)},
         }
+        if args.dump_outputs:
+            if share > 1:   # rank 0's share alone: its packed tiles (no frame is assembled)
+                dump_outputs(args.dump_outputs, acc_local.cpu().numpy(), ids_local.cpu().numpy())
+            else:
+                dump_outputs(args.dump_outputs, frame.cpu().numpy(), frame_ids.cpu().numpy())
         print(json.dumps(line), flush=True)
         if args.dump_frame:
             np.savez(args.dump_frame, accum=frame.cpu().numpy(), ids=frame_ids.cpu().numpy().view(np.uint32))

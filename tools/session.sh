@@ -7,7 +7,7 @@
 #   ab<C>[f]:<v1>,<v2>,.. A/B of variants/<v>/lib02562rt.so on config C (2, 3, 4; 5 at 128 spp;
 #                         f: the fast margin)
 #   m<C>[fast] / m4sil    bench line + kernel-trace stats + PMC passes (tools/measure.sh)
-#   bench:a,b,..          one bench line (bench.py --no-cpu-baseline a b ..), no profiling
+#   bench:a,b,..          one bench line (bench.py --full --no-cpu-baseline a b ..), no profiling
 #   n2 / n4 / n8          the same for rank 0's share of an N-rank split (bench.py --rank-share N)
 #   wf<C>[f] / wfpmc<C>   the wavefront split's price (tools/wavefront_price.py) / its PMC passes
 #   stress                tools/cull_stress.py: configs 3-5 whole frames, every culling mode
@@ -80,7 +80,7 @@ for step in "$@"; do
       # one bench line, no profiling: bench:--config,4,--bsp-cull,4
       a=$(echo ${step#bench:} | tr , ' ')
       echo "== bench $a" >> $OUT/bench_lines.txt
-      timeout -k 10 600 python bench.py --no-cpu-baseline $a > $OUT/bench.tmp 2>&1 || { echo "bench rc=$?"; tail -20 $OUT/bench.tmp; exit 1; }
+      timeout -k 10 600 python bench.py --full --no-cpu-baseline $a > $OUT/bench.tmp 2>&1 || { echo "bench rc=$?"; tail -20 $OUT/bench.tmp; exit 1; }
       grep '^{' $OUT/bench.tmp >> $OUT/bench_lines.txt
       grep '^{' $OUT/bench.tmp | python tools/bench_brief.py ;;
     *) echo "unknown step $step"; exit 2 ;;

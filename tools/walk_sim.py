@@ -22,7 +22,7 @@ NAMES = ["walk_trips", "leaf_trips", "decisions", "leaf_visits", "empty_leaves",
 
 def lib():
     src = os.path.join(ROOT, "tools", "walk_sim.c")
-    so = "/tmp/walk_sim.so"
+    so = os.path.join(ROOT, "tools", "walk_sim.so")   # in the tree, beside its source (git ignores *.so)
     if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
         subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, src], check=True)
     return ctypes.CDLL(so)
