@@ -84,6 +84,8 @@ struct rt_ctx {
     uint32_t nverts = 0, ntris = 0, nmats = 0, nlights = 0;
     bool has_mesh = false;
     DevBuf pos, nrm, idx, mats, lights;
+    DevBuf sweep_recs;           // W5 modes: 48-B records in index-buffer order (ensure_sweep, built at the first W5 render)
+    bool has_sweep = false;
     DevBuf bsp_nodes, bsp_ids;   // bsp_nodes: [8-B nodes | 48-B records]
     DevBuf bsp_tm;               // per record slot {triangle id, material} (DevScene.bsp_tm)
     DevBuf plane_flag;           // launch_plane_range's 4-B result
@@ -507,7 +509,7 @@ int rt_upload_mesh(rt_ctx* c, const float* pos_vec4, const float* nrm_vec4, uint
     }
     if (int r = set_dev(c)) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->has_mesh = c->has_bsp = c->has_bvh = false;
+    c->has_mesh = c->has_bsp = c->has_bvh = c->has_sweep = false;
     c->h_pos.assign(pos_vec4, pos_vec4 + (size_t)nverts * 4);
     c->h_idx.assign(idx_vec4u, idx_vec4u + (size_t)ntris * 4);
     std::vector<float> nrm;
@@ -925,7 +927,8 @@ static hipEvent_t gather_event(rt_ctx* c, hipStream_t s)
 
 // Launch the traversal kernel, bracketed by a pair of pooled events when
 // kernel timing is on (rt_kernel_time).
-static int launch_timed(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_mode mode, rt_traverse trav)
+static int launch_timed(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_mode mode, rt_traverse trav,
+                        const rtk::SweepScene* sweep = nullptr)
 {
     const bool t = c->ktiming && c->kused + 2 <= 8192;
     if (t) {
@@ -936,7 +939,8 @@ static int launch_timed(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch&
         }
         HIPCHK(c, hipEventRecord(c->kev[c->kused], c->stream));
     }
-    int r = rtk::launch_render(S, L, mode, trav, c->detail, c->num_cus, c->waves_per_cu, c->stream);
+    int r = sweep ? rtk::launch_sweep(*sweep, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
+                  : rtk::launch_render(S, L, mode, trav, c->detail, c->num_cus, c->waves_per_cu, c->stream);
     if (r) return fail(c, r, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     if (t) {
         HIPCHK(c, hipEventRecord(c->kev[c->kused + 1], c->stream));
@@ -981,6 +985,24 @@ static int ensure_hcam(rt_ctx* c)
         return fail(c, RT_E_DEVICE, "BSP camera terms: launch failed");
     memcpy(c->hcam_eye, e, sizeof c->hcam_eye);
     c->hcam_valid = true;
+    return RT_OK;
+}
+
+// The W5 modes' flat record array (rt_internal.h SweepScene): record i is triangle i of
+// the index buffer -- the BSP repack is in treeIds order and cannot serve -- built from
+// the host copy of the mesh at the first W5 render after an upload, zero-padded to a
+// whole block of the sweep.
+static int ensure_sweep(rt_ctx* c)
+{
+    if (c->has_sweep) return RT_OK;
+    std::vector<uint32_t> ids(c->ntris);
+    for (uint32_t i = 0; i < c->ntris; i++) ids[i] = i;
+    std::vector<float> recs;
+    build_recs(c->h_pos, c->h_idx, ids.data(), ids.size(), recs);
+    const size_t padded = ((size_t)c->ntris + rtk::SWEEP_PAD_RECS) / rtk::SWEEP_PAD_RECS * rtk::SWEEP_PAD_RECS;
+    recs.resize(padded * 12, 0.0f);
+    if (int r = upload(c, c->sweep_recs, recs.data(), recs.size() * 4)) return r;
+    c->has_sweep = true;
     return RT_OK;
 }
 
@@ -1250,7 +1272,9 @@ static int probe_launch(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch&
 static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaunch& L, rt_ray_counts* counts)
 {
     if (!c->has_u) return fail(c, RT_E_NOT_READY, "rt_render: uniforms not set");
-    if (mode < RT_MODE_W1E6 || mode > RT_MODE_W9E3) return fail(c, RT_E_INVALID, "rt_render: bad mode");
+    if (mode < RT_MODE_W1E6 || mode > RT_MODE_W5E5) return fail(c, RT_E_INVALID, "rt_render: bad mode");
+    // the brute-force W5 scenes: the triangle sweep over the mesh alone (rt_sweep.hip)
+    const bool sweep = mode >= RT_MODE_W5E2 && mode <= RT_MODE_W5E5;
     // W7E1/W7E2: progressive, folded inside k_direct (no per-iteration samples)
     const bool direct_prog = mode == RT_MODE_W7E1 || mode == RT_MODE_W7E2;
     // progressive path tracers: per-iteration samples, folded in order by k_fold
@@ -1258,6 +1282,10 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
                       mode == RT_MODE_W8E3 || mode == RT_MODE_W9E2 || mode == RT_MODE_W9E3;
     if (mode == RT_MODE_W1E6) {
         if (trav != RT_TRAVERSE_NONE) return fail(c, RT_E_UNSUPPORTED, "W1E6 is analytic: traverse must be NONE");
+    } else if (sweep) {
+        if (trav != RT_TRAVERSE_NONE)
+            return fail(c, RT_E_UNSUPPORTED, "W5E2..W5E5 sweep the triangle list: traverse must be NONE");
+        if (!c->has_mesh) return fail(c, RT_E_NOT_READY, "rt_render: no mesh uploaded");
     } else {
         if (!c->has_mesh) return fail(c, RT_E_NOT_READY, "rt_render: no mesh uploaded");
         if (trav == RT_TRAVERSE_BSP && !c->has_bsp) return fail(c, RT_E_NOT_READY, "rt_render: no BSP uploaded");
@@ -1273,6 +1301,8 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
     // the fold stream); every other mode writes accum / ids on the context stream
     // itself, so a fold of an earlier path render still pending there is joined first
     if (int r = path ? set_dev_nojoin(c) : set_dev(c)) return r;
+    if (sweep)
+        if (int r = ensure_sweep(c)) return r;
     if (int r = ensure_hcam(c)) return r;
     rtk::DevScene S = dev_scene(c);
     L.u = c->u;
@@ -1379,6 +1409,19 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
             const int r = rtk::launch_fold(L, c->stream);
             if (r) return fail(c, r, std::string("fold launch failed: ") + hipGetErrorString(hipGetLastError()));
         }
+    } else if (sweep) {
+        rtk::SweepScene W;
+        W.recs = c->sweep_recs.as<float4>();
+        W.pos = S.pos;
+        W.nrm = S.nrm;
+        W.tri_idx = S.tri_idx;
+        W.mats = S.mats;
+        W.lights = S.lights;
+        W.ntris = c->ntris;
+        W.nmats = c->nmats;
+        W.nlights = c->nlights;
+        HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
+        if (int r = launch_timed(c, S, L, mode, trav, &W)) return r;
     } else {
         HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
         if (int r = launch_timed(c, S, L, mode, trav)) return r;

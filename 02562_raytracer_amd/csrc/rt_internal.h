@@ -109,6 +109,26 @@ struct DevLaunch {
     unsigned long long cap_max;
 };
 
+// The scene of the brute-force W5 modes (rt_sweep.hip k_sweep), its own argument
+// block so that DevScene's layout stays as the other kernels were tuned for.
+// recs: one 48-B record {v0, e0 = v1 - v0, e1 = v2 - v0, n = cross(e0, e1)} per
+// triangle in INDEX-BUFFER order (record i is triangle i; tri_idx[i] holds its three
+// vertex indices and its material), padded with zero records to a multiple of
+// SWEEP_PAD_RECS so that a block of the sweep never reads past the allocation.
+constexpr uint32_t SWEEP_PAD_RECS = 4;
+struct SweepScene {
+    const float4* recs;
+    const float4* pos;
+    const float4* nrm;
+    const uint4* tri_idx;
+    const rt_material* mats;
+    const uint32_t* lights;
+    uint32_t ntris, nmats, nlights;
+};
+// RT_MODE_W5E2 .. RT_MODE_W5E5 (RT_TRAVERSE_NONE); detail = counting instantiation.
+int launch_sweep(const SweepScene& s, const DevLaunch& l, rt_mode mode, bool detail, int num_cus, int waves_per_cu,
+                 hipStream_t stream);
+
 // Launch the kernel for (mode, trav); detail = counting instantiation.
 int launch_render(const DevScene& s, const DevLaunch& l, rt_mode mode, rt_traverse trav, bool detail,
                   int num_cus, int waves_per_cu, hipStream_t stream);

@@ -37,32 +37,10 @@
 
 #include "../../include/rt_detmath.h"
 #include "rt_internal.h"
+// the f32 vector math, counters, camera ray and work mapping (shared with rt_sweep.hip)
+#include "rt_device_common.h"
 
 namespace rtk {
-
-// ------------------------------------------------------------------ f32 vector math
-// Component formulas of the WGSL builtins, evaluated left to right.
-struct f3 {
-    float x, y, z;
-};
-__device__ __forceinline__ f3 V(float x, float y, float z) { return f3{x, y, z}; }
-__device__ __forceinline__ f3 add(f3 a, f3 b) { return V(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ f3 sub(f3 a, f3 b) { return V(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ f3 mul(f3 a, f3 b) { return V(a.x * b.x, a.y * b.y, a.z * b.z); }
-__device__ __forceinline__ f3 muls(f3 a, float s) { return V(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ f3 divs(f3 a, float s) { return V(a.x / s, a.y / s, a.z / s); }
-__device__ __forceinline__ f3 neg(f3 a) { return V(-a.x, -a.y, -a.z); }
-__device__ __forceinline__ float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ f3 cross(f3 a, f3 b)
-{
-    return V(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
-}
-__device__ __forceinline__ f3 normalize(f3 a) { return divs(a, rt_det_sqrtf(dot(a, a))); }
-__device__ __forceinline__ f3 ld3(const float4 v) { return V(v.x, v.y, v.z); }
-__device__ __forceinline__ f3 ld3(const float* p) { return V(p[0], p[1], p[2]); }
-__device__ __forceinline__ float comp(f3 a, uint32_t i) { return i == 0 ? a.x : (i == 1 ? a.y : a.z); }
-
-#define RT_PI_F 3.14159265359f
 
 // The lane's index in its wave, recomputed where used (volatile: never hoisted
 // into a long-lived register, which at 8 waves/SIMD would be spilled).
@@ -147,63 +125,8 @@ __device__ __forceinline__ uint32_t mcg31(uint32_t& prev)
 }
 __device__ __forceinline__ float rnd(uint32_t& prev) { return (float)mcg31(prev) / (float)0x80000000u; }
 
-// ------------------------------------------------------------------ counters
-enum { C_SAMPLES, C_PRIMARY, C_SHADOW, C_BOUNCE, C_INTERIOR, C_LEAF, C_POPS, C_IDS, C_TESTS, C_ACCEPTS,
-       C_TRIPS, C_LANE_STEPS, C_LEAF_LANE_STEPS, C_NODE_TRIPS, C_LEAF_TRIPS, C_EXACT_TESTS, C_EXACT_NODES,
-       C_SHADE_PASSES, C_SHADE_LANES, C_TRAV_CYC64, C_SHADE_CYC64, C_MEMWAIT_CYC64, C_CULLS, C_N };
-
-struct Counters {
-    uint32_t v[C_N];
-};
-
-__device__ __forceinline__ void flush_counters(const Counters& c, unsigned long long* out, bool detail)
-{
-    const int n = detail ? (int)C_N : 4;
-    for (int i = 0; i < n; i++) {
-        uint32_t x = c.v[i];
-        unsigned long long s = x;
-        if (i == C_TRAV_CYC64 || i == C_SHADE_CYC64 || i == C_MEMWAIT_CYC64)
-            s <<= 6;   // wave cycles, accumulated in units of 64
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-        if ((threadIdx.x & 63u) == 0 && s) atomicAdd(out + i, s);
-    }
-}
-
 // ------------------------------------------------------------------ camera (w7e3.wgsl:211-228)
-struct Cam {
-    f3 e, v, b1, b2;
-    float d, aspect;
-};
-// The basis v = normalize(p - e), b1 = normalize(cross(v, u)), b2 = cross(b1, v)
-// is loop-invariant: rt_api.cpp evaluates it once on the host with the same
-// IEEE operations (no contraction) and passes it as kernel arguments (SGPRs).
-__device__ __forceinline__ Cam make_cam(const DevLaunch& L)
-{
-    Cam c;
-    c.e = ld3(L.cam + 0);
-    c.v = ld3(L.cam + 3);
-    c.b1 = ld3(L.cam + 6);
-    c.b2 = ld3(L.cam + 9);
-    c.d = L.cam[12];
-    c.aspect = L.cam[13];
-    return c;
-}
-// Kernel arguments made opaque where a sample starts or a lane is refilled:
-// the values derived from them (the camera products, float resolutions,
-// integer-division reciprocals) are then recomputed there from SGPRs instead
-// of being hoisted out of the persistent loop into VGPRs that live across the
-// trip loop and are spilled (k_path at 8 waves/SIMD has 64 VGPRs).
-__device__ __forceinline__ uint32_t sopaque(uint32_t x)
-{
-    asm volatile("" : "+s"(x));
-    return x;
-}
-__device__ __forceinline__ float sopaque(float x)
-{
-    asm volatile("" : "+s"(x));
-    return x;
-}
+// make_cam with its kernel arguments made opaque (sopaque, rt_device_common.h)
 __device__ __forceinline__ Cam make_cam_opaque(const DevLaunch& L)
 {
     Cam c = make_cam(L);
@@ -235,44 +158,7 @@ __device__ __forceinline__ const T& kreload(size_t off)
     asm volatile("" : "+s"(p));
     return *(const T*)(p + off);   // generic; the address-space inference restores the scalar loads
 }
-__device__ __forceinline__ f3 cam_dir(const Cam& c, float ux, float uy, float jx, float jy)
-{
-    return normalize(add(add(muls(muls(c.b1, ux + jx), c.aspect), muls(c.b2, uy + jy)), muls(c.v, c.d)));
-}
-
 // ------------------------------------------------------------------ work mapping
-struct Pix {
-    uint32_t x, y, out;
-    bool valid;
-};
-// The tile rows' rotation is ty mod 8 (tiling.tile_of_seq)
-__device__ __forceinline__ Pix map_pixel(const DevLaunch& L, uint32_t work, uint32_t lane)
-{
-    Pix p;
-    const uint32_t lx = lane & 7u, ly = lane >> 3;
-    const uint32_t tiles_x = sopaque(L.tiles_x);   // see make_cam_opaque
-    if (L.tileset == 0) {
-        uint32_t tx = work % tiles_x, ty = work / tiles_x;
-        uint32_t rx = tx * 8u + lx, ry = ty * 8u + ly;
-        p.valid = rx < L.w && ry < L.h;
-        p.x = L.x0 + rx;
-        p.y = L.y0 + ry;
-        p.out = ry * L.w + rx;
-    } else {
-        // sequence position s = work * nranks + rank; row ty = s / tiles_x, the
-        // row rotated by ty mod 8 (tiling.tile_of_seq): rank r owns the diagonal
-        // columns tx = r + ty (mod nranks) when nranks divides 8 and tiles_x
-        // (1080p: 240 tile columns); frames under 8 tiles wide are not rotated
-        uint32_t t = work * L.nranks + L.rank;
-        uint32_t ty = t / tiles_x, tx = t - ty * tiles_x + (tiles_x >= 8u ? (ty & 7u) : 0u);
-        tx = tx >= tiles_x ? tx - tiles_x : tx;
-        p.x = tx * 8u + lx;
-        p.y = ty * 8u + ly;
-        p.valid = (t < L.tiles_x * L.tiles_y) && p.x < L.u.resolution[0] && p.y < L.u.resolution[1];
-        p.out = work * 64u + lane;
-    }
-    return p;
-}
 // map_pixel's output index recomputed from the pixel (k_path keeps only the
 // pixel across the trip loop): region mode ry * w + rx; tileset mode the
 // packed slot work * 64 + lane of tile t = work * nranks + rank.
@@ -297,18 +183,6 @@ __device__ __forceinline__ uint32_t shard_of_wave()
     const uint32_t cu = ((uint32_t)__builtin_amdgcn_s_getreg(4 | (8 << 6) | ((4 - 1) << 11))) & 15u;
     constexpr uint32_t SUB = RT_SHARD_LG > 3 ? RT_SHARD_LG - 3 : 0;
     return (xcc << SUB) | (cu & ((1u << SUB) - 1u));
-}
-
-__device__ __forceinline__ uint32_t fetch_work(uint32_t* ctr, uint32_t lane)
-{
-    uint32_t v = 0;
-    if (lane == 0) v = atomicAdd(ctr, 1u);
-    return __shfl(v, 0, 64);
-}
-__device__ __forceinline__ void pixel_uv(const rt_uniform& u, uint32_t x, uint32_t y, float& ux, float& uy)
-{
-    ux = ((float)x + 0.5f) / (float)u.resolution[0] - 0.5f;
-    uy = 0.5f - ((float)y + 0.5f) / (float)u.resolution[1];
 }
 
 // ------------------------------------------------------------------ triangle test

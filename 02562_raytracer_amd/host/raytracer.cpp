@@ -115,6 +115,16 @@ std::optional<rt_mode> SceneDescriptor::mode() const
     return std::nullopt;
 }
 
+std::optional<rt_mode> SceneDescriptor::render_mode() const
+{
+    if (const auto m = mode()) return m;
+    if (shader == "w5e2.wgsl") return RT_MODE_W5E2;
+    if (shader == "w5e3.wgsl") return RT_MODE_W5E3;
+    if (shader == "w5e4.wgsl") return RT_MODE_W5E4;
+    if (shader == "w5e5.wgsl") return RT_MODE_W5E5;
+    return std::nullopt;
+}
+
 std::vector<SceneDescriptor> get_scenes()
 {
     // cameras, scenes.rs:47-85 (aspect comes from the frame)
@@ -343,7 +353,7 @@ void RenderState::alloc_tiles()
 
 void RenderState::setup_rendering(const SceneDescriptor& scene)
 {
-    const auto m = scene.mode();
+    const auto m = scene.render_mode();
     if (!m) throw Error(RT_E_UNSUPPORTED, scene.shader + " is outside the hot path (SURVEY.md section 2)");
     scene_ = scene;
     camera_ = scene.camera;
@@ -361,7 +371,9 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
         Mesh mesh = (!exists && scene.model == std::string("bunny.obj") && opts_.bunny_standin) ? Mesh::synth_bunny()
                                                                                                  : Mesh::load(path);
         gpu_.check(rt_upload_mesh_host(c, mesh.get()), "upload mesh");
-        if (trav_ == RT_TRAVERSE_BSP) {
+        if (mode_ >= RT_MODE_W5E2 && mode_ <= RT_MODE_W5E5) {
+            trav_ = RT_TRAVERSE_NONE;   // the brute-force W5 scenes: the mesh alone, no tree
+        } else if (trav_ == RT_TRAVERSE_BSP) {
             if (opts_.device_build) {
                 gpu_.check(rt_build_bsp_device(c, 20, 4, nullptr), "BSP device build");
             } else {   // Mesh::bsp_tree, mesh.rs:229-231 (depth 20, leaf 4)

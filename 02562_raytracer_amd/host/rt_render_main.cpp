@@ -82,6 +82,10 @@ static const char* mode_name(std::optional<rt_mode> m)
     case RT_MODE_W7E2: return "W7E2";
     case RT_MODE_W6E3: return "W6E3";
     case RT_MODE_W9E3: return "W9E3";
+    case RT_MODE_W5E2: return "W5E2";
+    case RT_MODE_W5E3: return "W5E3";
+    case RT_MODE_W5E4: return "W5E4";
+    case RT_MODE_W5E5: return "W5E5";
     }
     return nullptr;
 }
@@ -157,9 +161,12 @@ int main(int argc, char** argv)
         if (flag("--list-scenes")) {
             for (const auto& s : get_scenes()) {
                 const char* m = mode_name(s.mode());
-                std::printf("{\"name\":%s,\"shader\":%s,\"mode\":%s,\"model\":%s,\"res\":[%u,%u],\"vertex_type\":%s,"
+                const char* rm = mode_name(s.render_mode());
+                std::printf("{\"name\":%s,\"shader\":%s,\"mode\":%s,\"render_mode\":%s,\"model\":%s,\"res\":[%u,%u],"
+                            "\"vertex_type\":%s,"
                             "\"traverse_type\":%s,\"background_hdri\":%s,\"camera\":%s}\n",
                             jstr(s.name).c_str(), jstr(s.shader).c_str(), m ? jstr(m).c_str() : "null",
+                            rm ? jstr(rm).c_str() : "null",
                             s.model ? jstr(*s.model).c_str() : "null", s.res.first, s.res.second,
                             s.vertex_type == VertexType::Combined ? "\"Combined\"" : "\"Split\"",
                             s.traverse_type == TraverseType::Bsp ? "\"BSP\"" : "\"BVH\"",
@@ -251,7 +258,7 @@ int main(int argc, char** argv)
         }
         std::printf("{\"scene\":%s,\"mode\":%s,\"width\":%u,\"height\":%u,\"iteration\":%u,\"frames\":%u,"
                     "\"last_launch\":{\"samples\":%llu,\"primary\":%llu,\"shadow\":%llu,\"bounce\":%llu},\"camera\":%s}\n",
-                    jstr(rs.scene().name).c_str(), jstr(mode_name(rs.scene().mode())).c_str(), rs.width(), rs.height(),
+                    jstr(rs.scene().name).c_str(), jstr(mode_name(rs.scene().render_mode())).c_str(), rs.width(), rs.height(),
                     rs.iteration(), frames, (unsigned long long)c.samples, (unsigned long long)c.primary,
                     (unsigned long long)c.shadow, (unsigned long long)c.bounce, cam_json(rs.camera()).c_str());
         return 0;

@@ -55,15 +55,20 @@ class RenderState:
 
     # render_state.rs:161-265
     def setup_rendering(self, scene):
-        if scene.mode is None:
+        if scene.render_mode is None:
             raise F.RtError(F.RT_E_UNSUPPORTED, f"{scene.shader} is outside the hot path (SURVEY.md section 2)")
         self.scene = scene
         self.camera = Camera.from_tuple(scene.camera)
-        self.mode = scene.mode
+        self.mode = scene.render_mode
         self.width, self.height = self.resolution or scene.res
         self.mesh = self.bsp = self.bvh = None
-        if scene.mode == "W1E6":
+        if self.mode == "W1E6":
             self.trav = "NONE"
+        elif self.mode in F.SWEEP_MODES:
+            # the brute-force W5 scenes: the mesh alone, no tree (w5e2.wgsl:230-239)
+            self.trav = "NONE"
+            self.mesh = self._load_model(scene.model)
+            self.ctx.upload_mesh(self.mesh)
         else:
             self.trav = scene.traverse_type
             self.mesh = self._load_model(scene.model)

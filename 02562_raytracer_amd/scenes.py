@@ -26,6 +26,16 @@ SHADER_MODES = {
     "w9e3.wgsl": "W9E3",
 }
 
+# shader file -> rt_mode name of the brute-force worksheet-5 scenes: no tree, a
+# sweep over the triangle list (RT_TRAVERSE_NONE).  Kept apart from SHADER_MODES,
+# whose `mode` means the tree-walk / W1E6 hot path.
+SWEEP_MODES = {
+    "w5e2.wgsl": "W5E2",
+    "w5e3.wgsl": "W5E3",
+    "w5e4.wgsl": "W5E4",
+    "w5e5.wgsl": "W5E5",
+}
+
 
 @dataclass(frozen=True)
 class Camera:
@@ -51,6 +61,12 @@ class SceneDescriptor:
     @property
     def mode(self):
         return SHADER_MODES.get(self.shader)
+
+    @property
+    def render_mode(self):
+        """The rt_mode that renders the scene: `mode`, or else the sweep mode
+        (None = no kernel restates the shader)."""
+        return self.mode or SWEEP_MODES.get(self.shader)
 
     def with_(self, **kw):
         return replace(self, **kw)

@@ -91,6 +91,9 @@ struct SceneDescriptor {   /* :20-44 */
     /* the HIP kernel that restates the shader; nullopt = a worksheet shader
      * outside the hot path */
     std::optional<rt_mode> mode() const;
+    /* the rt_mode that renders the scene: mode(), or else the triangle-sweep mode
+     * of the brute-force W5 scenes (RT_MODE_W5E2..W5E5, RT_TRAVERSE_NONE, no tree) */
+    std::optional<rt_mode> render_mode() const;
 };
 
 std::vector<SceneDescriptor> get_scenes();            /* :46-488, the 44 scenes in order */

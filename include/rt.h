@@ -99,14 +99,22 @@ typedef enum rt_mode {
     RT_MODE_W7E1    = 10, /* res/shaders/w7e1.wgsl: as W6E2, progressive (TEA jitter), no max(., 0) */
     RT_MODE_W7E2    = 11, /* res/shaders/w7e2.wgsl: random area-light points, progressive */
     RT_MODE_W6E3    = 12, /* res/shaders/w6e3.wgsl: W6E2's box + mirror ball and glossy (Phong + refraction) ball */
-    RT_MODE_W9E3    = 13  /* res/shaders/w9e3.wgsl: sun light, holdout plane (AO + sun rays), culled triangles */
+    RT_MODE_W9E3    = 13, /* res/shaders/w9e3.wgsl: sun light, holdout plane (AO + sun rays), culled triangles */
+    /* The brute-force worksheet-5 mesh scenes: no tree, every ray tests the triangles in
+     * index-buffer order and takes the FIRST whose test accepts (intersect_scene_loop's
+     * `has_hit || ...` short-circuits), not the closest.  RT_TRAVERSE_NONE only; they need
+     * rt_upload_mesh and no BSP or BVH.  One frame per call (first_iter and spp are not read). */
+    RT_MODE_W5E2    = 14, /* res/shaders/w5e2.wgsl: flat normals, directional light, one shadow sweep per hit */
+    RT_MODE_W5E3    = 15, /* res/shaders/w5e3.wgsl: interpolated vertex normals, directional light, no shadow rays */
+    RT_MODE_W5E4    = 16, /* res/shaders/w5e4.wgsl: material diffuse + ambient; no 1/subdiv^2 multiplier */
+    RT_MODE_W5E5    = 17  /* res/shaders/w5e5.wgsl: every area-light centre, one shadow sweep per light and hit */
 } rt_mode;
 
 /* SceneDescriptor.traverse_type, src/scenes.rs:13-17 */
 typedef enum rt_traverse {
     RT_TRAVERSE_BSP  = 0,
     RT_TRAVERSE_BVH  = 1,
-    RT_TRAVERSE_NONE = 2   /* only valid with RT_MODE_W1E6 */
+    RT_TRAVERSE_NONE = 2   /* only valid with RT_MODE_W1E6 (analytic) and RT_MODE_W5E2..W5E5 (triangle sweep) */
 } rt_traverse;
 
 /* A rectangle of the frame in GLOBAL pixel coordinates. */
@@ -264,7 +272,7 @@ int rt_memset_device(rt_ctx* ctx, void* dst_dev, int value, size_t bytes);
 int rt_timer_start(rt_ctx* ctx);
 int rt_timer_stop(rt_ctx* ctx, float* ms);   /* synchronizes */
 
-/* Per-launch timing of the traversal kernels (k_path / k_primary / k_w1e6),
+/* Per-launch timing of the traversal kernels (k_path / k_primary / k_w1e6 / k_sweep),
  * enabled by RT_OPT_KERNEL_TIMING: HIP events around every such launch on the
  * context stream.  rt_kernel_time synchronizes and returns the summed
  * duration and the number of launches since the last reset (reset != 0
@@ -399,7 +407,8 @@ int rt_set_environment_map(rt_ctx* ctx, const uint8_t* rgba8, uint32_t width, ui
  *     in/out: holds the accumulation of iterations < first_iter (read when
  *     first_iter > 0; the RenderDestination texture, render_state.rs:541-555),
  *     and receives max(vec4(accum,1),0) (w7e3.wgsl:261-271).  For W1E6/W6E1/
- *     PROJECT it receives the linear per-frame result (before pow(.,1.5)).
+ *     PROJECT and W5E2..W5E5 it receives the linear per-frame result (before
+ *     pow(.,1.5)).
  *   primary_hit_ids: DEVICE or NULL, region.w*region.h u32: triangle index of
  *     the primary hit of the LAST traced iteration, UINT32_MAX on miss.
  *   counts: host pointer or NULL; when non-NULL the call synchronizes and
