@@ -24,7 +24,9 @@ RT_E_UNSUPPORTED = -6
 
 (RT_MODE_W1E6, RT_MODE_W6E1, RT_MODE_PROJECT, RT_MODE_W7E3, RT_MODE_W9E1, RT_MODE_W8E1, RT_MODE_W8E2, RT_MODE_W8E3,
  RT_MODE_W9E2, RT_MODE_W6E2, RT_MODE_W7E1, RT_MODE_W7E2, RT_MODE_W6E3, RT_MODE_W9E3,
- RT_MODE_W5E2, RT_MODE_W5E3, RT_MODE_W5E4, RT_MODE_W5E5) = range(18)
+ RT_MODE_W5E2, RT_MODE_W5E3, RT_MODE_W5E4, RT_MODE_W5E5,
+ RT_MODE_W2E1, RT_MODE_W2E2, RT_MODE_W2E3, RT_MODE_W2E4, RT_MODE_W2E5,
+ RT_MODE_W3E1, RT_MODE_W3E2, RT_MODE_W3E3, RT_MODE_W3E4) = range(27)
 RT_TRAVERSE_BSP, RT_TRAVERSE_BVH, RT_TRAVERSE_NONE = range(3)
 RT_OPT_DETAIL_COUNTERS = 1
 RT_OPT_WAVES_PER_CU = 2
@@ -43,9 +45,16 @@ MODES = {"W1E6": RT_MODE_W1E6, "W6E1": RT_MODE_W6E1, "PROJECT": RT_MODE_PROJECT,
          "W9E1": RT_MODE_W9E1, "W8E1": RT_MODE_W8E1, "W8E2": RT_MODE_W8E2, "W8E3": RT_MODE_W8E3,
          "W9E2": RT_MODE_W9E2, "W6E2": RT_MODE_W6E2, "W7E1": RT_MODE_W7E1, "W7E2": RT_MODE_W7E2,
          "W6E3": RT_MODE_W6E3, "W9E3": RT_MODE_W9E3,
-         "W5E2": RT_MODE_W5E2, "W5E3": RT_MODE_W5E3, "W5E4": RT_MODE_W5E4, "W5E5": RT_MODE_W5E5}
+         "W5E2": RT_MODE_W5E2, "W5E3": RT_MODE_W5E3, "W5E4": RT_MODE_W5E4, "W5E5": RT_MODE_W5E5,
+         "W2E1": RT_MODE_W2E1, "W2E2": RT_MODE_W2E2, "W2E3": RT_MODE_W2E3, "W2E4": RT_MODE_W2E4,
+         "W2E5": RT_MODE_W2E5, "W3E1": RT_MODE_W3E1, "W3E2": RT_MODE_W3E2, "W3E3": RT_MODE_W3E3,
+         "W3E4": RT_MODE_W3E4}
 # the brute-force W5 scenes: a triangle sweep over the mesh alone (RT_TRAVERSE_NONE, no BSP / BVH)
 SWEEP_MODES = ("W5E2", "W5E3", "W5E4", "W5E5")
+# the analytic W2 / W3 scenes: three constant objects, materials, bounces (RT_TRAVERSE_NONE, no mesh);
+# the W3 ones sample texture0 (rt_set_texture)
+ANALYTIC_MODES = ("W2E1", "W2E2", "W2E3", "W2E4", "W2E5", "W3E1", "W3E2", "W3E3", "W3E4")
+TEXTURED_MODES = ("W3E1", "W3E2", "W3E3", "W3E4")
 # progressive path tracers (per-iteration samples folded in order)
 PATH_MODES = ("W7E3", "W9E1", "W8E1", "W8E2", "W8E3", "W9E2", "W7E1", "W7E2", "W9E3")
 TRAVERSALS = {"BSP": RT_TRAVERSE_BSP, "BVH": RT_TRAVERSE_BVH, "NONE": RT_TRAVERSE_NONE}
@@ -160,6 +169,7 @@ SIGNATURES = {
     "rt_set_uniforms": (C.c_int, [vp, C.POINTER(Uniform), f32p]),
     "rt_set_environment": (C.c_int, [vp, f32p]),
     "rt_set_environment_map": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]),
+    "rt_set_texture": (C.c_int, [vp, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32]),
     "rt_render": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(Tile), C.c_uint32, C.c_uint32, vp, vp,
                             C.POINTER(RayCounts)]),
     "rt_render_tiles": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(Tileset), C.c_uint32, C.c_uint32, vp, vp,

@@ -158,8 +158,10 @@ class Bvh:
         return raw, F.np_from(v.tri_ids, v.nids, np.uint32)
 
 
-def make_uniform(eye, target, up, constant, width, height, selection1=0, subdiv=1, aspect=None, iteration=0):
-    """Uniform (src/bindings/uniform.rs:6-34) for a headless W x H frame."""
+def make_uniform(eye, target, up, constant, width, height, selection1=0, subdiv=1, aspect=None, iteration=0,
+                 selection2=0, use_texture=0, uv_scale=(1.0, 1.0)):
+    """Uniform (src/bindings/uniform.rs:6-34) for a headless W x H frame; selection2,
+    use_texture and uv_scale default to the reference's (uniform.rs:152-156)."""
     u = F.Uniform()
     u.camera_pos[:] = [float(v) for v in eye]
     u.camera_look_at[:] = [float(v) for v in target]
@@ -167,9 +169,11 @@ def make_uniform(eye, target, up, constant, width, height, selection1=0, subdiv=
     u.camera_constant = float(constant)
     u.aspect_ratio = float(np.float32(width) / np.float32(height)) if aspect is None else float(aspect)
     u.selection1 = selection1
+    u.selection2 = selection2
     u.subdivision_level = subdiv
+    u.use_texture = use_texture
     u.iteration = iteration
-    u.uv_scale[:] = [1.0, 1.0]
+    u.uv_scale[:] = [float(v) for v in uv_scale]
     u.resolution[:] = [width, height]
     return u
 
@@ -390,6 +394,16 @@ class Context:
         self._chk(F.lib().rt_set_environment_map(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1],
                                                  a.shape[0]))
 
+    def set_texture(self, rgba8):
+        """texture0 of the W3 scenes: uint8[h, w, 4] (RGBA, row 0 at v = 0), or None."""
+        if rgba8 is None:
+            self._chk(F.lib().rt_set_texture(self._h, None, 0, 0))
+            return
+        a = np.ascontiguousarray(rgba8, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("texture must be uint8[h, w, 4]")
+        self._chk(F.lib().rt_set_texture(self._h, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.shape[1], a.shape[0]))
+
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)
 
@@ -527,6 +541,22 @@ def load_texture_rgba8(path):
     from PIL import Image
     with Image.open(path) as im:
         return np.asarray(im.convert("RGBA"), dtype=np.uint8).copy()
+
+
+def synth_texture(size=64):
+    """Deterministic stand-in for res/textures/grass.jpg (not redistributed): uint8
+    [size, size, 4], mottled greens from an integer hash of the texel coordinates
+    (the same arithmetic as raytracer::synth_texture, include/raytracer.hpp)."""
+    y, x = np.meshgrid(np.arange(size, dtype=np.uint32), np.arange(size, dtype=np.uint32), indexing="ij")
+    h = (x * np.uint32(73856093)) ^ (y * np.uint32(19349663))
+    h = (h ^ (h >> np.uint32(13))) * np.uint32(0x5BD1E995)
+    h = h ^ (h >> np.uint32(15))
+    t = np.empty((size, size, 4), np.uint8)
+    t[..., 0] = 40 + (h & np.uint32(63))
+    t[..., 1] = 120 + ((h >> np.uint32(8)) & np.uint32(127))
+    t[..., 2] = 20 + ((h >> np.uint32(16)) & np.uint32(31))
+    t[..., 3] = 255
+    return t
 
 
 def local_tiles(width, height, nranks):

@@ -125,6 +125,8 @@ struct rt_ctx {
     bool has_jitter = false;
     float env[3] = {1.0f, 1.0f, 1.0f};
     DevBuf env_tex;   // RGBA8 equirectangular hdri0 (rt_set_environment_map)
+    DevBuf tex0;      // RGBA8 texture0 of the W3 modes (rt_set_texture)
+    uint32_t tex0_w = 0, tex0_h = 0;
     uint32_t env_w = 0, env_h = 0;
     DevBuf work, counters;
     DevBuf bvh_deep;   // BVH stack entries beyond the kernels' LDS share
@@ -928,7 +930,7 @@ static hipEvent_t gather_event(rt_ctx* c, hipStream_t s)
 // Launch the traversal kernel, bracketed by a pair of pooled events when
 // kernel timing is on (rt_kernel_time).
 static int launch_timed(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_mode mode, rt_traverse trav,
-                        const rtk::SweepScene* sweep = nullptr)
+                        const rtk::SweepScene* sweep = nullptr, const rtk::AnalyticTex* analytic = nullptr)
 {
     const bool t = c->ktiming && c->kused + 2 <= 8192;
     if (t) {
@@ -939,8 +941,9 @@ static int launch_timed(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch&
         }
         HIPCHK(c, hipEventRecord(c->kev[c->kused], c->stream));
     }
-    int r = sweep ? rtk::launch_sweep(*sweep, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
-                  : rtk::launch_render(S, L, mode, trav, c->detail, c->num_cus, c->waves_per_cu, c->stream);
+    int r = analytic ? rtk::launch_analytic(*analytic, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
+            : sweep  ? rtk::launch_sweep(*sweep, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
+                     : rtk::launch_render(S, L, mode, trav, c->detail, c->num_cus, c->waves_per_cu, c->stream);
     if (r) return fail(c, r, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     if (t) {
         HIPCHK(c, hipEventRecord(c->kev[c->kused + 1], c->stream));
@@ -964,6 +967,28 @@ int rt_set_environment_map(rt_ctx* c, const uint8_t* rgba8, uint32_t width, uint
     if (int r = upload(c, c->env_tex, rgba8, (size_t)width * height * 4)) return r;
     c->env_w = width;
     c->env_h = height;
+    return RT_OK;
+}
+
+int rt_set_texture(rt_ctx* c, const uint8_t* rgba8, uint32_t width, uint32_t height)
+{
+    if (!c) return RT_E_INVALID;
+    if (!rgba8) {
+        if (c->tex0.p) {   // a render that reads it may still be in flight
+            if (int r = set_dev(c)) return r;
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
+        c->tex0.reset();
+        c->tex0_w = c->tex0_h = 0;
+        return RT_OK;
+    }
+    if (width == 0 || height == 0 || (uint64_t)width * height >= (1ull << 31))
+        return fail(c, RT_E_INVALID, "rt_set_texture: bad texture size");
+    if (int r = set_dev(c)) return r;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int r = upload(c, c->tex0, rgba8, (size_t)width * height * 4)) return r;
+    c->tex0_w = width;
+    c->tex0_h = height;
     return RT_OK;
 }
 
@@ -1272,7 +1297,9 @@ static int probe_launch(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch&
 static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaunch& L, rt_ray_counts* counts)
 {
     if (!c->has_u) return fail(c, RT_E_NOT_READY, "rt_render: uniforms not set");
-    if (mode < RT_MODE_W1E6 || mode > RT_MODE_W5E5) return fail(c, RT_E_INVALID, "rt_render: bad mode");
+    if (mode < RT_MODE_W1E6 || mode > RT_MODE_W3E4) return fail(c, RT_E_INVALID, "rt_render: bad mode");
+    // the analytic W2 / W3 scenes: three constant objects, no mesh (rt_analytic.hip)
+    const bool analytic = mode >= RT_MODE_W2E1 && mode <= RT_MODE_W3E4;
     // the brute-force W5 scenes: the triangle sweep over the mesh alone (rt_sweep.hip)
     const bool sweep = mode >= RT_MODE_W5E2 && mode <= RT_MODE_W5E5;
     // W7E1/W7E2: progressive, folded inside k_direct (no per-iteration samples)
@@ -1282,6 +1309,11 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
                       mode == RT_MODE_W8E3 || mode == RT_MODE_W9E2 || mode == RT_MODE_W9E3;
     if (mode == RT_MODE_W1E6) {
         if (trav != RT_TRAVERSE_NONE) return fail(c, RT_E_UNSUPPORTED, "W1E6 is analytic: traverse must be NONE");
+    } else if (analytic) {
+        if (trav != RT_TRAVERSE_NONE)
+            return fail(c, RT_E_UNSUPPORTED, "W2E1..W3E4 are analytic: traverse must be NONE");
+        if (mode >= RT_MODE_W3E1 && c->u.use_texture > 0u && !c->tex0_w)
+            return fail(c, RT_E_NOT_READY, "rt_render: uniforms.use_texture is set and no texture is (rt_set_texture)");
     } else if (sweep) {
         if (trav != RT_TRAVERSE_NONE)
             return fail(c, RT_E_UNSUPPORTED, "W5E2..W5E5 sweep the triangle list: traverse must be NONE");
@@ -1409,6 +1441,13 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
             const int r = rtk::launch_fold(L, c->stream);
             if (r) return fail(c, r, std::string("fold launch failed: ") + hipGetErrorString(hipGetLastError()));
         }
+    } else if (analytic) {
+        rtk::AnalyticTex T;
+        T.texels = c->tex0_w ? c->tex0.as<uint32_t>() : nullptr;
+        T.w = c->tex0_w;
+        T.h = c->tex0_h;
+        HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
+        if (int r = launch_timed(c, S, L, mode, trav, nullptr, &T)) return r;
     } else if (sweep) {
         rtk::SweepScene W;
         W.recs = c->sweep_recs.as<float4>();

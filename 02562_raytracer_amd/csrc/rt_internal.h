@@ -1,5 +1,5 @@
 // rt_internal.h -- launch interface between the C ABI layer (rt_api.cpp) and
-// the gfx950 kernels (rt_kernels.hip).  Not part of the public ABI.
+// the gfx950 kernels (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -128,6 +128,16 @@ struct SweepScene {
 // RT_MODE_W5E2 .. RT_MODE_W5E5 (RT_TRAVERSE_NONE); detail = counting instantiation.
 int launch_sweep(const SweepScene& s, const DevLaunch& l, rt_mode mode, bool detail, int num_cus, int waves_per_cu,
                  hipStream_t stream);
+
+// texture0 of the analytic W3 modes (rt_analytic.hip k_analytic), the kernel's own
+// small argument block for the same reason: RGBA8 texels, row 0 at v = 0 (null: none).
+struct AnalyticTex {
+    const uint32_t* texels;
+    uint32_t w, h;
+};
+// RT_MODE_W2E1 .. RT_MODE_W3E4 (RT_TRAVERSE_NONE); detail = counting instantiation.
+int launch_analytic(const AnalyticTex& t, const DevLaunch& l, rt_mode mode, bool detail, int num_cus, int waves_per_cu,
+                    hipStream_t stream);
 
 // Launch the kernel for (mode, trav); detail = counting instantiation.
 int launch_render(const DevScene& s, const DevLaunch& l, rt_mode mode, rt_traverse trav, bool detail,

@@ -125,6 +125,15 @@ std::optional<rt_mode> SceneDescriptor::render_mode() const
     return std::nullopt;
 }
 
+std::optional<rt_mode> SceneDescriptor::analytic_mode() const
+{
+    static const char* const files[9] = {"w2e1.wgsl", "w2e2.wgsl", "w2e3.wgsl", "w2e4.wgsl", "w2e5.wgsl",
+                                         "w3e1.wgsl", "w3e2.wgsl", "w3e3.wgsl", "w3e4.wgsl"};
+    for (int i = 0; i < 9; i++)
+        if (shader == files[i]) return (rt_mode)(RT_MODE_W2E1 + i);
+    return std::nullopt;
+}
+
 std::vector<SceneDescriptor> get_scenes()
 {
     // cameras, scenes.rs:47-85 (aspect comes from the frame)
@@ -259,7 +268,8 @@ std::vector<std::array<float, 2>> compute_jitters(double pixel_size, uint32_t su
 }
 
 rt_uniform make_uniform(const Camera& cam, uint32_t width, uint32_t height, uint32_t selection1,
-                        uint32_t subdivision_level, uint32_t iteration)
+                        uint32_t subdivision_level, uint32_t iteration, uint32_t selection2, uint32_t use_texture,
+                        std::array<float, 2> uv_scale)
 {
     rt_uniform u;
     std::memset(&u, 0, sizeof u);
@@ -271,12 +281,32 @@ rt_uniform make_uniform(const Camera& cam, uint32_t width, uint32_t height, uint
     u.camera_constant = cam.constant;
     u.aspect_ratio = (float)width / (float)height;   // headless: the frame's W/H (render_state.rs:563-566)
     u.selection1 = selection1;
+    u.selection2 = selection2;
     u.subdivision_level = subdivision_level;
+    u.use_texture = use_texture;
     u.iteration = iteration;
-    u.uv_scale[0] = u.uv_scale[1] = 1.0f;
+    u.uv_scale[0] = uv_scale[0];
+    u.uv_scale[1] = uv_scale[1];
     u.resolution[0] = width;
     u.resolution[1] = height;
     return u;
+}
+
+std::vector<uint8_t> synth_texture(uint32_t size)
+{
+    std::vector<uint8_t> t((size_t)size * size * 4);
+    for (uint32_t y = 0; y < size; y++)
+        for (uint32_t x = 0; x < size; x++) {
+            uint32_t h = (x * 73856093u) ^ (y * 19349663u);
+            h = (h ^ (h >> 13)) * 0x5BD1E995u;
+            h = h ^ (h >> 15);
+            uint8_t* p = &t[((size_t)y * size + x) * 4];
+            p[0] = (uint8_t)(40u + (h & 63u));
+            p[1] = (uint8_t)(120u + ((h >> 8) & 127u));
+            p[2] = (uint8_t)(20u + ((h >> 16) & 31u));
+            p[3] = 255;
+        }
+    return t;
 }
 
 // ------------------------------------------------------------------ mesh.rs
@@ -353,7 +383,7 @@ void RenderState::alloc_tiles()
 
 void RenderState::setup_rendering(const SceneDescriptor& scene)
 {
-    const auto m = scene.render_mode();
+    const auto m = scene.render_mode() ? scene.render_mode() : scene.analytic_mode();
     if (!m) throw Error(RT_E_UNSUPPORTED, scene.shader + " is outside the hot path (SURVEY.md section 2)");
     scene_ = scene;
     camera_ = scene.camera;
@@ -363,6 +393,16 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
     rt_ctx* c = gpu_.ctx();
     if (mode_ == RT_MODE_W1E6) {
         trav_ = RT_TRAVERSE_NONE;
+    } else if (mode_ >= RT_MODE_W2E1 && mode_ <= RT_MODE_W3E4) {
+        // the analytic W2 / W3 scenes: no mesh; the W3 ones sample texture0 (grass.jpg is
+        // not redistributed and this layer decodes no JPEG: the stand-in, or set_texture_image)
+        trav_ = RT_TRAVERSE_NONE;
+        if (mode_ >= RT_MODE_W3E1) {
+            const auto tex = synth_texture();
+            gpu_.check(rt_set_texture(c, tex.data(), 64, 64), "texture0");
+        } else {
+            gpu_.check(rt_set_texture(c, nullptr, 0, 0), "texture0");
+        }
     } else {
         trav_ = scene.traverse_type == TraverseType::Bsp ? RT_TRAVERSE_BSP : RT_TRAVERSE_BVH;
         const std::string path = opts_.models_dir + "/" + scene.model.value_or("");
@@ -417,7 +457,8 @@ void RenderState::update()
 {
     camera_.aspect = (float)width_ / (float)height_;
     controller_.update_camera(camera_);
-    const rt_uniform u = make_uniform(camera_, width_, height_, selection1_, subdivision_, iteration_);
+    const rt_uniform u = make_uniform(camera_, width_, height_, selection1_, subdivision_, iteration_, selection2_,
+                                      use_texture_, uv_scale_);
     const auto jit = compute_jitters(1.0 / (double)height_, subdivision_);
     gpu_.check(rt_set_uniforms(gpu_.ctx(), &u, &jit[0][0]), "set uniforms");
 }
@@ -466,6 +507,17 @@ void RenderState::set_samples(uint32_t samples, bool enabled)
 
 void RenderState::set_subdivision_level(uint32_t level) { subdivision_ = level <= MAX_SUBDIVISION ? level : MAX_SUBDIVISION; }
 void RenderState::set_selection1(uint32_t shader) { selection1_ = shader; }
+
+void RenderState::set_other_material(uint32_t shader) { selection2_ = shader; }
+void RenderState::set_texture(uint32_t use_texture, std::array<float, 2> uv_scale)
+{
+    use_texture_ = use_texture;
+    uv_scale_ = uv_scale;
+}
+void RenderState::set_texture_image(const uint8_t* rgba8, uint32_t width, uint32_t height)
+{
+    gpu_.check(rt_set_texture(gpu_.ctx(), rgba8, width, height), "texture0");
+}
 
 void RenderState::set_environment_map(const uint8_t* rgba8, uint32_t width, uint32_t height)
 {

@@ -5,8 +5,10 @@
 //
 //   rt_render --list-scenes
 //   rt_render --scene NAME [--res WxH] [--spp N | --samples N] [--keys K1,K2 --updates N]
-//             [--selection K] [--subdiv K] [--camera-constant C] [--device-build]
-//             [--env-rgba FILE --env-size WxH] [--models DIR] [--out PREFIX]
+//             [--selection K] [--selection2 K] [--use-texture K] [--uv-scale A,B]
+//             [--subdiv K] [--camera-constant C] [--device-build]
+//             [--env-rgba FILE --env-size WxH] [--tex-rgba FILE --tex-size WxH]
+//             [--models DIR] [--out PREFIX]
 //   rt_render ... --nranks N --rank R --comm-file PATH [--comm-token T] [--device D]
 //                                        (one process per GPU: rank R renders its
 //                                        interleaved tiles, rank 0 gathers the frame
@@ -86,6 +88,15 @@ static const char* mode_name(std::optional<rt_mode> m)
     case RT_MODE_W5E3: return "W5E3";
     case RT_MODE_W5E4: return "W5E4";
     case RT_MODE_W5E5: return "W5E5";
+    case RT_MODE_W2E1: return "W2E1";
+    case RT_MODE_W2E2: return "W2E2";
+    case RT_MODE_W2E3: return "W2E3";
+    case RT_MODE_W2E4: return "W2E4";
+    case RT_MODE_W2E5: return "W2E5";
+    case RT_MODE_W3E1: return "W3E1";
+    case RT_MODE_W3E2: return "W3E2";
+    case RT_MODE_W3E3: return "W3E3";
+    case RT_MODE_W3E4: return "W3E4";
     }
     return nullptr;
 }
@@ -162,11 +173,13 @@ int main(int argc, char** argv)
             for (const auto& s : get_scenes()) {
                 const char* m = mode_name(s.mode());
                 const char* rm = mode_name(s.render_mode());
-                std::printf("{\"name\":%s,\"shader\":%s,\"mode\":%s,\"render_mode\":%s,\"model\":%s,\"res\":[%u,%u],"
+                const char* am = mode_name(s.analytic_mode());
+                std::printf("{\"name\":%s,\"shader\":%s,\"mode\":%s,\"render_mode\":%s,\"analytic_mode\":%s,"
+                            "\"model\":%s,\"res\":[%u,%u],"
                             "\"vertex_type\":%s,"
                             "\"traverse_type\":%s,\"background_hdri\":%s,\"camera\":%s}\n",
                             jstr(s.name).c_str(), jstr(s.shader).c_str(), m ? jstr(m).c_str() : "null",
-                            rm ? jstr(rm).c_str() : "null",
+                            rm ? jstr(rm).c_str() : "null", am ? jstr(am).c_str() : "null",
                             s.model ? jstr(*s.model).c_str() : "null", s.res.first, s.res.second,
                             s.vertex_type == VertexType::Combined ? "\"Combined\"" : "\"Split\"",
                             s.traverse_type == TraverseType::Bsp ? "\"BSP\"" : "\"BVH\"",
@@ -227,7 +240,25 @@ int main(int argc, char** argv)
             if (!f) throw Error(RT_E_INVALID, "cannot read " + *ef);
             rs.set_environment_map(env.data(), w, h);
         }
+        std::vector<uint8_t> tex;
+        if (const std::string* tf = arg("--tex-rgba")) {
+            unsigned w = 0, h = 0;
+            if (!arg("--tex-size") || std::sscanf(arg("--tex-size")->c_str(), "%ux%u", &w, &h) != 2)
+                throw Error(RT_E_INVALID, "--tex-rgba needs --tex-size WxH");
+            std::ifstream f(*tf, std::ios::binary);
+            tex.resize((size_t)w * h * 4);
+            f.read(reinterpret_cast<char*>(tex.data()), (std::streamsize)tex.size());
+            if (!f) throw Error(RT_E_INVALID, "cannot read " + *tf);
+            rs.set_texture_image(tex.data(), w, h);
+        }
         if (const std::string* s = arg("--selection")) rs.set_selection1((uint32_t)std::atoi(s->c_str()));
+        if (const std::string* s = arg("--selection2")) rs.set_other_material((uint32_t)std::atoi(s->c_str()));
+        if (arg("--use-texture") || arg("--uv-scale")) {
+            float a = 1.0f, b = 1.0f;
+            if (const std::string* s = arg("--uv-scale"))
+                if (std::sscanf(s->c_str(), "%f,%f", &a, &b) != 2) throw Error(RT_E_INVALID, "--uv-scale A,B");
+            rs.set_texture(arg("--use-texture") ? (uint32_t)std::atoi(arg("--use-texture")->c_str()) : 0u, {a, b});
+        }
         if (const std::string* s = arg("--subdiv")) rs.set_subdivision_level((uint32_t)std::atoi(s->c_str()));
         if (const std::string* s = arg("--camera-constant")) rs.update_camera_constant((float)std::atof(s->c_str()));
         if (const std::string* k = arg("--keys")) {
@@ -258,7 +289,7 @@ int main(int argc, char** argv)
         }
         std::printf("{\"scene\":%s,\"mode\":%s,\"width\":%u,\"height\":%u,\"iteration\":%u,\"frames\":%u,"
                     "\"last_launch\":{\"samples\":%llu,\"primary\":%llu,\"shadow\":%llu,\"bounce\":%llu},\"camera\":%s}\n",
-                    jstr(rs.scene().name).c_str(), jstr(mode_name(rs.scene().render_mode())).c_str(), rs.width(), rs.height(),
+                    jstr(rs.scene().name).c_str(), jstr(mode_name(rs.mode())).c_str(), rs.width(), rs.height(),
                     rs.iteration(), frames, (unsigned long long)c.samples, (unsigned long long)c.primary,
                     (unsigned long long)c.shadow, (unsigned long long)c.bounce, cam_json(rs.camera()).c_str());
         return 0;

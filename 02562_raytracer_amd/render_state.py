@@ -11,7 +11,10 @@ Differences from the windowed reference, all deliberate:
     when the file is in assets/textures (decoded with PIL, sampled as
     include/rt_detmath.h pins it), else a constant environment colour;
   * a missing bunny.obj can be replaced by the deterministic stand-in
-    (bunny_standin=True), since the reference checkout lacks it.
+    (bunny_standin=True), since the reference checkout lacks it;
+  * texture0 of the W3 scenes is assets/textures/grass.jpg when a user has put
+    it there (the reference's file is not redistributed), else the
+    deterministic stand-in core.synth_texture().
 """
 import os
 
@@ -20,7 +23,7 @@ import numpy as np
 from . import _ffi as F
 from .camera import Camera, CameraController
 from .jitter import MAX_SUBDIVISION, jitters_for
-from .core import BspTree, Bvh, Context, Mesh, make_uniform
+from .core import BspTree, Bvh, Context, Mesh, make_uniform, synth_texture
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(REPO, "assets", "models")
@@ -33,6 +36,9 @@ class RenderState:
         self.models_dir = models_dir
         self.bunny_standin = bunny_standin
         self.selection1 = selection1
+        self.selection2 = 0          # Uniform defaults, uniform.rs:152-156
+        self.use_texture = 0
+        self.uv_scale = (1.0, 1.0)
         self.env = env
         self.resolution = resolution
         self.device_build = device_build   # build the BSP / HLBVH on the GPU (same arrays)
@@ -53,17 +59,29 @@ class RenderState:
         from .core import load_texture_rgba8
         return load_texture_rgba8(path)
 
+    def _texture0(self):
+        """render_state.rs:176-189: texture0 (grass.jpg), or its stand-in."""
+        path = os.path.join(REPO, "assets", "textures", "grass.jpg")
+        if os.path.exists(path):
+            from .core import load_texture_rgba8
+            return load_texture_rgba8(path)
+        return synth_texture()
+
     # render_state.rs:161-265
     def setup_rendering(self, scene):
-        if scene.render_mode is None:
+        if (scene.render_mode or scene.analytic_mode) is None:
             raise F.RtError(F.RT_E_UNSUPPORTED, f"{scene.shader} is outside the hot path (SURVEY.md section 2)")
         self.scene = scene
         self.camera = Camera.from_tuple(scene.camera)
-        self.mode = scene.render_mode
+        self.mode = scene.render_mode or scene.analytic_mode
         self.width, self.height = self.resolution or scene.res
         self.mesh = self.bsp = self.bvh = None
         if self.mode == "W1E6":
             self.trav = "NONE"
+        elif self.mode in F.ANALYTIC_MODES:
+            # the analytic W2 / W3 scenes: no mesh; the W3 ones sample texture0
+            self.trav = "NONE"
+            self.ctx.set_texture(self._texture0() if self.mode in F.TEXTURED_MODES else None)
         elif self.mode in F.SWEEP_MODES:
             # the brute-force W5 scenes: the mesh alone, no tree (w5e2.wgsl:230-239)
             self.trav = "NONE"
@@ -116,7 +134,8 @@ class RenderState:
         eye, target, up, constant = self.camera.as_args()
         self.uniform = make_uniform(eye, target, up, constant, self.width, self.height,
                                     selection1=self.selection1, iteration=self.iteration,
-                                    subdiv=self.subdivision_level)
+                                    subdiv=self.subdivision_level, selection2=self.selection2,
+                                    use_texture=self.use_texture, uv_scale=self.uv_scale)
         # UniformGpu::update_buffer (uniform.rs:163-175): the jitter table with the uniforms
         self.ctx.set_uniforms(self.uniform, jitters_for(self.height, self.subdivision_level))
 
@@ -124,6 +143,19 @@ class RenderState:
         """Uniform::update_subdivision_level (uniform.rs:122-129): clamped to 10;
         W6E1/PROJECT take level^2 stratified samples per pixel."""
         self.subdivision_level = min(int(level), MAX_SUBDIVISION)
+
+    def set_sphere_material(self, shader):
+        """Command::SetSphereMaterial (lib.rs:404-408): selection1, at the next update()."""
+        self.selection1 = int(shader)
+
+    def set_other_material(self, shader):
+        """Command::SetOtherMaterial (lib.rs:409-411): selection2, at the next update()."""
+        self.selection2 = int(shader)
+
+    def set_texture(self, use, uv_scale):
+        """Command::SetTexture (lib.rs:415-421): use_texture and uv_scale, at the next update()."""
+        self.use_texture = int(use)
+        self.uv_scale = (float(uv_scale[0]), float(uv_scale[1]))
 
     def input(self, key, pressed=True):
         """RenderState::input_alt (render_state.rs:462-465): a key event for the

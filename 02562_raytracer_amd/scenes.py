@@ -36,6 +36,21 @@ SWEEP_MODES = {
     "w5e5.wgsl": "W5E5",
 }
 
+# shader file -> rt_mode name of the analytic worksheet-2 and worksheet-3 scenes:
+# W1E6's three objects with the control panel's materials, bounces and (W3) the
+# plane's texture (RT_TRAVERSE_NONE, no mesh).  Kept apart for the same reason.
+ANALYTIC_MODES = {
+    "w2e1.wgsl": "W2E1",
+    "w2e2.wgsl": "W2E2",
+    "w2e3.wgsl": "W2E3",
+    "w2e4.wgsl": "W2E4",
+    "w2e5.wgsl": "W2E5",
+    "w3e1.wgsl": "W3E1",
+    "w3e2.wgsl": "W3E2",
+    "w3e3.wgsl": "W3E3",
+    "w3e4.wgsl": "W3E4",
+}
+
 
 @dataclass(frozen=True)
 class Camera:
@@ -67,6 +82,12 @@ class SceneDescriptor:
         """The rt_mode that renders the scene: `mode`, or else the sweep mode
         (None = no kernel restates the shader)."""
         return self.mode or SWEEP_MODES.get(self.shader)
+
+    @property
+    def analytic_mode(self):
+        """The rt_mode of an analytic W2 / W3 scene (None for every other scene);
+        a RenderState renders `render_mode or analytic_mode`."""
+        return ANALYTIC_MODES.get(self.shader)
 
     def with_(self, **kw):
         return replace(self, **kw)

@@ -94,6 +94,9 @@ struct SceneDescriptor {   /* :20-44 */
     /* the rt_mode that renders the scene: mode(), or else the triangle-sweep mode
      * of the brute-force W5 scenes (RT_MODE_W5E2..W5E5, RT_TRAVERSE_NONE, no tree) */
     std::optional<rt_mode> render_mode() const;
+    /* the rt_mode of an analytic W2 / W3 scene (RT_MODE_W2E1..W3E4, RT_TRAVERSE_NONE, no
+     * mesh), nullopt for every other scene; a RenderState renders render_mode() or else this */
+    std::optional<rt_mode> analytic_mode() const;
 };
 
 std::vector<SceneDescriptor> get_scenes();            /* :46-488, the 44 scenes in order */
@@ -103,8 +106,13 @@ const SceneDescriptor& find_scene(const std::string& name);
 constexpr uint32_t MAX_SUBDIVISION = 10;
 /* compute_jitters (:254-277): PCG32 Lcg64Xsh32::new(0, 0), rand's f64 gen_range */
 std::vector<std::array<float, 2>> compute_jitters(double pixel_size, uint32_t subdivs);
+/* selection2, use_texture and uv_scale default to the reference's (:152-156) */
 rt_uniform make_uniform(const Camera& cam, uint32_t width, uint32_t height, uint32_t selection1 = 0,
-                        uint32_t subdivision_level = 1, uint32_t iteration = 0);
+                        uint32_t subdivision_level = 1, uint32_t iteration = 0, uint32_t selection2 = 0,
+                        uint32_t use_texture = 0, std::array<float, 2> uv_scale = {1.0f, 1.0f});
+/* deterministic stand-in for res/textures/grass.jpg (not redistributed): size x size
+ * RGBA8 texels, the same integer arithmetic as core.synth_texture() */
+std::vector<uint8_t> synth_texture(uint32_t size = 64);
 
 /* PCG32 (XSH RR), as rand_pcg 0.3.1's Lcg64Xsh32 */
 class Lcg64Xsh32 {
@@ -158,7 +166,13 @@ public:
     void update_camera_constant(float constant);     /* :591-593 */
     void set_samples(uint32_t samples, bool enabled);   /* Command::SetSamples, lib.rs:472-479 */
     void set_subdivision_level(uint32_t level);      /* uniform.rs:122-129 */
-    void set_selection1(uint32_t shader);            /* Command::SetSphereMaterial, lib.rs:405-409 */
+    void set_selection1(uint32_t shader);            /* Command::SetSphereMaterial, lib.rs:404-408 */
+    void set_sphere_material(uint32_t shader) { set_selection1(shader); }
+    void set_other_material(uint32_t shader);        /* Command::SetOtherMaterial, lib.rs:409-411 */
+    void set_texture(uint32_t use_texture, std::array<float, 2> uv_scale);   /* Command::SetTexture, lib.rs:415-421 */
+    /* texture0 of the W3 scenes, decoded by the caller (render_state.rs:179-189): RGBA8
+     * texels, row 0 at v = 0; setup_rendering installs synth_texture() for them */
+    void set_texture_image(const uint8_t* rgba8, uint32_t width, uint32_t height);
     /* the scene's background_hdri, decoded by the caller (render_state.rs:191-206):
      * RGBA8 equirectangular texels, or nullptr for the constant environment */
     void set_environment_map(const uint8_t* rgba8, uint32_t width, uint32_t height);
@@ -180,6 +194,7 @@ public:
     uint32_t iteration() const { return iteration_; }
     const Camera& camera() const { return camera_; }
     const SceneDescriptor& scene() const { return scene_; }
+    rt_mode mode() const { return mode_; }   /* the rt_mode this state renders */
     rt_ray_counts last_counts() const;
 
 private:
@@ -195,6 +210,8 @@ private:
     rt_traverse trav_ = RT_TRAVERSE_BSP;
     uint32_t width_ = 0, height_ = 0;
     uint32_t iteration_ = 0, max_iterations_ = 2, subdivision_ = 1, selection1_ = 0;
+    uint32_t selection2_ = 0, use_texture_ = 0;
+    std::array<float, 2> uv_scale_{1.0f, 1.0f};
     bool progressive_ = true;
     void* accum_ = nullptr;
     void* ids_ = nullptr;

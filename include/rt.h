@@ -107,14 +107,31 @@ typedef enum rt_mode {
     RT_MODE_W5E2    = 14, /* res/shaders/w5e2.wgsl: flat normals, directional light, one shadow sweep per hit */
     RT_MODE_W5E3    = 15, /* res/shaders/w5e3.wgsl: interpolated vertex normals, directional light, no shadow rays */
     RT_MODE_W5E4    = 16, /* res/shaders/w5e4.wgsl: material diffuse + ambient; no 1/subdiv^2 multiplier */
-    RT_MODE_W5E5    = 17  /* res/shaders/w5e5.wgsl: every area-light centre, one shadow sweep per light and hit */
+    RT_MODE_W5E5    = 17, /* res/shaders/w5e5.wgsl: every area-light centre, one shadow sweep per light and hit */
+    /* The analytic worksheet-2 and worksheet-3 scenes: W1E6's triangle, sphere and plane with the
+     * control panel's materials (uniforms.selection1: the sphere, selection2: the plane; 0 Lambertian,
+     * 1 Phong, 2 mirror, 3 transmit, 4 glossy, 5 normal, 6 base colour -- a value the file's switch
+     * does not know shades (0.7, 0, 0.7)), up to ten bounces, and from W3E1 on texture0 on the plane
+     * (uniforms.use_texture, uv_scale; rt_set_texture).  intersect_scene takes the FIRST of triangle,
+     * sphere, plane whose test accepts, not the closest.  RT_TRAVERSE_NONE only; no mesh, BSP or BVH.
+     * One frame per call (first_iter and spp are not read).  DESIGN.md "Analytic worksheet scenes". */
+    RT_MODE_W2E1    = 18, /* res/shaders/w2e1.wgsl: Lambertian everywhere (selections not read), black sphere */
+    RT_MODE_W2E2    = 19, /* res/shaders/w2e2.wgsl: + selection1 / selection2, mirror (restarts at the hit point) */
+    RT_MODE_W2E3    = 20, /* res/shaders/w2e3.wgsl: + transmit (ior 1.5), mirror offset by normal * 1e-5 */
+    RT_MODE_W2E4    = 21, /* res/shaders/w2e4.wgsl: + Phong (specular 0.1, shininess 42), ior 1.4, diffuse x 0.9 */
+    RT_MODE_W2E5    = 22, /* res/shaders/w2e5.wgsl: + glossy (Phong + transmit), transmit offset by w_t * 1e-5 */
+    RT_MODE_W3E1    = 23, /* res/shaders/w3e1.wgsl: + texture0 on the plane, uv0 not wrapped (ClampToEdge) */
+    RT_MODE_W3E2    = 24, /* res/shaders/w3e2.wgsl: uv0 % 1, fract(uv0 * uv_scale) */
+    RT_MODE_W3E3    = 25, /* res/shaders/w3e3.wgsl: + subdivision_level^2 jittered samples */
+    RT_MODE_W3E4    = 26  /* res/shaders/w3e4.wgsl: use_texture picks the sampler (1, 2 linear; 3 nearest), diffuse x 1 */
 } rt_mode;
 
 /* SceneDescriptor.traverse_type, src/scenes.rs:13-17 */
 typedef enum rt_traverse {
     RT_TRAVERSE_BSP  = 0,
     RT_TRAVERSE_BVH  = 1,
-    RT_TRAVERSE_NONE = 2   /* only valid with RT_MODE_W1E6 (analytic) and RT_MODE_W5E2..W5E5 (triangle sweep) */
+    RT_TRAVERSE_NONE = 2   /* only valid with RT_MODE_W1E6 and RT_MODE_W2E1..W3E4 (analytic) and with
+                              RT_MODE_W5E2..W5E5 (triangle sweep); those modes take no other traversal */
 } rt_traverse;
 
 /* A rectangle of the frame in GLOBAL pixel coordinates. */
@@ -272,7 +289,7 @@ int rt_memset_device(rt_ctx* ctx, void* dst_dev, int value, size_t bytes);
 int rt_timer_start(rt_ctx* ctx);
 int rt_timer_stop(rt_ctx* ctx, float* ms);   /* synchronizes */
 
-/* Per-launch timing of the traversal kernels (k_path / k_primary / k_w1e6 / k_sweep),
+/* Per-launch timing of the traversal kernels (k_path / k_primary / k_w1e6 / k_sweep / k_analytic),
  * enabled by RT_OPT_KERNEL_TIMING: HIP events around every such launch on the
  * context stream.  rt_kernel_time synchronizes and returns the summed
  * duration and the number of launches since the last reset (reset != 0
@@ -394,6 +411,16 @@ int rt_set_environment(rt_ctx* ctx, const float rgb[3]);
  * NULL removes it (the constant of rt_set_environment applies again). */
 int rt_set_environment_map(rt_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32_t height);
 
+/* texture0 of the W3 scenes (the reference builds res/textures/grass.jpg into every
+ * RenderState: Rgba8Unorm, image.to_rgba8(), one mip level, ClampToEdge,
+ * src/bindings/texture.rs:98-141): width x height RGBA8 texels, row 0 at v = 0,
+ * copied to the device.  Sampled by texture_sample (w3e1.wgsl:189-193 ..
+ * w3e4.wgsl:196-215) as include/rt_detmath.h rt_det_tex_sample pins it.  NULL
+ * removes it; RT_E_INVALID for a zero size with data.  RT_MODE_W3E1..W3E4
+ * rendered with uniforms.use_texture > 0 and no texture give RT_E_NOT_READY;
+ * the W2 modes never read it. */
+int rt_set_texture(rt_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32_t height);
+
 /* ---- render (replaces RenderState::render, src/render_state.rs:483-561) -- */
 
 /* Trace `spp` progressive iterations first_iter .. first_iter+spp-1 for every
@@ -407,10 +434,12 @@ int rt_set_environment_map(rt_ctx* ctx, const uint8_t* rgba8, uint32_t width, ui
  *     in/out: holds the accumulation of iterations < first_iter (read when
  *     first_iter > 0; the RenderDestination texture, render_state.rs:541-555),
  *     and receives max(vec4(accum,1),0) (w7e3.wgsl:261-271).  For W1E6/W6E1/
- *     PROJECT and W5E2..W5E5 it receives the linear per-frame result (before
- *     pow(.,1.5)).
+ *     PROJECT, W5E2..W5E5 and W2E1..W3E4 it receives the linear per-frame
+ *     result (before pow(.,1.5)), alpha 1.
  *   primary_hit_ids: DEVICE or NULL, region.w*region.h u32: triangle index of
- *     the primary hit of the LAST traced iteration, UINT32_MAX on miss.
+ *     the primary hit of the LAST traced iteration, UINT32_MAX on miss.  The
+ *     analytic modes (W1E6, W2E1..W3E4) store the object the camera ray of the
+ *     last sample accepted: 0 triangle, 1 sphere, 2 plane.
  *   counts: host pointer or NULL; when non-NULL the call synchronizes and
  *     stores this launch's counters. */
 int rt_render(rt_ctx* ctx, rt_mode mode, rt_traverse trav, const rt_tile* region,

@@ -259,13 +259,12 @@ RT_HD float rt_det_atan2f(float y, float x)
  * magnification (Linear) filter is used for every lookup; texel weights and
  * the unorm conversion c/255 are f32, evaluated as written here. */
 RT_HD float rt_det__unorm8(unsigned int c) { return (float)c / 255.0f; }
-RT_HD void rt_det_env_sample(const unsigned int* tex, unsigned int w, unsigned int h, float dx, float dy, float dz,
-                             float* rgb)
+/* The magnification (Linear) filter with ClampToEdge at the continuous texel
+ * coordinates (x, y) = (s * w - 0.5, t * h - 0.5): the four texels around it,
+ * weights and unorm conversion in f32 as written, the first nch channels.  A
+ * NaN coordinate reads texel 0 (pinned).  Shared by every sampler below. */
+RT_HD void rt_det__bilinear(const unsigned int* tex, unsigned int w, unsigned int h, float x, float y, int nch, float* out)
 {
-    const float u = 0.5f * (1.0f + (1.0f / RT_DET_PIF) * rt_det_atan2f(dx, -dz));
-    const float v = 1.0f / RT_DET_PIF * rt_det_acosf(-dy);
-    const float s = u, t = 1.0f - v;
-    float x = s * (float)w - 0.5f, y = t * (float)h - 0.5f;
     x = x == x ? x : 0.0f;   /* NaN direction: texel 0 (pinned) */
     y = y == y ? y : 0.0f;
     const float fx = __builtin_floorf(x), fy = __builtin_floorf(y);
@@ -279,11 +278,19 @@ RT_HD void rt_det_env_sample(const unsigned int* tex, unsigned int w, unsigned i
     const unsigned int t00 = tex[(unsigned int)y0 * w + (unsigned int)x0], t10 = tex[(unsigned int)y0 * w + (unsigned int)x1];
     const unsigned int t01 = tex[(unsigned int)y1 * w + (unsigned int)x0], t11 = tex[(unsigned int)y1 * w + (unsigned int)x1];
     const float w00 = (1.0f - a) * (1.0f - b), w10 = a * (1.0f - b), w01 = (1.0f - a) * b, w11 = a * b;
-    for (int c = 0; c < 3; c++) {
+    for (int c = 0; c < nch; c++) {
         const unsigned int sh = 8u * (unsigned int)c;
-        rgb[c] = rt_det__unorm8((t00 >> sh) & 255u) * w00 + rt_det__unorm8((t10 >> sh) & 255u) * w10 +
+        out[c] = rt_det__unorm8((t00 >> sh) & 255u) * w00 + rt_det__unorm8((t10 >> sh) & 255u) * w10 +
                  rt_det__unorm8((t01 >> sh) & 255u) * w01 + rt_det__unorm8((t11 >> sh) & 255u) * w11;
     }
+}
+RT_HD void rt_det_env_sample(const unsigned int* tex, unsigned int w, unsigned int h, float dx, float dy, float dz,
+                             float* rgb)
+{
+    const float u = 0.5f * (1.0f + (1.0f / RT_DET_PIF) * rt_det_atan2f(dx, -dz));
+    const float v = 1.0f / RT_DET_PIF * rt_det_acosf(-dy);
+    const float s = u, t = 1.0f - v;
+    rt_det__bilinear(tex, w, h, s * (float)w - 0.5f, t * (float)h - 0.5f, 3, rgb);
 }
 
 /* environment_map of w9e2.wgsl:234-246: the same lookup on an RGBE-encoded
@@ -296,28 +303,44 @@ RT_HD void rt_det_env_sample_rgbe(const unsigned int* tex, unsigned int w, unsig
     const float u = 0.5f * (1.0f + (1.0f / RT_DET_PIF) * rt_det_atan2f(dx, -dz));
     const float v = 1.0f / RT_DET_PIF * rt_det_acosf(-dy);
     const float s = u, t = 1.0f - v;
-    float x = s * (float)w - 0.5f, y = t * (float)h - 0.5f;
-    x = x == x ? x : 0.0f;
-    y = y == y ? y : 0.0f;
-    const float fx = __builtin_floorf(x), fy = __builtin_floorf(y);
-    const float a = x - fx, b = y - fy;
-    int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    const int wm = (int)w - 1, hm = (int)h - 1;
-    x0 = x0 < 0 ? 0 : (x0 > wm ? wm : x0);
-    x1 = x1 < 0 ? 0 : (x1 > wm ? wm : x1);
-    y0 = y0 < 0 ? 0 : (y0 > hm ? hm : y0);
-    y1 = y1 < 0 ? 0 : (y1 > hm ? hm : y1);
-    const unsigned int t00 = tex[(unsigned int)y0 * w + (unsigned int)x0], t10 = tex[(unsigned int)y0 * w + (unsigned int)x1];
-    const unsigned int t01 = tex[(unsigned int)y1 * w + (unsigned int)x0], t11 = tex[(unsigned int)y1 * w + (unsigned int)x1];
-    const float w00 = (1.0f - a) * (1.0f - b), w10 = a * (1.0f - b), w01 = (1.0f - a) * b, w11 = a * b;
     float c4[4];
-    for (int c = 0; c < 4; c++) {
-        const unsigned int sh = 8u * (unsigned int)c;
-        c4[c] = rt_det__unorm8((t00 >> sh) & 255u) * w00 + rt_det__unorm8((t10 >> sh) & 255u) * w10 +
-                rt_det__unorm8((t01 >> sh) & 255u) * w01 + rt_det__unorm8((t11 >> sh) & 255u) * w11;
-    }
+    rt_det__bilinear(tex, w, h, s * (float)w - 0.5f, t * (float)h - 0.5f, 4, c4);
     const float e = rt_det_exp2f(c4[3] * 255.0f - 128.0f);
     for (int c = 0; c < 3; c++) rgb[c] = c4[c] * e;
+}
+
+/* texture_sample (res/shaders/w3e1.wgsl:189-193 .. w3e4.wgsl:196-215) on texture0,
+ * an RGBA8 (Rgba8Unorm, one mip level) texture of w x h texels, row 0 at v = 0,
+ * ClampToEdge (src/bindings/texture.rs:98-141), at the coordinates (u, v); the alpha
+ * channel is not read.  Pinned choices: as for hdri0 above, textureSample's LOD is
+ * implementation-defined inside the bounce loop and there is one mip level, so
+ * sampler0 (mag Linear, min Nearest) and sampler0_bilinear both use the Linear
+ * filter for every lookup (nearest == 0): x = u * w - 0.5 and the four texels of
+ * rt_det__bilinear.  sampler0_nearest (nearest != 0) reads the one texel
+ * floor(u * w), floor(v * h).  ClampToEdge: the texel coordinate is first clamped
+ * to [-1, w] (resp. [-1, h]), where every lookup already returns edge texels alone,
+ * so that the integer conversion is defined for every coordinate (W3E1 does not
+ * wrap its plane coordinates); a NaN coordinate reads texel 0. */
+RT_HD float rt_det__clamp_texel(float x, unsigned int n)
+{
+    x = x == x ? x : 0.0f;
+    return x < -1.0f ? -1.0f : (x > (float)n ? (float)n : x);
+}
+RT_HD void rt_det_tex_sample(const unsigned int* tex, unsigned int w, unsigned int h, float u, float v, int nearest,
+                             float* rgb)
+{
+    if (nearest) {
+        const int wm = (int)w - 1, hm = (int)h - 1;
+        int x = (int)__builtin_floorf(rt_det__clamp_texel(u * (float)w, w));
+        int y = (int)__builtin_floorf(rt_det__clamp_texel(v * (float)h, h));
+        x = x < 0 ? 0 : (x > wm ? wm : x);
+        y = y < 0 ? 0 : (y > hm ? hm : y);
+        const unsigned int t = tex[(unsigned int)y * w + (unsigned int)x];
+        for (int c = 0; c < 3; c++) rgb[c] = rt_det__unorm8((t >> (8u * (unsigned int)c)) & 255u);
+        return;
+    }
+    rt_det__bilinear(tex, w, h, rt_det__clamp_texel(u * (float)w - 0.5f, w), rt_det__clamp_texel(v * (float)h - 0.5f, h),
+                     3, rgb);
 }
 
 #endif /* RT02562_DETMATH_H */
