@@ -6,8 +6,8 @@ packed tiles are gathered to rank 0, and rank 0 scatters them into the frame
 
 The packed layout (include/rt.h rt_render_tiles): local tile l occupies pixels
 [l*64, l*64+64), row-major inside the tile; every rank holds
-rt_tileset_local_tiles(W, H, nranks) tiles (padding tiles past the frame are
-left untouched by the kernel and dropped by the unpack).
+rt_tileset_local_tiles(W, H, nranks) tiles.  What happens to the padding slots
+is stated there, once (tests/test_gpu_tiles.py pins it).
 """
 import numpy as np
 
@@ -22,7 +22,8 @@ def tile_of_seq(s, tx_n):
     """Tile (tx, ty) at sequence position s (include/rt.h rt_tileset): row-major,
     each row rotated by its index mod 8 (frames under 8 tiles wide: not rotated),
     so the ranks' tiles (s % nranks) form diagonal stripes instead of whole
-    columns when nranks divides 8 and the tile columns."""
+    columns when nranks divides 8 and the tile columns (whole columns remain
+    on the unrotated frames)."""
     ty = s // tx_n
     r = (ty & 7) if tx_n >= 8 else 0 * ty
     return (s % tx_n + r) % tx_n, ty

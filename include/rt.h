@@ -143,8 +143,10 @@ typedef struct rt_tile {
  * (SURVEY.md 8(e)): the tiles (ceil(W/8) x ceil(H/8)) are taken in sequence
  * s = ty * tiles_x + (tx - (ty & 7)) mod tiles_x -- row-major, each row rotated
  * by its index mod 8 (not rotated when tiles_x < 8) -- and sequence position s
- * is owned by rank s % nranks (diagonal stripes: when nranks divides 8 and
- * tiles_x, rank r owns tx = r + ty mod nranks).
+ * is owned by rank s % nranks (diagonal stripes: on a rotated frame, when
+ * nranks divides 8 and tiles_x, rank r owns tx = r + ty mod nranks; a frame
+ * under 8 tiles wide is not rotated, and rank r then owns the whole columns
+ * tx = r mod nranks).
  * Global pixel coordinates keep PRNG seeds, and therefore images, identical
  * for every nranks. */
 typedef struct rt_tileset {
@@ -450,7 +452,13 @@ int rt_render(rt_ctx* ctx, rt_mode mode, rt_traverse trav, const rt_tile* region
 /* Same, over the 8x8 tiles owned by `ts` (multi-GPU framebuffer tiling).
  * Outputs are PACKED: local tile l (the tile at sequence position
  * s = l*nranks + rank, rt_tileset above) occupies pixels [l*64, l*64+64),
- * row-major inside the tile.  Buffers hold rt_tileset_local_tiles() * 64 px. */
+ * row-major inside the tile: slot l*64 + (y & 7)*8 + (x & 7) holds pixel (x, y).
+ * Buffers hold rt_tileset_local_tiles() * 64 px.  Padding: a slot that holds no
+ * pixel of the frame -- the lanes of an edge tile past the right or bottom
+ * edge, and every slot of a local tile whose sequence position is past the
+ * last tile (ranks own ceil(ntiles / nranks) tiles each) -- is neither read
+ * nor written by this call and keeps what it held; rt_gather_tiles transfers
+ * it as it is and rt_unpack_tiles drops it. */
 int rt_render_tiles(rt_ctx* ctx, rt_mode mode, rt_traverse trav, const rt_tileset* ts,
                     uint32_t first_iter, uint32_t spp,
                     float* accum_rgba32f, uint32_t* primary_hit_ids,
