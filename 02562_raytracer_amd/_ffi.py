@@ -26,7 +26,8 @@ RT_E_UNSUPPORTED = -6
  RT_MODE_W9E2, RT_MODE_W6E2, RT_MODE_W7E1, RT_MODE_W7E2, RT_MODE_W6E3, RT_MODE_W9E3,
  RT_MODE_W5E2, RT_MODE_W5E3, RT_MODE_W5E4, RT_MODE_W5E5,
  RT_MODE_W2E1, RT_MODE_W2E2, RT_MODE_W2E3, RT_MODE_W2E4, RT_MODE_W2E5,
- RT_MODE_W3E1, RT_MODE_W3E2, RT_MODE_W3E3, RT_MODE_W3E4) = range(27)
+ RT_MODE_W3E1, RT_MODE_W3E2, RT_MODE_W3E3, RT_MODE_W3E4,
+ RT_MODE_W1E2, RT_MODE_W1E3, RT_MODE_W1E4, RT_MODE_W1E5) = range(31)
 RT_TRAVERSE_BSP, RT_TRAVERSE_BVH, RT_TRAVERSE_NONE = range(3)
 RT_OPT_DETAIL_COUNTERS = 1
 RT_OPT_WAVES_PER_CU = 2
@@ -48,13 +49,18 @@ MODES = {"W1E6": RT_MODE_W1E6, "W6E1": RT_MODE_W6E1, "PROJECT": RT_MODE_PROJECT,
          "W5E2": RT_MODE_W5E2, "W5E3": RT_MODE_W5E3, "W5E4": RT_MODE_W5E4, "W5E5": RT_MODE_W5E5,
          "W2E1": RT_MODE_W2E1, "W2E2": RT_MODE_W2E2, "W2E3": RT_MODE_W2E3, "W2E4": RT_MODE_W2E4,
          "W2E5": RT_MODE_W2E5, "W3E1": RT_MODE_W3E1, "W3E2": RT_MODE_W3E2, "W3E3": RT_MODE_W3E3,
-         "W3E4": RT_MODE_W3E4}
+         "W3E4": RT_MODE_W3E4,
+         "W1E2": RT_MODE_W1E2, "W1E3": RT_MODE_W1E3, "W1E4": RT_MODE_W1E4, "W1E5": RT_MODE_W1E5}
 # the brute-force W5 scenes: a triangle sweep over the mesh alone (RT_TRAVERSE_NONE, no BSP / BVH)
 SWEEP_MODES = ("W5E2", "W5E3", "W5E4", "W5E5")
 # the analytic W2 / W3 scenes: three constant objects, materials, bounces (RT_TRAVERSE_NONE, no mesh);
 # the W3 ones sample texture0 (rt_set_texture)
 ANALYTIC_MODES = ("W2E1", "W2E2", "W2E3", "W2E4", "W2E5", "W3E1", "W3E2", "W3E3", "W3E4")
 TEXTURED_MODES = ("W3E1", "W3E2", "W3E3", "W3E4")
+# the worksheet-1 scenes before W1E6: the uniforms alone (RT_TRAVERSE_NONE, no mesh); the shaders of
+# LINEAR_DISPLAY_MODES return their colour without pow(., 1.5) (rt_frame_rgba8_mode)
+WORKSHEET1_MODES = ("W1E2", "W1E3", "W1E4", "W1E5")
+LINEAR_DISPLAY_MODES = ("W1E2", "W1E3")
 # progressive path tracers (per-iteration samples folded in order)
 PATH_MODES = ("W7E3", "W9E1", "W8E1", "W8E2", "W8E3", "W9E2", "W7E1", "W7E2", "W9E3")
 TRAVERSALS = {"BSP": RT_TRAVERSE_BSP, "BVH": RT_TRAVERSE_BVH, "NONE": RT_TRAVERSE_NONE}
@@ -155,6 +161,7 @@ SIGNATURES = {
     "rt_timer_start": (C.c_int, [vp]),
     "rt_timer_stop": (C.c_int, [vp, f32p]),
     "rt_frame_rgba8": (C.c_int, [vp, vp, C.c_uint32, vp]),
+    "rt_frame_rgba8_mode": (C.c_int, [vp, C.c_int, vp, C.c_uint32, vp]),
     "rt_kernel_time": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), u32p]),
     "rt_gather_time": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), u32p]),
     "rt_build_bvh_device": (C.c_int, [vp, C.c_uint32, C.POINTER(BvhBuildTimes)]),

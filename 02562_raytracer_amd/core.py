@@ -490,9 +490,15 @@ class Context:
         self._chk(F.lib().rt_timer_stop(self._h, C.byref(ms)))
         return ms.value
 
-    def frame_rgba8(self, accum_ptr, npix, out_ptr):
-        """Display transform of npix accumulated pixels into 8-bit sRGB RGBA (device pointers)."""
-        self._chk(F.lib().rt_frame_rgba8(self._h, C.c_void_p(accum_ptr), npix, C.c_void_p(out_ptr)))
+    def frame_rgba8(self, accum_ptr, npix, out_ptr, mode=None):
+        """Display transform of npix accumulated pixels into 8-bit sRGB RGBA (device pointers).
+        mode: the rt_mode that rendered them (rt_frame_rgba8_mode: W1E2 and W1E3 are
+        displayed without the pow); None: rt_frame_rgba8."""
+        if mode is None:
+            self._chk(F.lib().rt_frame_rgba8(self._h, C.c_void_p(accum_ptr), npix, C.c_void_p(out_ptr)))
+        else:
+            self._chk(F.lib().rt_frame_rgba8_mode(self._h, F.MODES.get(mode, mode), C.c_void_p(accum_ptr), npix,
+                                                  C.c_void_p(out_ptr)))
 
     def kernel_time(self, reset=True):
         """(summed ms, launches) of the traversal-kernel launches timed since the

@@ -930,7 +930,8 @@ static hipEvent_t gather_event(rt_ctx* c, hipStream_t s)
 // Launch the traversal kernel, bracketed by a pair of pooled events when
 // kernel timing is on (rt_kernel_time).
 static int launch_timed(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_mode mode, rt_traverse trav,
-                        const rtk::SweepScene* sweep = nullptr, const rtk::AnalyticTex* analytic = nullptr)
+                        const rtk::SweepScene* sweep = nullptr, const rtk::AnalyticTex* analytic = nullptr,
+                        bool worksheet1 = false)
 {
     const bool t = c->ktiming && c->kused + 2 <= 8192;
     if (t) {
@@ -941,9 +942,10 @@ static int launch_timed(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch&
         }
         HIPCHK(c, hipEventRecord(c->kev[c->kused], c->stream));
     }
-    int r = analytic ? rtk::launch_analytic(*analytic, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
-            : sweep  ? rtk::launch_sweep(*sweep, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
-                     : rtk::launch_render(S, L, mode, trav, c->detail, c->num_cus, c->waves_per_cu, c->stream);
+    int r = worksheet1 ? rtk::launch_worksheet1(L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
+            : analytic ? rtk::launch_analytic(*analytic, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
+            : sweep    ? rtk::launch_sweep(*sweep, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
+                       : rtk::launch_render(S, L, mode, trav, c->detail, c->num_cus, c->waves_per_cu, c->stream);
     if (r) return fail(c, r, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
     if (t) {
         HIPCHK(c, hipEventRecord(c->kev[c->kused + 1], c->stream));
@@ -1297,7 +1299,9 @@ static int probe_launch(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch&
 static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaunch& L, rt_ray_counts* counts)
 {
     if (!c->has_u) return fail(c, RT_E_NOT_READY, "rt_render: uniforms not set");
-    if (mode < RT_MODE_W1E6 || mode > RT_MODE_W3E4) return fail(c, RT_E_INVALID, "rt_render: bad mode");
+    if (mode < RT_MODE_W1E6 || mode > RT_MODE_W1E5) return fail(c, RT_E_INVALID, "rt_render: bad mode");
+    // the worksheet-1 scenes before W1E6: the uniforms alone (rt_worksheet1.hip)
+    const bool worksheet1 = mode >= RT_MODE_W1E2 && mode <= RT_MODE_W1E5;
     // the analytic W2 / W3 scenes: three constant objects, no mesh (rt_analytic.hip)
     const bool analytic = mode >= RT_MODE_W2E1 && mode <= RT_MODE_W3E4;
     // the brute-force W5 scenes: the triangle sweep over the mesh alone (rt_sweep.hip)
@@ -1309,6 +1313,9 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
                       mode == RT_MODE_W8E3 || mode == RT_MODE_W9E2 || mode == RT_MODE_W9E3;
     if (mode == RT_MODE_W1E6) {
         if (trav != RT_TRAVERSE_NONE) return fail(c, RT_E_UNSUPPORTED, "W1E6 is analytic: traverse must be NONE");
+    } else if (worksheet1) {
+        if (trav != RT_TRAVERSE_NONE)
+            return fail(c, RT_E_UNSUPPORTED, "W1E2..W1E5 are analytic: traverse must be NONE");
     } else if (analytic) {
         if (trav != RT_TRAVERSE_NONE)
             return fail(c, RT_E_UNSUPPORTED, "W2E1..W3E4 are analytic: traverse must be NONE");
@@ -1461,6 +1468,9 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
         W.nlights = c->nlights;
         HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
         if (int r = launch_timed(c, S, L, mode, trav, &W)) return r;
+    } else if (worksheet1) {
+        HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
+        if (int r = launch_timed(c, S, L, mode, trav, nullptr, nullptr, true)) return r;
     } else {
         HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
         if (int r = launch_timed(c, S, L, mode, trav)) return r;
@@ -1563,6 +1573,20 @@ int rt_frame_rgba8(rt_ctx* c, const float* accum_rgba32f, uint32_t npix, uint8_t
     if (rtk::launch_frame(reinterpret_cast<const float4*>(accum_rgba32f), npix, c->srgb_thr.as<float>(),
                           reinterpret_cast<uchar4*>(frame_rgba8), c->stream))
         return fail(c, RT_E_DEVICE, "rt_frame_rgba8: launch failed");
+    return RT_OK;
+}
+
+int rt_frame_rgba8_mode(rt_ctx* c, rt_mode mode, const float* accum_rgba32f, uint32_t npix, uint8_t* frame_rgba8)
+{
+    if (!c || (!accum_rgba32f && npix) || (!frame_rgba8 && npix)) return RT_E_INVALID;
+    if (mode < RT_MODE_W1E6 || mode > RT_MODE_W1E5) return fail(c, RT_E_INVALID, "rt_frame_rgba8_mode: bad mode");
+    // every shader but w1e2.wgsl and w1e3.wgsl ends in pow(result, 1.5)
+    if (mode != RT_MODE_W1E2 && mode != RT_MODE_W1E3) return rt_frame_rgba8(c, accum_rgba32f, npix, frame_rgba8);
+    if (int r = rt_frame_rgba8(c, nullptr, 0, nullptr)) return r;   // binds the device and uploads the thresholds
+    if (npix == 0) return RT_OK;
+    if (rtk::launch_frame_linear(reinterpret_cast<const float4*>(accum_rgba32f), npix, c->srgb_thr.as<float>(),
+                                 reinterpret_cast<uchar4*>(frame_rgba8), c->stream))
+        return fail(c, RT_E_DEVICE, "rt_frame_rgba8_mode: launch failed");
     return RT_OK;
 }
 

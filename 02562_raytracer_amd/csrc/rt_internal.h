@@ -1,5 +1,5 @@
 // rt_internal.h -- launch interface between the C ABI layer (rt_api.cpp) and
-// the gfx950 kernels (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip).  Not part of the public ABI.
+// the gfx950 kernels (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -139,6 +139,11 @@ struct AnalyticTex {
 int launch_analytic(const AnalyticTex& t, const DevLaunch& l, rt_mode mode, bool detail, int num_cus, int waves_per_cu,
                     hipStream_t stream);
 
+// RT_MODE_W1E2 .. RT_MODE_W1E5 (RT_TRAVERSE_NONE; rt_worksheet1.hip k_w1): the uniforms alone,
+// no scene block; detail = counting instantiation.
+int launch_worksheet1(const DevLaunch& l, rt_mode mode, bool detail, int num_cus, int waves_per_cu,
+                      hipStream_t stream);
+
 // Launch the kernel for (mode, trav); detail = counting instantiation.
 int launch_render(const DevScene& s, const DevLaunch& l, rt_mode mode, rt_traverse trav, bool detail,
                   int num_cus, int waves_per_cu, hipStream_t stream);
@@ -160,6 +165,9 @@ int launch_fold(const DevLaunch& l, hipStream_t stream);
 
 // display frame: RGBA32F accum -> 8-bit sRGB (thr: 255 device floats, srgb_code_thresholds)
 int launch_frame(const float4* accum, uint32_t npix, const float* thr, uchar4* out, hipStream_t stream);
+// the same without the pow, for the modes whose shader returns its colour as it is
+// (RT_MODE_W1E2, RT_MODE_W1E3; rt_worksheet1.hip k_frame_linear)
+int launch_frame_linear(const float4* accum, uint32_t npix, const float* thr, uchar4* out, hipStream_t stream);
 
 int launch_unpack(uint32_t width, uint32_t height, uint32_t nranks, uint32_t local_tiles,
                   const float4* packed_accum, const uint32_t* packed_ids, float4* frame_accum,

@@ -134,6 +134,15 @@ std::optional<rt_mode> SceneDescriptor::analytic_mode() const
     return std::nullopt;
 }
 
+std::optional<rt_mode> SceneDescriptor::worksheet1_mode() const
+{
+    if (shader == "w1e2.wgsl") return RT_MODE_W1E2;
+    if (shader == "w1e3.wgsl") return RT_MODE_W1E3;
+    if (shader == "w1e4.wgsl") return RT_MODE_W1E4;
+    if (shader == "w1e5.wgsl") return RT_MODE_W1E5;
+    return std::nullopt;   // w1e1.wgsl, the blank template, stays unrendered
+}
+
 std::vector<SceneDescriptor> get_scenes()
 {
     // cameras, scenes.rs:47-85 (aspect comes from the frame)
@@ -383,7 +392,9 @@ void RenderState::alloc_tiles()
 
 void RenderState::setup_rendering(const SceneDescriptor& scene)
 {
-    const auto m = scene.render_mode() ? scene.render_mode() : scene.analytic_mode();
+    const auto m = scene.render_mode()     ? scene.render_mode()
+                   : scene.analytic_mode() ? scene.analytic_mode()
+                                           : scene.worksheet1_mode();
     if (!m) throw Error(RT_E_UNSUPPORTED, scene.shader + " is outside the hot path (SURVEY.md section 2)");
     scene_ = scene;
     camera_ = scene.camera;
@@ -391,8 +402,8 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
     width_ = opts_.resolution ? opts_.resolution->first : scene.res.first;
     height_ = opts_.resolution ? opts_.resolution->second : scene.res.second;
     rt_ctx* c = gpu_.ctx();
-    if (mode_ == RT_MODE_W1E6) {
-        trav_ = RT_TRAVERSE_NONE;
+    if (mode_ == RT_MODE_W1E6 || (mode_ >= RT_MODE_W1E2 && mode_ <= RT_MODE_W1E5)) {
+        trav_ = RT_TRAVERSE_NONE;   // the worksheet-1 scenes: the uniforms alone, no mesh
     } else if (mode_ >= RT_MODE_W2E1 && mode_ <= RT_MODE_W3E4) {
         // the analytic W2 / W3 scenes: no mesh; the W3 ones sample texture0 (grass.jpg is
         // not redistributed and this layer decodes no JPEG: the stand-in, or set_texture_image)
@@ -550,7 +561,8 @@ std::vector<uint8_t> RenderState::frame_rgba8() const
     void* d = nullptr;
     gpu_.check(rt_device_alloc(gpu_.ctx(), npx * 4, &d), "frame buffer");
     std::vector<uint8_t> out(npx * 4);
-    int rc = rt_frame_rgba8(gpu_.ctx(), static_cast<const float*>(accum_), (uint32_t)npx, static_cast<uint8_t*>(d));
+    int rc = rt_frame_rgba8_mode(gpu_.ctx(), mode_, static_cast<const float*>(accum_), (uint32_t)npx,
+                                 static_cast<uint8_t*>(d));
     if (rc == RT_OK) rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), d, out.size());
     rt_device_free(gpu_.ctx(), d);
     gpu_.check(rc, "frame_rgba8");

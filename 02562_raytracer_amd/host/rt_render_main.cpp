@@ -97,6 +97,10 @@ static const char* mode_name(std::optional<rt_mode> m)
     case RT_MODE_W3E2: return "W3E2";
     case RT_MODE_W3E3: return "W3E3";
     case RT_MODE_W3E4: return "W3E4";
+    case RT_MODE_W1E2: return "W1E2";
+    case RT_MODE_W1E3: return "W1E3";
+    case RT_MODE_W1E4: return "W1E4";
+    case RT_MODE_W1E5: return "W1E5";
     }
     return nullptr;
 }
@@ -174,13 +178,14 @@ int main(int argc, char** argv)
                 const char* m = mode_name(s.mode());
                 const char* rm = mode_name(s.render_mode());
                 const char* am = mode_name(s.analytic_mode());
+                const char* wm = mode_name(s.worksheet1_mode());
                 std::printf("{\"name\":%s,\"shader\":%s,\"mode\":%s,\"render_mode\":%s,\"analytic_mode\":%s,"
-                            "\"model\":%s,\"res\":[%u,%u],"
+                            "\"worksheet1_mode\":%s,\"model\":%s,\"res\":[%u,%u],"
                             "\"vertex_type\":%s,"
                             "\"traverse_type\":%s,\"background_hdri\":%s,\"camera\":%s}\n",
                             jstr(s.name).c_str(), jstr(s.shader).c_str(), m ? jstr(m).c_str() : "null",
                             rm ? jstr(rm).c_str() : "null", am ? jstr(am).c_str() : "null",
-                            s.model ? jstr(*s.model).c_str() : "null", s.res.first, s.res.second,
+                            wm ? jstr(wm).c_str() : "null", s.model ? jstr(*s.model).c_str() : "null", s.res.first, s.res.second,
                             s.vertex_type == VertexType::Combined ? "\"Combined\"" : "\"Split\"",
                             s.traverse_type == TraverseType::Bsp ? "\"BSP\"" : "\"BVH\"",
                             s.background_hdri ? jstr(*s.background_hdri).c_str() : "null",

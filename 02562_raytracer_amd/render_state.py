@@ -69,14 +69,16 @@ class RenderState:
 
     # render_state.rs:161-265
     def setup_rendering(self, scene):
-        if (scene.render_mode or scene.analytic_mode) is None:
+        mode = scene.render_mode or scene.analytic_mode or scene.worksheet1_mode
+        if mode is None:
             raise F.RtError(F.RT_E_UNSUPPORTED, f"{scene.shader} is outside the hot path (SURVEY.md section 2)")
         self.scene = scene
         self.camera = Camera.from_tuple(scene.camera)
-        self.mode = scene.render_mode or scene.analytic_mode
+        self.mode = mode
         self.width, self.height = self.resolution or scene.res
         self.mesh = self.bsp = self.bvh = None
-        if self.mode == "W1E6":
+        if self.mode == "W1E6" or self.mode in F.WORKSHEET1_MODES:
+            # the worksheet-1 scenes: the uniforms alone, no mesh
             self.trav = "NONE"
         elif self.mode in F.ANALYTIC_MODES:
             # the analytic W2 / W3 scenes: no mesh; the W3 ones sample texture0
@@ -205,10 +207,10 @@ class RenderState:
 
     def frame_rgba8(self):
         """The displayed frame as the sRGB surface holds it: uint8 [H, W, 4]
-        (rt_frame_rgba8, on the device)."""
+        (rt_frame_rgba8_mode, on the device: W1E2 and W1E3 without the pow)."""
         npx = self.width * self.height
         out = self.ctx.alloc(npx * 4)
-        self.ctx.frame_rgba8(self.accum.ptr, npx, out.ptr)
+        self.ctx.frame_rgba8(self.accum.ptr, npx, out.ptr, mode=self.mode)
         img = out.to_numpy(np.uint8, (self.height, self.width, 4))
         out.free()
         return img
@@ -219,6 +221,8 @@ class RenderState:
         Image.fromarray(self.frame_rgba8(), "RGBA").save(path)
 
     @staticmethod
-    def display(accum):
-        """fs_main's frame output: saturate(pow(accum, 1.5)) (w7e3.wgsl:265)."""
-        return np.clip(np.power(np.maximum(accum[..., :3], 0), 1.5), 0, 1)
+    def display(accum, mode=None):
+        """fs_main's frame output: saturate(pow(accum, 1.5)) (w7e3.wgsl:265); for
+        mode W1E2 or W1E3, whose shaders return the colour as it is, saturate(accum)."""
+        x = np.maximum(accum[..., :3], 0)
+        return np.clip(x if mode in F.LINEAR_DISPLAY_MODES else np.power(x, 1.5), 0, 1)

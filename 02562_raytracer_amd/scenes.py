@@ -51,6 +51,16 @@ ANALYTIC_MODES = {
     "w3e4.wgsl": "W3E4",
 }
 
+# shader file -> rt_mode name of the worksheet-1 scenes before W1E6, partial steps
+# towards it (RT_TRAVERSE_NONE, no mesh).  Kept apart for the same reason.  w1e1.wgsl,
+# the blank template (constant black), has no mode: W1 E1 stays unrendered.
+WORKSHEET1_MODES = {
+    "w1e2.wgsl": "W1E2",
+    "w1e3.wgsl": "W1E3",
+    "w1e4.wgsl": "W1E4",
+    "w1e5.wgsl": "W1E5",
+}
+
 
 @dataclass(frozen=True)
 class Camera:
@@ -86,8 +96,14 @@ class SceneDescriptor:
     @property
     def analytic_mode(self):
         """The rt_mode of an analytic W2 / W3 scene (None for every other scene);
-        a RenderState renders `render_mode or analytic_mode`."""
+        a RenderState renders `render_mode or analytic_mode or worksheet1_mode`."""
         return ANALYTIC_MODES.get(self.shader)
+
+    @property
+    def worksheet1_mode(self):
+        """The rt_mode of W1 E2 .. W1 E5 (None for every other scene, W1 E1 included); a
+        RenderState renders `render_mode or analytic_mode or worksheet1_mode`."""
+        return WORKSHEET1_MODES.get(self.shader)
 
     def with_(self, **kw):
         return replace(self, **kw)

@@ -97,6 +97,10 @@ struct SceneDescriptor {   /* :20-44 */
     /* the rt_mode of an analytic W2 / W3 scene (RT_MODE_W2E1..W3E4, RT_TRAVERSE_NONE, no
      * mesh), nullopt for every other scene; a RenderState renders render_mode() or else this */
     std::optional<rt_mode> analytic_mode() const;
+    /* the rt_mode of W1 E2 .. W1 E5 (RT_MODE_W1E2..W1E5, RT_TRAVERSE_NONE, no mesh), nullopt for
+     * every other scene, W1 E1 (the blank template) included; a RenderState renders
+     * render_mode(), or else analytic_mode(), or else this */
+    std::optional<rt_mode> worksheet1_mode() const;
 };
 
 std::vector<SceneDescriptor> get_scenes();            /* :46-488, the 44 scenes in order */
@@ -187,7 +191,8 @@ public:
 
     std::vector<float> frame() const;        /* linear RGBA32F accumulation, H x W x 4 */
     std::vector<uint32_t> hit_ids() const;   /* primary-hit triangle ids, H x W */
-    std::vector<uint8_t> frame_rgba8() const;   /* the sRGB surface frame, H x W x 4 */
+    /* the sRGB surface frame, H x W x 4 (rt_frame_rgba8_mode: W1E2 and W1E3 without the pow) */
+    std::vector<uint8_t> frame_rgba8() const;
 
     uint32_t width() const { return width_; }
     uint32_t height() const { return height_; }

@@ -123,15 +123,25 @@ typedef enum rt_mode {
     RT_MODE_W3E1    = 23, /* res/shaders/w3e1.wgsl: + texture0 on the plane, uv0 not wrapped (ClampToEdge) */
     RT_MODE_W3E2    = 24, /* res/shaders/w3e2.wgsl: uv0 % 1, fract(uv0 * uv_scale) */
     RT_MODE_W3E3    = 25, /* res/shaders/w3e3.wgsl: + subdivision_level^2 jittered samples */
-    RT_MODE_W3E4    = 26  /* res/shaders/w3e4.wgsl: use_texture picks the sampler (1, 2 linear; 3 nearest), diffuse x 1 */
+    RT_MODE_W3E4    = 26, /* res/shaders/w3e4.wgsl: use_texture picks the sampler (1, 2 linear; 3 nearest), diffuse x 1 */
+    /* The worksheet-1 scenes before W1E6, partial steps towards it: the uniforms alone (selections,
+     * subdivision level and texture settings are not read).  W1E4 and W1E5 take the CLOSEST of triangle,
+     * sphere, plane, as W1E6 does (each accepted test lowers tmax for the next).  W1E2 and W1E3 return their
+     * colour without the pow(., 1.5) of every other shader: display them with rt_frame_rgba8_mode.
+     * RT_TRAVERSE_NONE only; no mesh, BSP or BVH.  One frame per call (first_iter and spp are treated as
+     * RT_MODE_W1E6 treats them).  W1E1, the blank template, has no mode.  DESIGN.md "Worksheet-1 scenes". */
+    RT_MODE_W1E2    = 27, /* res/shaders/w1e2.wgsl: the quad scaled by 0.9 in (0.1, 0.3, 0.6), the clear colour (0, 0, 0) around it; no ray */
+    RT_MODE_W1E3    = 28, /* res/shaders/w1e3.wgsl: the camera ray's direction as (q + 1) / 2; no aspect ratio, camera constant 1 */
+    RT_MODE_W1E4    = 29, /* res/shaders/w1e4.wgsl: W1E3's ray, closest hit, the base colour alone (background on a miss) */
+    RT_MODE_W1E5    = 30  /* res/shaders/w1e5.wgsl: as W1E4, the ray with the aspect ratio and the camera constant */
 } rt_mode;
 
 /* SceneDescriptor.traverse_type, src/scenes.rs:13-17 */
 typedef enum rt_traverse {
     RT_TRAVERSE_BSP  = 0,
     RT_TRAVERSE_BVH  = 1,
-    RT_TRAVERSE_NONE = 2   /* only valid with RT_MODE_W1E6 and RT_MODE_W2E1..W3E4 (analytic) and with
-                              RT_MODE_W5E2..W5E5 (triangle sweep); those modes take no other traversal */
+    RT_TRAVERSE_NONE = 2   /* only valid with RT_MODE_W1E6, RT_MODE_W1E2..W1E5 and RT_MODE_W2E1..W3E4 (analytic) and
+                              with RT_MODE_W5E2..W5E5 (triangle sweep); those modes take no other traversal */
 } rt_traverse;
 
 /* A rectangle of the frame in GLOBAL pixel coordinates. */
@@ -291,7 +301,7 @@ int rt_memset_device(rt_ctx* ctx, void* dst_dev, int value, size_t bytes);
 int rt_timer_start(rt_ctx* ctx);
 int rt_timer_stop(rt_ctx* ctx, float* ms);   /* synchronizes */
 
-/* Per-launch timing of the traversal kernels (k_path / k_primary / k_w1e6 / k_sweep / k_analytic),
+/* Per-launch timing of the traversal kernels (k_path / k_primary / k_w1e6 / k_sweep / k_analytic / k_w1),
  * enabled by RT_OPT_KERNEL_TIMING: HIP events around every such launch on the
  * context stream.  rt_kernel_time synchronizes and returns the summed
  * duration and the number of launches since the last reset (reset != 0
@@ -436,12 +446,13 @@ int rt_set_texture(rt_ctx* ctx, const uint8_t* rgba8, uint32_t width, uint32_t h
  *     in/out: holds the accumulation of iterations < first_iter (read when
  *     first_iter > 0; the RenderDestination texture, render_state.rs:541-555),
  *     and receives max(vec4(accum,1),0) (w7e3.wgsl:261-271).  For W1E6/W6E1/
- *     PROJECT, W5E2..W5E5 and W2E1..W3E4 it receives the linear per-frame
- *     result (before pow(.,1.5)), alpha 1.
+ *     PROJECT, W5E2..W5E5, W2E1..W3E4 and W1E2..W1E5 it receives the linear
+ *     per-frame result (before pow(.,1.5); W1E2 and W1E3 have none), alpha 1.
  *   primary_hit_ids: DEVICE or NULL, region.w*region.h u32: triangle index of
  *     the primary hit of the LAST traced iteration, UINT32_MAX on miss.  The
  *     analytic modes (W1E6, W2E1..W3E4) store the object the camera ray of the
- *     last sample accepted: 0 triangle, 1 sphere, 2 plane.
+ *     last sample accepted: 0 triangle, 1 sphere, 2 plane.  W1E4 and W1E5
+ *     store the closest object as W1E6 does; W1E2 and W1E3 store UINT32_MAX.
  *   counts: host pointer or NULL; when non-NULL the call synchronizes and
  *     stores this launch's counters. */
 int rt_render(rt_ctx* ctx, rt_mode mode, rt_traverse trav, const rt_tile* region,
@@ -474,6 +485,13 @@ uint32_t rt_tileset_local_tiles(uint32_t width, uint32_t height, uint32_t nranks
  * pow and the sRGB rounding are pinned here (the display path is outside
  * the parity contract). */
 int rt_frame_rgba8(rt_ctx* ctx, const float* accum_rgba32f, uint32_t npix, uint8_t* frame_rgba8);
+
+/* The displayed frame of `mode`'s fs_main.  w1e2.wgsl and w1e3.wgsl return their colour
+ * as it is, without the pow: for RT_MODE_W1E2 and RT_MODE_W1E3 the 8-bit code is the sRGB
+ * code of saturate(accum), by the same thresholds and rounding as rt_frame_rgba8.  For
+ * every other rt_mode the output is rt_frame_rgba8's, byte for byte.  NULL and empty
+ * arguments behave as rt_frame_rgba8's do; RT_E_INVALID for a value that is no rt_mode. */
+int rt_frame_rgba8_mode(rt_ctx* ctx, rt_mode mode, const float* accum_rgba32f, uint32_t npix, uint8_t* frame_rgba8);
 
 /* Scatter gathered packed buffers (nranks x local_tiles x 64 px, rank-major as
  * a gather to the root produces them) into a row-major W x H frame, on the context's
