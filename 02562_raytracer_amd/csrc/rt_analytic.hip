@@ -35,16 +35,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
-#include "rt_device_common.h"
+#include "rt_scene3.h"
 
 namespace rtk {
 
 namespace {
 
-constexpr float AN_ETA = 0.00001f;
-constexpr float AN_TMAX = 5000.0f;   // ray_init
+constexpr float AN_ETA = SCENE3_ETA;
 constexpr uint32_t AN_NONE = 0xFFFFFFFFu;
 constexpr int AN_MAX_DEPTH = 10;
 
@@ -79,56 +76,13 @@ struct AnMode {
     }
 };
 
-// intersect_triangle (w2e1.wgsl:206-236) on the scene's one triangle
-__device__ __forceinline__ bool an_triangle(const f3 o, const f3 w, f3& pos, f3& nrm)
-{
-    const f3 v0 = V(0.2f, 0.1f, 0.9f), v1 = V(-0.2f, 0.1f, -0.1f), v2 = V(-0.2f, 0.1f, 0.9f);
-    const f3 e0 = sub(v1, v0), e1 = sub(v2, v0), ov = sub(v0, o);
-    const f3 normal = cross(e0, e1);
-    const f3 nom = cross(ov, w);
-    const float denom = dot(w, normal);
-    if (rt_absf(denom) < 1e-6f) return false;
-    const float beta = dot(nom, e1) / denom;
-    const float gamma = -dot(nom, e0) / denom;
-    const float distance = dot(ov, normal) / denom;
-    if ((beta < 0.0f) | (gamma < 0.0f) | (beta + gamma > 1.0f) | (distance > AN_TMAX) | (distance < AN_ETA)) return false;
-    pos = add(o, muls(w, distance));
-    nrm = normalize(normal);
-    return true;
-}
-// intersect_sphere (w2e1.wgsl:238-264); the direction of a refracted ray is not a unit vector
-__device__ __forceinline__ bool an_sphere(const f3 o, const f3 w, f3& pos, f3& nrm)
-{
-    const f3 center = V(0.0f, 0.5f, 0.0f);
-    const float radius = 0.3f;
-    const f3 oc = sub(o, center);
-    const float a = dot(w, w);
-    const float b_over_2 = dot(oc, w);
-    const float c = dot(oc, oc) - radius * radius;
-    const float discriminant = b_over_2 * b_over_2 - a * c;
-    if (discriminant < 0.0f) return false;
-    const float disc_sqrt = rt_det_sqrtf(discriminant);
-    float root = (-b_over_2 - disc_sqrt) / a;
-    if ((root < AN_ETA) | (root > AN_TMAX)) {
-        root = (-b_over_2 + disc_sqrt) / a;
-        if ((root < AN_ETA) | (root > AN_TMAX)) return false;
-    }
-    pos = add(o, muls(w, root));
-    nrm = normalize(sub(pos, center));
-    return true;
-}
-// intersect_plane (w2e1.wgsl:191-204; w3e1.wgsl:241-257 and w3e2.wgsl:252-253 for uv0)
+// uv0 of a plane hit at pos (w3e1.wgsl:241-257, w3e2.wgsl:252-253)
 template <int MODE>
-__device__ __forceinline__ bool an_plane(const f3 o, const f3 w, f3& pos, f3& nrm, float& u, float& v)
+__device__ __forceinline__ void an_plane_uv(const f3 pos, float& u, float& v)
 {
-    const f3 tangent = V(-1.0f, 0.0f, 0.0f), binormal = V(0.0f, 0.0f, 1.0f), normal = V(0.0f, 1.0f, 0.0f);
-    const f3 position = V(0.0f, 0.0f, 0.0f);
-    const float distance = dot(sub(position, o), normal) / dot(w, normal);
-    if ((distance < AN_ETA) | (distance > AN_TMAX)) return false;
-    pos = add(o, muls(w, distance));
-    nrm = normal;
+    const f3 tangent = V(-1.0f, 0.0f, 0.0f), binormal = V(0.0f, 0.0f, 1.0f);
     if (AnMode<MODE>::w3) {
-        const f3 d = sub(pos, position);
+        const f3 d = sub(pos, scene3_plane_position());
         float pu = dot(d, tangent), pv = dot(d, binormal);
         if (AnMode<MODE>::wrap_uv) {   // WGSL %: the truncated remainder; exact with the divisor 1
             pu = pu - __builtin_truncf(pu);
@@ -137,49 +91,43 @@ __device__ __forceinline__ bool an_plane(const f3 o, const f3 w, f3& pos, f3& nr
         u = rt_absf(pu);
         v = rt_absf(pv);
     }
-    return true;
 }
 
 // intersect_scene + wrap_shader: the first object in the order triangle, sphere,
-// plane whose test accepts (0, 1, 2; AN_NONE: none).  On an accept the record is
-// overwritten; on a miss it is untouched.
+// plane whose test accepts (0, 1, 2; AN_NONE: none): every test sees the tmax the ray
+// came with.  On an accept the record is overwritten; on a miss it is untouched.
 template <int MODE>
 __device__ __forceinline__ uint32_t an_scene(const f3 o, const f3 w, uint32_t sel1, uint32_t sel2, bool plane_tex,
                                              AnHit& h)
 {
-    if (an_triangle(o, w, h.pos, h.nrm)) {
+    if (float dist; scene3_triangle(o, w, AN_ETA, SCENE3_TMAX, dist)) {
+        h.pos = add(o, muls(w, dist));
+        h.nrm = normalize(scene3_tri().normal);
         h.shader = 0u;   // the triangle is always Lambertian
         h.tex = false;
-        h.base = V(0.4f, 0.3f, 0.2f);
+        h.base = scene3_triangle_color();
         return 0u;
     }
-    if (an_sphere(o, w, h.pos, h.nrm)) {
+    if (float dist; scene3_sphere(o, w, AN_ETA, SCENE3_TMAX, scene3_center(), SCENE3_RADIUS, dist)) {
+        h.pos = add(o, muls(w, dist));
+        h.nrm = normalize(sub(h.pos, scene3_center()));
         h.shader = sel1;
         h.tex = false;
-        h.base = MODE == RT_MODE_W2E1 ? V(0.0f, 0.0f, 0.0f) : V(0.4f, 0.3f, 0.2f);
+        h.base = MODE == RT_MODE_W2E1 ? scene3_sphere_color() : scene3_triangle_color();
         return 1u;
     }
-    if (an_plane<MODE>(o, w, h.pos, h.nrm, h.u, h.v)) {
+    if (float dist; scene3_plane(o, w, AN_ETA, SCENE3_TMAX, dist)) {
+        h.pos = add(o, muls(w, dist));
+        h.nrm = scene3_plane_normal();
+        an_plane_uv<MODE>(h.pos, h.u, h.v);
         h.shader = sel2;
         h.tex = plane_tex;
-        h.base = plane_tex ? V(1.0f, 1.0f, 1.0f) : V(0.1f, 0.7f, 0.0f);   // wrap_shader: a textured hit is white
+        h.base = plane_tex ? V(1.0f, 1.0f, 1.0f) : scene3_plane_color();   // wrap_shader: a textured hit is white
         return 2u;
     }
     return AN_NONE;
 }
 
-struct AnLight {
-    f3 l_i, w_i;
-};
-__device__ __forceinline__ AnLight an_point_light(const f3 pos)
-{
-    const f3 intensity = muls(V(RT_PI_F, RT_PI_F, RT_PI_F), 5.0f);
-    AnLight l;
-    l.w_i = sub(V(0.0f, 1.2f, 0.0f), pos);
-    const float dist = dot(l.w_i, l.w_i);   // the squared length
-    l.l_i = divs(intensity, dist * dist);
-    return l;
-}
 __device__ __forceinline__ f3 an_reflect(const f3 i, const f3 n)
 {
     return sub(i, muls(n, 2.0f * dot(n, i)));
@@ -191,7 +139,7 @@ __device__ __forceinline__ f3 an_phong(const f3 eye, const AnHit& h)
 {
     const float specular = 0.1f, s = 42.0f;
     const f3 w_o = normalize(sub(eye, h.pos));
-    const AnLight light = an_point_light(h.pos);
+    const Scene3Light light = scene3_point_light(h.pos);
     const f3 w_r = normalize(an_reflect(neg(light.w_i), h.nrm));
     const float sat = rt_satf(dot(h.nrm, light.w_i));
     const f3 diffuse = divs(muls(light.l_i, sat), RT_PI_F);
@@ -245,13 +193,6 @@ __device__ __forceinline__ f3 an_texture(const AnalyticTex& T, const rt_uniform&
     return V(rgb[0], rgb[1], rgb[2]);
 }
 
-__device__ __forceinline__ unsigned long long an_wave_sum(unsigned long long s)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    return s;
-}
-
 }  // namespace
 
 // fs_main of the nine shaders.  MODE: RT_MODE_W2E1 .. RT_MODE_W3E4.  COUNT: the
@@ -268,7 +209,7 @@ __global__ void __launch_bounds__(256) k_analytic(AnalyticTex T, DevLaunch L)
     const uint32_t nsamp = M::multi ? subdiv * subdiv : 1u;   // the first seven shaders read neither
     const uint32_t sel1 = M::selections ? L.u.selection1 : 0u, sel2 = M::selections ? L.u.selection2 : 0u;
     const bool plane_tex = M::w3 && L.u.use_texture > 0u;
-    const f3 bg = V(0.1f, 0.3f, 0.6f);
+    const f3 bg = scene3_background();
     const float kd = M::diffuse_factor();
     uint32_t n_samples = 0, n_shadow = 0, n_bounce = 0;
 
@@ -324,7 +265,7 @@ __global__ void __launch_bounds__(256) k_analytic(AnalyticTex T, DevLaunch L)
                     const uint32_t sh = hit.shader;
                     if (sh == 0u) {
                         // lambertian: its shadow ray is the next trip
-                        const AnLight light = an_point_light(hit.pos);
+                        const Scene3Light light = scene3_point_light(hit.pos);
                         lam_n = hit.nrm;
                         lam_base = hit.base;
                         lam_li = light.l_i;
@@ -371,7 +312,7 @@ __global__ void __launch_bounds__(256) k_analytic(AnalyticTex T, DevLaunch L)
         L.accum[px.out] = make_float4(result.x, result.y, result.z, 1.0f);
         if (L.ids) L.ids[px.out] = prim;
     }
-    const unsigned long long s0 = an_wave_sum(n_samples), s2 = an_wave_sum(n_shadow), s3 = an_wave_sum(n_bounce);
+    const unsigned long long s0 = wave_sum(n_samples), s2 = wave_sum(n_shadow), s3 = wave_sum(n_bounce);
     if (lane == 0) {
         if (s0) {
             atomicAdd(L.counters + C_SAMPLES, s0);
@@ -382,33 +323,15 @@ __global__ void __launch_bounds__(256) k_analytic(AnalyticTex T, DevLaunch L)
     }
 }
 
-template <int MODE>
-static void launch_analytic_mode(const AnalyticTex& t, const DevLaunch& l, bool detail, int grid, hipStream_t st)
-{
-    if (detail) hipLaunchKernelGGL((k_analytic<MODE, true>), dim3(grid), dim3(256), 0, st, t, l);
-    else hipLaunchKernelGGL((k_analytic<MODE, false>), dim3(grid), dim3(256), 0, st, t, l);
-}
-
 int launch_analytic(const AnalyticTex& t, const DevLaunch& l, rt_mode mode, bool detail, int num_cus, int waves_per_cu,
                     hipStream_t stream)
 {
-    // persistent grid: four waves (tiles in flight) per block
-    const int wpc = waves_per_cu > 0 ? waves_per_cu : 16;
-    const long long cap = std::max(1LL, (long long)num_cus * wpc / 4);
-    const int grid = (int)std::min<long long>(cap, ((long long)l.nwork + 3) / 4);
+    const int grid = flat_grid(num_cus, waves_per_cu, l.nwork);
     if (grid <= 0) return RT_OK;
-    switch (mode) {
-    case RT_MODE_W2E1: launch_analytic_mode<RT_MODE_W2E1>(t, l, detail, grid, stream); break;
-    case RT_MODE_W2E2: launch_analytic_mode<RT_MODE_W2E2>(t, l, detail, grid, stream); break;
-    case RT_MODE_W2E3: launch_analytic_mode<RT_MODE_W2E3>(t, l, detail, grid, stream); break;
-    case RT_MODE_W2E4: launch_analytic_mode<RT_MODE_W2E4>(t, l, detail, grid, stream); break;
-    case RT_MODE_W2E5: launch_analytic_mode<RT_MODE_W2E5>(t, l, detail, grid, stream); break;
-    case RT_MODE_W3E1: launch_analytic_mode<RT_MODE_W3E1>(t, l, detail, grid, stream); break;
-    case RT_MODE_W3E2: launch_analytic_mode<RT_MODE_W3E2>(t, l, detail, grid, stream); break;
-    case RT_MODE_W3E3: launch_analytic_mode<RT_MODE_W3E3>(t, l, detail, grid, stream); break;
-    case RT_MODE_W3E4: launch_analytic_mode<RT_MODE_W3E4>(t, l, detail, grid, stream); break;
-    default: return RT_E_UNSUPPORTED;
-    }
+    const auto launch = [&](auto M, auto C) {
+        hipLaunchKernelGGL((k_analytic<decltype(M)::value, decltype(C)::value>), dim3(grid), dim3(256), 0, stream, t, l);
+    };
+    if (!with_mode<RT_MODE_W2E1, RT_MODE_W3E4>(mode, detail, launch)) return RT_E_UNSUPPORTED;
     return hipGetLastError() == hipSuccess ? RT_OK : RT_E_DEVICE;
 }
 

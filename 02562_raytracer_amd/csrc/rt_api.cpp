@@ -927,11 +927,11 @@ static hipEvent_t gather_event(rt_ctx* c, hipStream_t s)
     return e;
 }
 
-// Launch the traversal kernel, bracketed by a pair of pooled events when
-// kernel timing is on (rt_kernel_time).
-static int launch_timed(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_mode mode, rt_traverse trav,
-                        const rtk::SweepScene* sweep = nullptr, const rtk::AnalyticTex* analytic = nullptr,
-                        bool worksheet1 = false)
+// Run launch() -- one traversal-kernel launch on the context stream, returning an rt
+// status -- bracketed by a pair of pooled events when kernel timing is on
+// (rt_kernel_time).  what: the failure message's prefix.
+extern "C++" template <class Launch>
+static int launch_timed(rt_ctx* c, const char* what, Launch&& launch)
 {
     const bool t = c->ktiming && c->kused + 2 <= 8192;
     if (t) {
@@ -942,11 +942,7 @@ static int launch_timed(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch&
         }
         HIPCHK(c, hipEventRecord(c->kev[c->kused], c->stream));
     }
-    int r = worksheet1 ? rtk::launch_worksheet1(L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
-            : analytic ? rtk::launch_analytic(*analytic, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
-            : sweep    ? rtk::launch_sweep(*sweep, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream)
-                       : rtk::launch_render(S, L, mode, trav, c->detail, c->num_cus, c->waves_per_cu, c->stream);
-    if (r) return fail(c, r, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+    if (const int r = launch()) return fail(c, r, std::string(what) + hipGetErrorString(hipGetLastError()));
     if (t) {
         HIPCHK(c, hipEventRecord(c->kev[c->kused + 1], c->stream));
         c->kused += 2;
@@ -1119,23 +1115,10 @@ int rt_trace_batch(rt_ctx* c, rt_traverse trav, const float* rays_dev, const uin
     if (int r = set_dev(c)) return r;
     if (int r = ensure_hcam(c)) return r;
     const uint32_t T = c->shade_threshold >= 0 ? (uint32_t)c->shade_threshold & 0xFFu : 16u;
-    const bool t = c->ktiming && c->kused + 2 <= 8192;
-    if (t) {
-        while (c->kev.size() < c->kused + 2) {
-            hipEvent_t e;
-            HIPCHK(c, hipEventCreate(&e));
-            c->kev.push_back(e);
-        }
-        HIPCHK(c, hipEventRecord(c->kev[c->kused], c->stream));
-    }
-    const int r = rtk::launch_trace_batch(dev_scene(c), rays_dev, flags_dev, n, hits_dev, c->work.as<uint32_t>(),
-                                          T < 64u ? T : 63u, c->num_cus, c->stream);
-    if (r) return fail(c, r, std::string("rt_trace_batch: launch failed: ") + hipGetErrorString(hipGetLastError()));
-    if (t) {
-        HIPCHK(c, hipEventRecord(c->kev[c->kused + 1], c->stream));
-        c->kused += 2;
-    }
-    return RT_OK;
+    return launch_timed(c, "rt_trace_batch: launch failed: ", [&] {
+        return rtk::launch_trace_batch(dev_scene(c), rays_dev, flags_dev, n, hits_dev, c->work.as<uint32_t>(),
+                                       T < 64u ? T : 63u, c->num_cus, c->stream);
+    });
 }
 
 int rt_trace_rays(rt_ctx* c, rt_traverse trav, const float* rays, const uint32_t* flags, uint32_t n, rt_ray_hit* hits)
@@ -1276,11 +1259,21 @@ int rt_bsp_cull_in_use(rt_ctx* c, int* mode, float* probe_ms, uint32_t* probes)
     return RT_OK;
 }
 
+static const char* const kLaunchFailed = "kernel launch failed: ";
+
+// the tree-walk kernel of (mode, trav)
+static int launch_walk(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_mode mode, rt_traverse trav)
+{
+    return launch_timed(c, kLaunchFailed, [&] {
+        return rtk::launch_render(S, L, mode, trav, c->detail, c->num_cus, c->waves_per_cu, c->stream);
+    });
+}
+
 // a render launch; slot >= 0: the probe's launch `slot`, bracketed by its events
 static int probe_launch(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_mode mode, rt_traverse trav,
                         int slot)
 {
-    if (slot < 0) return launch_timed(c, S, L, mode, trav);
+    if (slot < 0) return launch_walk(c, S, L, mode, trav);
     for (hipEvent_t& e : c->auto_ev)
         if (!e) HIPCHK(c, hipEventCreate(&e));
     if (slot == 0) {
@@ -1288,7 +1281,7 @@ static int probe_launch(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch&
         c->probe_reach = eye_reach(c);
     }
     HIPCHK(c, hipEventRecord(c->auto_ev[2 * slot], c->stream));
-    if (int r = launch_timed(c, S, L, mode, trav)) return r;
+    if (int r = launch_walk(c, S, L, mode, trav)) return r;
     HIPCHK(c, hipEventRecord(c->auto_ev[2 * slot + 1], c->stream));
     c->probe_samples[slot] = (uint64_t)L.stride * L.spp;
     c->probe_n = (uint32_t)slot + 1;
@@ -1300,8 +1293,8 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
 {
     if (!c->has_u) return fail(c, RT_E_NOT_READY, "rt_render: uniforms not set");
     if (mode < RT_MODE_W1E6 || mode > RT_MODE_W1E5) return fail(c, RT_E_INVALID, "rt_render: bad mode");
-    // the worksheet-1 scenes before W1E6: the uniforms alone (rt_worksheet1.hip)
-    const bool worksheet1 = mode >= RT_MODE_W1E2 && mode <= RT_MODE_W1E5;
+    // the worksheet-1 scenes: the uniforms alone (rt_worksheet1.hip)
+    const bool worksheet1 = mode == RT_MODE_W1E6 || (mode >= RT_MODE_W1E2 && mode <= RT_MODE_W1E5);
     // the analytic W2 / W3 scenes: three constant objects, no mesh (rt_analytic.hip)
     const bool analytic = mode >= RT_MODE_W2E1 && mode <= RT_MODE_W3E4;
     // the brute-force W5 scenes: the triangle sweep over the mesh alone (rt_sweep.hip)
@@ -1311,11 +1304,10 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
     // progressive path tracers: per-iteration samples, folded in order by k_fold
     const bool path = mode == RT_MODE_W7E3 || mode == RT_MODE_W9E1 || mode == RT_MODE_W8E1 || mode == RT_MODE_W8E2 ||
                       mode == RT_MODE_W8E3 || mode == RT_MODE_W9E2 || mode == RT_MODE_W9E3;
-    if (mode == RT_MODE_W1E6) {
-        if (trav != RT_TRAVERSE_NONE) return fail(c, RT_E_UNSUPPORTED, "W1E6 is analytic: traverse must be NONE");
-    } else if (worksheet1) {
+    if (worksheet1) {
         if (trav != RT_TRAVERSE_NONE)
-            return fail(c, RT_E_UNSUPPORTED, "W1E2..W1E5 are analytic: traverse must be NONE");
+            return fail(c, RT_E_UNSUPPORTED, mode == RT_MODE_W1E6 ? "W1E6 is analytic: traverse must be NONE"
+                                                                  : "W1E2..W1E5 are analytic: traverse must be NONE");
     } else if (analytic) {
         if (trav != RT_TRAVERSE_NONE)
             return fail(c, RT_E_UNSUPPORTED, "W2E1..W3E4 are analytic: traverse must be NONE");
@@ -1454,7 +1446,10 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
         T.w = c->tex0_w;
         T.h = c->tex0_h;
         HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
-        if (int r = launch_timed(c, S, L, mode, trav, nullptr, &T)) return r;
+        if (int r = launch_timed(c, kLaunchFailed, [&] {
+                return rtk::launch_analytic(T, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream);
+            }))
+            return r;
     } else if (sweep) {
         rtk::SweepScene W;
         W.recs = c->sweep_recs.as<float4>();
@@ -1467,13 +1462,19 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
         W.nmats = c->nmats;
         W.nlights = c->nlights;
         HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
-        if (int r = launch_timed(c, S, L, mode, trav, &W)) return r;
+        if (int r = launch_timed(c, kLaunchFailed, [&] {
+                return rtk::launch_sweep(W, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream);
+            }))
+            return r;
     } else if (worksheet1) {
         HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
-        if (int r = launch_timed(c, S, L, mode, trav, nullptr, nullptr, true)) return r;
+        if (int r = launch_timed(c, kLaunchFailed, [&] {
+                return rtk::launch_worksheet1(L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream);
+            }))
+            return r;
     } else {
         HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
-        if (int r = launch_timed(c, S, L, mode, trav)) return r;
+        if (int r = launch_walk(c, S, L, mode, trav)) return r;
     }
     if (counts) return rt_last_counts(c, counts);
     return RT_OK;

@@ -1,7 +1,8 @@
 // rt_device_common.h -- device helpers shared by the kernel translation units
-// (rt_kernels.hip, rt_sweep.hip): the f32 vector math of the WGSL builtins, the
-// per-launch counters, the camera ray of get_camera_ray and the work mapping of
-// one 8x8 tile per wave.  Not part of the public ABI.
+// (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip): the f32 vector
+// math of the WGSL builtins, the per-launch counters and the wave sum, the camera ray
+// of get_camera_ray and the work mapping of one 8x8 tile per wave.  Not part of the
+// public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,6 +45,14 @@ struct Counters {
     uint32_t v[C_N];
 };
 
+// the sum of s over the wave's 64 lanes, in every lane
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long s)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    return s;
+}
+
 __device__ __forceinline__ void flush_counters(const Counters& c, unsigned long long* out, bool detail)
 {
     const int n = detail ? (int)C_N : 4;
@@ -52,6 +61,9 @@ __device__ __forceinline__ void flush_counters(const Counters& c, unsigned long 
         unsigned long long s = x;
         if (i == C_TRAV_CYC64 || i == C_SHADE_CYC64 || i == C_MEMWAIT_CYC64)
             s <<= 6;   // wave cycles, accumulated in units of 64
+        // wave_sum written out: inlined from the function, the first add's operands come
+        // out commuted, which tools/isa_compare.py reports as a change of every counting
+        // instantiation in rt_kernels.hip
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
         if ((threadIdx.x & 63u) == 0 && s) atomicAdd(out + i, s);

@@ -1,10 +1,14 @@
 // rt_internal.h -- launch interface between the C ABI layer (rt_api.cpp) and
-// the gfx950 kernels (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip).  Not part of the public ABI.
+// the gfx950 kernels (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip),
+// and what the launchers of the flat modes share: their grid and the expansion of a
+// run-time (mode, detail) into template constants.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "../../include/rt.h"
 
@@ -109,6 +113,37 @@ struct DevLaunch {
     unsigned long long cap_max;
 };
 
+// ---- the flat modes (RT_TRAVERSE_NONE): k_sweep, k_analytic, k_w1 ----
+// Their persistent grid: 256-thread blocks of four waves (tiles in flight), as many as
+// the device holds at waves_per_cu and no more than the launch has tiles for.
+inline int flat_grid(int num_cus, int waves_per_cu, uint32_t nwork)
+{
+    const int wpc = waves_per_cu > 0 ? waves_per_cu : 16;
+    const long long cap = std::max(1LL, (long long)num_cus * wpc / 4);
+    return (int)std::min<long long>(cap, ((long long)nwork + 3) / 4);
+}
+// Run-time values as template constants: f(std::bool_constant<b>), and
+// f(Int<mode>, std::bool_constant<detail>) for a mode in FIRST..LAST (false: outside).
+// A launcher instantiates its kernel from the arguments' types: k<decltype(M)::value, ..>.
+template <int N>
+using Int = std::integral_constant<int, N>;
+template <class F>
+void with_flag(bool b, F&& f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <int FIRST, int LAST, class F>
+bool with_mode(int mode, bool detail, F&& f)
+{
+    if constexpr (FIRST <= LAST) {
+        if (mode != FIRST) return with_mode<FIRST + 1, LAST>(mode, detail, f);
+        with_flag(detail, [&](auto count) { f(Int<FIRST>{}, count); });
+        return true;
+    }
+    return false;
+}
+
 // The scene of the brute-force W5 modes (rt_sweep.hip k_sweep), its own argument
 // block so that DevScene's layout stays as the other kernels were tuned for.
 // recs: one 48-B record {v0, e0 = v1 - v0, e1 = v2 - v0, n = cross(e0, e1)} per
@@ -139,8 +174,8 @@ struct AnalyticTex {
 int launch_analytic(const AnalyticTex& t, const DevLaunch& l, rt_mode mode, bool detail, int num_cus, int waves_per_cu,
                     hipStream_t stream);
 
-// RT_MODE_W1E2 .. RT_MODE_W1E5 (RT_TRAVERSE_NONE; rt_worksheet1.hip k_w1): the uniforms alone,
-// no scene block; detail = counting instantiation.
+// RT_MODE_W1E6 and RT_MODE_W1E2 .. RT_MODE_W1E5 (RT_TRAVERSE_NONE; rt_worksheet1.hip k_w1): the
+// uniforms alone, no scene block; detail = counting instantiation.
 int launch_worksheet1(const DevLaunch& l, rt_mode mode, bool detail, int num_cus, int waves_per_cu,
                       hipStream_t stream);
 

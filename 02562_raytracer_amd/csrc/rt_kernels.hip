@@ -38,7 +38,7 @@
 #include "../../include/rt_detmath.h"
 #include "rt_internal.h"
 // the f32 vector math, counters, camera ray and work mapping (shared with rt_sweep.hip)
-#include "rt_device_common.h"
+#include "rt_scene3.h"
 
 namespace rtk {
 
@@ -1156,27 +1156,6 @@ enum { PH_NEW = 0, PH_CLOSEST = 1, PH_SHADOW = 2 };
 #ifndef RT_PATH_WAVES_PER_EU
 #define RT_PATH_WAVES_PER_EU 8
 #endif
-// intersect_sphere (w1e6.wgsl / w8e1.wgsl:352-376): closest root in [tmin, tmax]
-__device__ __forceinline__ bool w1_sphere(f3 o, f3 w, float tmin, float& tmax, f3 center, float radius, f3& pos,
-                                          f3& nrm)
-{
-    const f3 oc = sub(o, center);
-    const float a = dot(w, w);
-    const float b2 = dot(oc, w);
-    const float c = dot(oc, oc) - radius * radius;
-    const float disc = b2 * b2 - a * c;
-    if (disc < 0.0f) return false;
-    const float ds = rt_det_sqrtf(disc);
-    float root = (-b2 - ds) / a;
-    if (root < tmin || root > tmax) {
-        root = (-b2 + ds) / a;
-        if (root < tmin || root > tmax) return false;
-    }
-    tmax = root;
-    pos = add(o, muls(w, root));
-    nrm = normalize(sub(pos, center));
-    return true;
-}
 // The two balls of intersect_scene_bsp (w8e1.wgsl:244-262), in its order: the
 // mirror ball, then the glass ball on the interval the first leaves.  id 0:
 // none, 1: mirror, 2: transparent (ior1_over_ior2 1.5).  The kernel tests them
@@ -1187,26 +1166,30 @@ struct W8Ball {
     float t;
     f3 pos, nrm;
 };
+// intersect_sphere (w8e1.wgsl:352-376) is the three-object scene's: the closest root in [tmin, b.t]
+__device__ __forceinline__ void w8_ball(f3 o, f3 w, float tmin, f3 center, uint32_t id, W8Ball& b)
+{
+    if (!scene3_sphere(o, w, tmin, b.t, center, 90.0f, b.t)) return;
+    b.id = id;
+    b.pos = add(o, muls(w, b.t));
+    b.nrm = normalize(sub(b.pos, center));
+}
 __device__ __forceinline__ W8Ball w8_balls(f3 o, f3 w, float tmin, float tmax)
 {
     W8Ball b;
     b.id = 0;
     b.t = tmax;
     b.pos = b.nrm = V(0, 0, 0);
-    if (w1_sphere(o, w, tmin, b.t, V(420.0f, 90.0f, 370.0f), 90.0f, b.pos, b.nrm)) b.id = 1;
-    if (w1_sphere(o, w, tmin, b.t, V(130.0f, 90.0f, 250.0f), 90.0f, b.pos, b.nrm)) b.id = 2;
+    w8_ball(o, w, tmin, V(420.0f, 90.0f, 370.0f), 1, b);
+    w8_ball(o, w, tmin, V(130.0f, 90.0f, 250.0f), 2, b);
     return b;
 }
 
 // intersect_plane (w9e2.wgsl:388-404): the holdout plane through the origin
-// with normal (0, 1, 0), in the shader's arithmetic
+// with normal (0, 1, 0) is the three-object scene's plane; a hit lowers tmax
 __device__ __forceinline__ bool w9_plane(f3 o, f3 w, float tmin, float& tmax)
 {
-    const f3 n = V(0.0f, 1.0f, 0.0f);
-    const float distance = dot(sub(V(0.0f, 0.0f, 0.0f), o), n) / dot(w, n);
-    if (distance < tmin || distance > tmax) return false;
-    tmax = distance;
-    return true;
+    return scene3_plane(o, w, tmin, tmax, tmax);
 }
 
 // sample_directional_light (w9e3.wgsl:405-414): the sun, L = 10, from -normalize(1, -0.35, 0)
@@ -2480,97 +2463,6 @@ __global__ void __launch_bounds__(256) k_direct(DevScene S, DevLaunch L)
     flush_counters(cnt, L.counters, COUNT);
 }
 
-// ------------------------------------------------------------------ W1E6 analytic kernel
-// res/shaders/w1e6.wgsl: triangle + sphere + plane, point light, no mesh.
-__device__ __forceinline__ bool w1_triangle(f3 o, f3 w, float tmin, float& tmax, f3 a, f3 b, f3 c, f3& pos,
-                                            f3& nrm)
-{
-    const f3 e0 = sub(b, a), e1 = sub(c, a), ov = sub(a, o);
-    const f3 normal = cross(e0, e1);
-    const f3 nom = cross(ov, w);
-    const float denom = dot(w, normal);
-    if (rt_absf(denom) < 1e-6f) return false;
-    const float beta = dot(nom, e1) / denom;
-    const float gamma = -dot(nom, e0) / denom;
-    const float distance = dot(ov, normal) / denom;
-    if (beta < 0.0f || gamma < 0.0f || beta + gamma > 1.0f || distance > tmax || distance < tmin) return false;
-    tmax = distance;
-    pos = add(o, muls(w, distance));
-    nrm = normalize(normal);
-    return true;
-}
-__device__ __forceinline__ bool w1_plane(f3 o, f3 w, float tmin, float& tmax, f3 normal, f3 position, f3& pos,
-                                         f3& nrm)
-{
-    const float distance = dot(sub(position, o), normal) / dot(w, normal);
-    if (distance < tmin || distance > tmax) return false;
-    tmax = distance;
-    pos = add(o, muls(w, distance));
-    nrm = normal;
-    return true;
-}
-
-__global__ void __launch_bounds__(256) k_w1e6(DevLaunch L)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const Cam cam = make_cam(L);
-    Counters cnt;
-#pragma unroll
-    for (int i = 0; i < C_N; i++) cnt.v[i] = 0;
-    for (;;) {
-        const uint32_t work = fetch_work(L.work_counter, lane);
-        if (work >= L.nwork) break;
-        const Pix px = map_pixel(L, work, lane);
-        if (!px.valid) continue;
-        cnt.v[C_SAMPLES]++;
-        cnt.v[C_PRIMARY]++;
-        float ux, uy;
-        pixel_uv(L.u, px.x, px.y, ux, uy);
-        const f3 w = normalize(add(add(muls(muls(cam.b1, ux), cam.aspect), muls(cam.b2, uy)), muls(cam.v, cam.d)));
-        const f3 o = cam.e;
-        float tmax = 5000.0f;
-        const float tmin = 0.00001f;
-        f3 pos = V(0, 0, 0), nrm = V(0, 0, 0), base = V(0, 0, 0);
-        bool any = false;
-        uint32_t which = 0xFFFFFFFFu;
-        if (w1_triangle(o, w, tmin, tmax, V(0.2f, 0.1f, 0.9f), V(-0.2f, 0.1f, -0.1f), V(-0.2f, 0.1f, 0.9f), pos,
-                        nrm)) {
-            any = true;
-            base = V(0.4f, 0.3f, 0.2f);
-            which = 0;
-        }
-        if (w1_sphere(o, w, tmin, tmax, V(0.0f, 0.5f, 0.0f), 0.3f, pos, nrm)) {
-            any = true;
-            base = V(0.0f, 0.0f, 0.0f);
-            which = 1;
-        }
-        if (w1_plane(o, w, tmin, tmax, V(0.0f, 1.0f, 0.0f), V(0.0f, 0.0f, 0.0f), pos, nrm)) {
-            any = true;
-            base = V(0.1f, 0.7f, 0.0f);
-            which = 2;
-        }
-        f3 result;
-        if (any) {
-            // lambertian + sample_point_light, w1e6.wgsl:239-284
-            const f3 intensity = muls(V(RT_PI_F, RT_PI_F, RT_PI_F), 5.0f);
-            const f3 dir = sub(V(0.0f, 1.2f, 0.0f), pos);
-            const float dist = dot(dir, dir);
-            const f3 l_i = divs(intensity, dist * dist);
-            const float dd = dot(nrm, dir);
-            f3 dfc = V(dd, dd, dd);
-            dfc = mul(dfc, l_i);
-            dfc = muls(dfc, (1.0f - 0.0f) / RT_PI_F);
-            const f3 diffuse = mul(base, dfc);
-            result = add(V(0, 0, 0), add(muls(diffuse, 0.9f), muls(base, 0.1f)));
-        } else {
-            result = add(V(0, 0, 0), V(0.1f, 0.3f, 0.6f));
-        }
-        L.accum[px.out] = make_float4(result.x, result.y, result.z, 1.0f);
-        if (L.ids) L.ids[px.out] = which;
-    }
-    flush_counters(cnt, L.counters, false);
-}
-
 // ------------------------------------------------------------------ tile unpack
 // packed (rank-major all-gather output): [nranks][local_tiles][64] -> row-major frame
 __global__ void __launch_bounds__(256) k_unpack(uint32_t W, uint32_t H, uint32_t nranks, uint32_t local_tiles,
@@ -2726,17 +2618,6 @@ static void launch_path(const DevScene& s, const DevLaunch& l, int grid, size_t 
     }
     hipLaunchKernelGGL((k_path<MODE, TRAV, COUNT>), dim3(grid), dim3(256), lds, st, s, l);
 }
-template <int MODE, int TRAV, bool COUNT>
-static void launch_direct(const DevScene& s, const DevLaunch& l, int grid, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((k_direct<MODE, TRAV, COUNT>), dim3(grid), dim3(256), lds, st, s, l);
-}
-template <int TRAV, bool COUNT>
-static void launch_primary(const DevScene& s, const DevLaunch& l, int project, int grid, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((k_primary<TRAV, COUNT>), dim3(grid), dim3(256), lds, st, s, l, project);
-}
-
 int launch_render(const DevScene& s, const DevLaunch& l, rt_mode mode, rt_traverse trav, bool detail, int num_cus,
                   int waves_per_cu, hipStream_t stream)
 {
@@ -2751,92 +2632,47 @@ int launch_render(const DevScene& s, const DevLaunch& l, rt_mode mode, rt_traver
                                                       : RT_PATH_WAVES_PER_EU);
     const int grid = grid_for(num_cus, std::min(std::min(waves_per_cu > 0 ? waves_per_cu : 16, reg_waves),
                                                 std::max(4, lds_waves)));
-    if (mode == RT_MODE_W1E6) {
-        hipLaunchKernelGGL(k_w1e6, dim3(grid), dim3(256), 0, stream, l);
-        return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
-    }
-    const bool bvh = trav == RT_TRAVERSE_BVH;
+    // the run-time (trav, detail) as the kernels' template constants
+    const auto instance = [&](auto&& f) {
+        with_flag(trav == RT_TRAVERSE_BVH, [&](auto bvh) {
+            with_flag(detail, [&](auto count) {
+                f(Int<decltype(bvh)::value ? RT_TRAVERSE_BVH : RT_TRAVERSE_BSP>{}, count);
+            });
+        });
+    };
+    const auto path = [&](auto M) {
+        instance([&](auto T, auto C) {
+            launch_path<decltype(M)::value, decltype(T)::value, decltype(C)::value>(s, l, grid, lds, stream);
+        });
+    };
+    const auto direct = [&](auto M) {
+        instance([&](auto T, auto C) {
+            hipLaunchKernelGGL((k_direct<decltype(M)::value, decltype(T)::value, decltype(C)::value>), dim3(grid),
+                               dim3(256), lds, stream, s, l);
+        });
+    };
     switch (mode) {
-    case RT_MODE_W7E3:
-        if (bvh) detail ? launch_path<RT_MODE_W7E3, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                        : launch_path<RT_MODE_W7E3, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-        else detail ? launch_path<RT_MODE_W7E3, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                    : launch_path<RT_MODE_W7E3, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        break;
+    case RT_MODE_W7E3: path(Int<RT_MODE_W7E3>{}); break;
     case RT_MODE_W9E1:
-        if (l.u.selection1 == 7u) {
-            if (bvh) detail ? launch_path<MODE_W9E1_TRANSPARENT, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                            : launch_path<MODE_W9E1_TRANSPARENT, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-            else detail ? launch_path<MODE_W9E1_TRANSPARENT, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                        : launch_path<MODE_W9E1_TRANSPARENT, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        } else {
-            if (bvh) detail ? launch_path<RT_MODE_W9E1, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                            : launch_path<RT_MODE_W9E1, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-            else detail ? launch_path<RT_MODE_W9E1, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                        : launch_path<RT_MODE_W9E1, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        }
+        if (l.u.selection1 == 7u) path(Int<MODE_W9E1_TRANSPARENT>{});
+        else path(Int<RT_MODE_W9E1>{});
         break;
-    case RT_MODE_W9E3:
-        if (bvh) detail ? launch_path<RT_MODE_W9E3, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                        : launch_path<RT_MODE_W9E3, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-        else detail ? launch_path<RT_MODE_W9E3, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                    : launch_path<RT_MODE_W9E3, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        break;
-    case RT_MODE_W9E2:
-        if (bvh) detail ? launch_path<RT_MODE_W9E2, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                        : launch_path<RT_MODE_W9E2, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-        else detail ? launch_path<RT_MODE_W9E2, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                    : launch_path<RT_MODE_W9E2, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        break;
-    case RT_MODE_W8E1:
-        if (bvh) detail ? launch_path<RT_MODE_W8E1, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                        : launch_path<RT_MODE_W8E1, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-        else detail ? launch_path<RT_MODE_W8E1, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                    : launch_path<RT_MODE_W8E1, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        break;
-    case RT_MODE_W8E2:
-        if (bvh) detail ? launch_path<RT_MODE_W8E2, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                        : launch_path<RT_MODE_W8E2, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-        else detail ? launch_path<RT_MODE_W8E2, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                    : launch_path<RT_MODE_W8E2, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        break;
-    case RT_MODE_W8E3:
-        if (bvh) detail ? launch_path<RT_MODE_W8E3, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                        : launch_path<RT_MODE_W8E3, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-        else detail ? launch_path<RT_MODE_W8E3, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                    : launch_path<RT_MODE_W8E3, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        break;
-    case RT_MODE_W6E2:
-        if (bvh) detail ? launch_direct<RT_MODE_W6E2, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                        : launch_direct<RT_MODE_W6E2, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-        else detail ? launch_direct<RT_MODE_W6E2, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                    : launch_direct<RT_MODE_W6E2, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        break;
-    case RT_MODE_W6E3:
-        if (bvh) detail ? launch_direct<RT_MODE_W6E3, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                        : launch_direct<RT_MODE_W6E3, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-        else detail ? launch_direct<RT_MODE_W6E3, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                    : launch_direct<RT_MODE_W6E3, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        break;
-    case RT_MODE_W7E1:
-        if (bvh) detail ? launch_direct<RT_MODE_W7E1, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                        : launch_direct<RT_MODE_W7E1, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-        else detail ? launch_direct<RT_MODE_W7E1, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                    : launch_direct<RT_MODE_W7E1, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        break;
-    case RT_MODE_W7E2:
-        if (bvh) detail ? launch_direct<RT_MODE_W7E2, RT_TRAVERSE_BVH, true>(s, l, grid, lds, stream)
-                        : launch_direct<RT_MODE_W7E2, RT_TRAVERSE_BVH, false>(s, l, grid, lds, stream);
-        else detail ? launch_direct<RT_MODE_W7E2, RT_TRAVERSE_BSP, true>(s, l, grid, lds, stream)
-                    : launch_direct<RT_MODE_W7E2, RT_TRAVERSE_BSP, false>(s, l, grid, lds, stream);
-        break;
+    case RT_MODE_W9E3: path(Int<RT_MODE_W9E3>{}); break;
+    case RT_MODE_W9E2: path(Int<RT_MODE_W9E2>{}); break;
+    case RT_MODE_W8E1: path(Int<RT_MODE_W8E1>{}); break;
+    case RT_MODE_W8E2: path(Int<RT_MODE_W8E2>{}); break;
+    case RT_MODE_W8E3: path(Int<RT_MODE_W8E3>{}); break;
+    case RT_MODE_W6E2: direct(Int<RT_MODE_W6E2>{}); break;
+    case RT_MODE_W6E3: direct(Int<RT_MODE_W6E3>{}); break;
+    case RT_MODE_W7E1: direct(Int<RT_MODE_W7E1>{}); break;
+    case RT_MODE_W7E2: direct(Int<RT_MODE_W7E2>{}); break;
     case RT_MODE_W6E1:
     case RT_MODE_PROJECT: {
         const int project = mode == RT_MODE_PROJECT;
-        if (bvh) detail ? launch_primary<RT_TRAVERSE_BVH, true>(s, l, project, grid, lds, stream)
-                        : launch_primary<RT_TRAVERSE_BVH, false>(s, l, project, grid, lds, stream);
-        else detail ? launch_primary<RT_TRAVERSE_BSP, true>(s, l, project, grid, lds, stream)
-                    : launch_primary<RT_TRAVERSE_BSP, false>(s, l, project, grid, lds, stream);
+        instance([&](auto T, auto C) {
+            hipLaunchKernelGGL((k_primary<decltype(T)::value, decltype(C)::value>), dim3(grid), dim3(256), lds, stream, s,
+                               l, project);
+        });
         break;
     }
     default:

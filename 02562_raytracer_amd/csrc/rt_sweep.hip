@@ -24,8 +24,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "rt_device_common.h"
 
 namespace rtk {
@@ -155,12 +153,6 @@ struct SweepCounts {
     uint32_t samples, primary, shadow;
     unsigned long long tests;
 };
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long s)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    return s;
-}
 
 // fs_main of the four shaders.  MODE: RT_MODE_W5E2 .. RT_MODE_W5E5.  COUNT: the
 // triangle tests the shader would make (a ray that accepts triangle i made i + 1,
@@ -311,28 +303,15 @@ __global__ void __launch_bounds__(256) k_sweep(SweepScene S, DevLaunch L)
     }
 }
 
-template <int MODE>
-static void launch_sweep_mode(const SweepScene& s, const DevLaunch& l, bool detail, int grid, hipStream_t st)
-{
-    if (detail) hipLaunchKernelGGL((k_sweep<MODE, true>), dim3(grid), dim3(256), 0, st, s, l);
-    else hipLaunchKernelGGL((k_sweep<MODE, false>), dim3(grid), dim3(256), 0, st, s, l);
-}
-
 int launch_sweep(const SweepScene& s, const DevLaunch& l, rt_mode mode, bool detail, int num_cus, int waves_per_cu,
                  hipStream_t stream)
 {
-    // persistent grid: four waves (tiles in flight) per block
-    const int wpc = waves_per_cu > 0 ? waves_per_cu : 16;
-    const long long cap = std::max(1LL, (long long)num_cus * wpc / 4);
-    const int grid = (int)std::min<long long>(cap, ((long long)l.nwork + 3) / 4);
+    const int grid = flat_grid(num_cus, waves_per_cu, l.nwork);
     if (grid <= 0) return RT_OK;
-    switch (mode) {
-    case RT_MODE_W5E2: launch_sweep_mode<RT_MODE_W5E2>(s, l, detail, grid, stream); break;
-    case RT_MODE_W5E3: launch_sweep_mode<RT_MODE_W5E3>(s, l, detail, grid, stream); break;
-    case RT_MODE_W5E4: launch_sweep_mode<RT_MODE_W5E4>(s, l, detail, grid, stream); break;
-    case RT_MODE_W5E5: launch_sweep_mode<RT_MODE_W5E5>(s, l, detail, grid, stream); break;
-    default: return RT_E_UNSUPPORTED;
-    }
+    const auto launch = [&](auto M, auto C) {
+        hipLaunchKernelGGL((k_sweep<decltype(M)::value, decltype(C)::value>), dim3(grid), dim3(256), 0, stream, s, l);
+    };
+    if (!with_mode<RT_MODE_W5E2, RT_MODE_W5E5>(mode, detail, launch)) return RT_E_UNSUPPORTED;
     return hipGetLastError() == hipSuccess ? RT_OK : RT_E_DEVICE;
 }
 

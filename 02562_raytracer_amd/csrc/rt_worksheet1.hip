@@ -1,8 +1,9 @@
-// rt_worksheet1.hip -- gfx950 kernels for the worksheet-1 scenes W1E2..W1E5
-// (res/shaders/{w1e2,w1e3,w1e4,w1e5}.wgsl), the partial steps towards W1E6, and the
-// display kernel of the two of them that return their colour without pow(., 1.5).
+// rt_worksheet1.hip -- gfx950 kernels for the worksheet-1 scenes W1E2..W1E6
+// (res/shaders/{w1e2,w1e3,w1e4,w1e5,w1e6}.wgsl): the partial steps towards W1E6 and
+// W1E6 itself, and the display kernel of the two of them that return their colour
+// without pow(., 1.5).  The scene of W1E4..W1E6 is rt_scene3.h's.
 //
-// What the four shaders do (DESIGN.md "Worksheet-1 scenes"):
+// What the five shaders do (DESIGN.md "Worksheet-1 scenes"):
 //   * W1E2 draws the full-screen quad scaled by 0.9 in one colour: the fragment
 //     shader never runs on the outer 5 % of the frame, which keeps the render pass's
 //     clear colour (0, 0, 0).  Coverage is the pinned integer rule of w1_covered and
@@ -17,29 +18,27 @@
 //     comparisons are false on it and the plane is accepted with a NaN distance.
 //     The bounce loop always ends after one pass (shade sets has_hit).
 //   * W1E5 is W1E4 with get_camera_ray reading the aspect ratio and the constant.
-// W1E2 and W1E3 return the colour as it is; W1E4 and W1E5 apply pow(result, 1.5)
-// like every later shader.  All four store `result` in accum; the display differs
+//   * W1E6 is W1E5 shaded by lambertian with the point light, no shadow ray.
+// W1E2 and W1E3 return the colour as it is; W1E4 to W1E6 apply pow(result, 1.5)
+// like every later shader.  All five store `result` in accum; the display differs
 // (k_frame_linear below, rt_frame_rgba8_mode).
 //
-// Structure: one lane per pixel of an 8x8 tile, map_pixel / fetch_work as k_w1e6, so
-// regions and tile sets both work.  Plain arithmetic only: no LDS, no scratch,
+// Structure: one lane per pixel of an 8x8 tile, map_pixel / fetch_work as k_primary,
+// so regions and tile sets both work.  Plain arithmetic only: no LDS, no scratch,
 // nothing indexed at run time.  MODE is a template parameter.
 //
 // Numerics: only + - * / sqrt, -ffp-contract=off, correctly rounded division and
-// sqrt => bit-identical to a plain C evaluation (tests/native/w1_ref.c).
+// sqrt => bit-identical to a plain C evaluation (tests/native/w1_ref.c; W1E6:
+// oracle/oracle_render.c).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
-#include "rt_device_common.h"
+#include "rt_scene3.h"
 
 namespace rtk {
 
 namespace {
 
-constexpr float W1_ETA = 0.00001f;    // ray_init's tmin (w1e4.wgsl:24-31)
-constexpr float W1_TMAX = 5000.0f;
 constexpr uint32_t W1_NONE = 0xFFFFFFFFu;
 
 // W1E2: is pixel (x, y) of a W x H frame inside the quad scaled by 0.9?  The quad's
@@ -52,64 +51,10 @@ __device__ __forceinline__ bool w1_covered(uint32_t x, uint32_t y, uint32_t W, u
     return (W <= cx) & (cx < 19u * W) & (H <= cy) & (cy < 19u * H);
 }
 
-// intersect_triangle (w1e4.wgsl:164-194) on the scene's one triangle
-__device__ __forceinline__ bool w1_hit_triangle(const f3 o, const f3 w, float& tmax)
-{
-    const f3 v0 = V(0.2f, 0.1f, 0.9f), v1 = V(-0.2f, 0.1f, -0.1f), v2 = V(-0.2f, 0.1f, 0.9f);
-    const f3 e0 = sub(v1, v0), e1 = sub(v2, v0), ov = sub(v0, o);
-    const f3 normal = cross(e0, e1);
-    const f3 nom = cross(ov, w);
-    const float denom = dot(w, normal);
-    if (rt_absf(denom) < 1e-6f) return false;
-    const float beta = dot(nom, e1) / denom;
-    const float gamma = -dot(nom, e0) / denom;
-    const float distance = dot(ov, normal) / denom;
-    if ((beta < 0.0f) | (gamma < 0.0f) | (beta + gamma > 1.0f) | (distance > tmax) | (distance < W1_ETA)) return false;
-    tmax = distance;
-    return true;
-}
-// intersect_sphere (w1e4.wgsl:196-222): the near root, or else the far one
-__device__ __forceinline__ bool w1_hit_sphere(const f3 o, const f3 w, float& tmax)
-{
-    const f3 center = V(0.0f, 0.5f, 0.0f);
-    const float radius = 0.3f;
-    const f3 oc = sub(o, center);
-    const float a = dot(w, w);
-    const float b_over_2 = dot(oc, w);
-    const float c = dot(oc, oc) - radius * radius;
-    const float discriminant = b_over_2 * b_over_2 - a * c;
-    if (discriminant < 0.0f) return false;
-    const float disc_sqrt = rt_det_sqrtf(discriminant);
-    float root = (-b_over_2 - disc_sqrt) / a;
-    if ((root < W1_ETA) | (root > tmax)) {
-        root = (-b_over_2 + disc_sqrt) / a;
-        if ((root < W1_ETA) | (root > tmax)) return false;
-    }
-    tmax = root;
-    return true;
-}
-// intersect_plane (w1e4.wgsl:149-162): the division is unguarded, and a NaN distance
-// passes both comparisons
-__device__ __forceinline__ bool w1_hit_plane(const f3 o, const f3 w, float& tmax)
-{
-    const f3 normal = V(0.0f, 1.0f, 0.0f), position = V(0.0f, 0.0f, 0.0f);
-    const float distance = dot(sub(position, o), normal) / dot(w, normal);
-    if ((distance < W1_ETA) | (distance > tmax)) return false;
-    tmax = distance;
-    return true;
-}
-
-__device__ __forceinline__ unsigned long long w1_wave_sum(unsigned long long s)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-    return s;
-}
-
 }  // namespace
 
-// fs_main of the four shaders (and, for W1E2, the rasteriser's coverage).  MODE:
-// RT_MODE_W1E2 .. RT_MODE_W1E5.  COUNT: the counting instantiation
+// fs_main of the five shaders (and, for W1E2, the rasteriser's coverage).  MODE:
+// RT_MODE_W1E2 .. RT_MODE_W1E5 or RT_MODE_W1E6.  COUNT: the counting instantiation
 // (RT_OPT_DETAIL_COUNTERS); samples and primary are always filled, so it differs in
 // nothing but its name and exists so that the launch interface matches launch_analytic's.
 template <int MODE, bool COUNT>
@@ -133,7 +78,7 @@ __global__ void __launch_bounds__(256) k_w1(DevLaunch L)
             float ux, uy;
             pixel_uv(L.u, px.x, px.y, ux, uy);
             // get_camera_ray: w1e3.wgsl:43-57 and w1e4.wgsl:84-98 (d = 1.0, no aspect), w1e5.wgsl:84-100
-            const f3 q = MODE == RT_MODE_W1E5
+            const f3 q = MODE == RT_MODE_W1E5 || MODE == RT_MODE_W1E6
                              ? add(add(muls(muls(cam.b1, ux), cam.aspect), muls(cam.b2, uy)), muls(cam.v, cam.d))
                              : add(add(muls(cam.b1, ux), muls(cam.b2, uy)), muls(cam.v, 1.0f));
             const f3 w = normalize(q);
@@ -141,55 +86,60 @@ __global__ void __launch_bounds__(256) k_w1(DevLaunch L)
                 result = divs(add(w, V(1.0f, 1.0f, 1.0f)), 2.0f);
             } else {
                 // intersect_scene: every accepted test lowers tmax for the ones after it
-                float tmax = W1_TMAX;
+                float tmax = SCENE3_TMAX;
                 f3 base = V(0, 0, 0);
-                if (w1_hit_triangle(cam.e, w, tmax)) {
-                    base = V(0.4f, 0.3f, 0.2f);
+                if (scene3_triangle(cam.e, w, SCENE3_ETA, tmax, tmax)) {
+                    base = scene3_triangle_color();
                     which = 0u;
                 }
-                if (w1_hit_sphere(cam.e, w, tmax)) {
-                    base = V(0.0f, 0.0f, 0.0f);
+                if (scene3_sphere(cam.e, w, SCENE3_ETA, tmax, scene3_center(), SCENE3_RADIUS, tmax)) {
+                    base = scene3_sphere_color();
                     which = 1u;
                 }
-                if (w1_hit_plane(cam.e, w, tmax)) {
-                    base = V(0.1f, 0.7f, 0.0f);
+                if (scene3_plane(cam.e, w, SCENE3_ETA, tmax, tmax)) {
+                    base = scene3_plane_color();
                     which = 2u;
                 }
-                // shade returns base_color; a miss adds bgcolor.rgb
-                result = add(V(0, 0, 0), which != W1_NONE ? base : V(0.1f, 0.3f, 0.6f));
+                if (MODE == RT_MODE_W1E6 && which != W1_NONE) {
+                    // the closest hit's position and normal, then lambertian + sample_point_light
+                    // (w1e6.wgsl:239-284)
+                    const f3 pos = add(cam.e, muls(w, tmax));
+                    const f3 nrm = which == 0u   ? normalize(scene3_tri().normal)
+                                   : which == 1u ? normalize(sub(pos, scene3_center()))
+                                                 : scene3_plane_normal();
+                    const Scene3Light light = scene3_point_light(pos);
+                    const float dd = dot(nrm, light.w_i);
+                    f3 dfc = V(dd, dd, dd);
+                    dfc = mul(dfc, light.l_i);
+                    dfc = muls(dfc, (1.0f - 0.0f) / RT_PI_F);
+                    const f3 diffuse = mul(base, dfc);
+                    result = add(V(0, 0, 0), add(muls(diffuse, 0.9f), muls(base, 0.1f)));
+                } else {
+                    // W1E4, W1E5: shade returns base_color; a miss adds bgcolor.rgb
+                    result = add(V(0, 0, 0), which != W1_NONE ? base : scene3_background());
+                }
             }
         }
         L.accum[px.out] = make_float4(result.x, result.y, result.z, 1.0f);
         if (L.ids) L.ids[px.out] = which;
     }
-    const unsigned long long s = w1_wave_sum(n_pixels);
+    const unsigned long long s = wave_sum(n_pixels);
     if (lane == 0 && s) {
         atomicAdd(L.counters + C_SAMPLES, s);
         if (MODE != RT_MODE_W1E2) atomicAdd(L.counters + C_PRIMARY, s);   // W1E2 casts no ray
     }
 }
 
-template <int MODE>
-static void launch_w1_mode(const DevLaunch& l, bool detail, int grid, hipStream_t st)
-{
-    if (detail) hipLaunchKernelGGL((k_w1<MODE, true>), dim3(grid), dim3(256), 0, st, l);
-    else hipLaunchKernelGGL((k_w1<MODE, false>), dim3(grid), dim3(256), 0, st, l);
-}
-
 int launch_worksheet1(const DevLaunch& l, rt_mode mode, bool detail, int num_cus, int waves_per_cu, hipStream_t stream)
 {
-    // persistent grid: four waves (tiles in flight) per block
-    const int wpc = waves_per_cu > 0 ? waves_per_cu : 16;
-    const long long cap = std::max(1LL, (long long)num_cus * wpc / 4);
-    const int grid = (int)std::min<long long>(cap, ((long long)l.nwork + 3) / 4);
+    const int grid = flat_grid(num_cus, waves_per_cu, l.nwork);
     if (grid <= 0) return RT_OK;
-    switch (mode) {
-    case RT_MODE_W1E2: launch_w1_mode<RT_MODE_W1E2>(l, detail, grid, stream); break;
-    case RT_MODE_W1E3: launch_w1_mode<RT_MODE_W1E3>(l, detail, grid, stream); break;
-    case RT_MODE_W1E4: launch_w1_mode<RT_MODE_W1E4>(l, detail, grid, stream); break;
-    case RT_MODE_W1E5: launch_w1_mode<RT_MODE_W1E5>(l, detail, grid, stream); break;
-    default: return RT_E_UNSUPPORTED;
-    }
+    const auto launch = [&](auto M, auto C) {
+        hipLaunchKernelGGL((k_w1<decltype(M)::value, decltype(C)::value>), dim3(grid), dim3(256), 0, stream, l);
+    };
+    if (!with_mode<RT_MODE_W1E2, RT_MODE_W1E5>(mode, detail, launch) &&
+        !with_mode<RT_MODE_W1E6, RT_MODE_W1E6>(mode, detail, launch))
+        return RT_E_UNSUPPORTED;
     return hipGetLastError() == hipSuccess ? RT_OK : RT_E_DEVICE;
 }
 

@@ -301,7 +301,7 @@ int rt_memset_device(rt_ctx* ctx, void* dst_dev, int value, size_t bytes);
 int rt_timer_start(rt_ctx* ctx);
 int rt_timer_stop(rt_ctx* ctx, float* ms);   /* synchronizes */
 
-/* Per-launch timing of the traversal kernels (k_path / k_primary / k_w1e6 / k_sweep / k_analytic / k_w1),
+/* Per-launch timing of the traversal kernels (k_path / k_primary / k_sweep / k_analytic / k_w1),
  * enabled by RT_OPT_KERNEL_TIMING: HIP events around every such launch on the
  * context stream.  rt_kernel_time synchronizes and returns the summed
  * duration and the number of launches since the last reset (reset != 0

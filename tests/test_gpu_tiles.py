@@ -35,7 +35,7 @@ COUNTS = ("samples", "primary", "shadow", "bounce")
 
 # (W, H, nranks): under / at / over 8 tiles wide, tile rows past 8, a rank without a tile, one pixel
 FRAMES = [(42, 26, 2), (42, 26, 5), (58, 20, 3), (70, 77, 8), (16, 8, 3), (1, 1, 2)]
-# one mode per kernel instantiation family (k_w1e6, k_analytic, k_sweep, k_primary, k_direct, k_path)
+# one mode per kernel instantiation family (k_w1, k_analytic, k_sweep, k_primary, k_direct, k_path)
 KERNELS = [("W1E6", "NONE"), ("W2E5", "NONE"), ("W5E2", "NONE"), ("W6E1", "BSP"), ("W6E1", "BVH"),
            ("PROJECT", "BSP"), ("W6E2", "BSP"), ("W7E1", "BVH"), ("W7E3", "BSP"), ("W7E3", "BVH"),
            ("W9E1", "BSP"), ("W8E2", "BSP")]

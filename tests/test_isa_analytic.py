@@ -6,34 +6,19 @@ the kernel, and nothing in it is indexed at run time.  Reads only the two
 fields of each kernel descriptor that say so."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import isa_util
+from isa_util import ROOT, descriptor
+
 # k_analytic<MODE, COUNT>: W2E1..W3E4 = 18..26, plain and counting
 KERNELS = [f"k_analyticILi{m}ELb{c}E" for m in range(18, 27) for c in (0, 1)]
 
 
 @pytest.fixture(scope="module")
 def device_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa_analytic") / "rt_analytic.s"
-    cmd = [HIPCC, "-std=c++17", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-bitwise-instead-of-logical",
-           "-fno-slp-vectorize",   # as the Makefile builds rt_analytic.o
-           "-x", "hip", "--cuda-device-only", "-S",
-           os.path.join(ROOT, "02562_raytracer_amd", "csrc", "rt_analytic.hip"), "-o", str(out)]
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    return open(out).read()
-
-
-def descriptor(s, ksub):
-    name = next(l.split(":")[0] for l in s.splitlines() if re.match(r"^_Z\S*:", l) and ksub in l)
-    k = s.index(".amdhsa_kernel " + name)
-    return s[k:s.index(".end_amdhsa_kernel", k)]
+    return open(isa_util.device_asm("rt_analytic.hip", tmp_path_factory.mktemp("isa_analytic"))).read()
 
 
 def test_makefile_builds_the_object_with_the_sweep_flags():

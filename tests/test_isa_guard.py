@@ -7,12 +7,14 @@ and the whole kernel's spill footprint (scratch bytes per lane, spill
 instructions) may not grow: the shading-phase spills are most of the kernel's
 HBM traffic ("HBM traffic")."""
 import os
-import subprocess
+import re
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import isa_util
+from isa_util import ROOT
+
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # kernel -> allowed scratch instructions in its trip loop (today's values)
@@ -30,16 +32,7 @@ BUDGET = {
 
 @pytest.fixture(scope="module")
 def device_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa") / "rt_kernels.s"
-    cmd = ["/opt/rocm/bin/hipcc", "-std=c++17", "-O3", "--offload-arch=gfx950", "-ffp-contract=off",
-           "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-bitwise-instead-of-logical",
-           "-fno-slp-vectorize",   # as the Makefile builds rt_kernels.o
-           "-x", "hip", "--cuda-device-only", "-S", os.path.join(ROOT, "02562_raytracer_amd", "csrc", "rt_kernels.hip"),
-           "-o", str(out)]
-    if not os.path.exists(cmd[0]):
-        pytest.skip("hipcc not available")
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    return str(out)
+    return isa_util.device_asm("rt_kernels.hip", tmp_path_factory.mktemp("isa"))
 
 
 # kernel -> (scratch bytes per lane, scratch instructions in the whole kernel), today's values
@@ -75,15 +68,9 @@ WHOLE_BUDGET = {
 
 
 def kernel_spills(path, ksub):
-    import re
     s = open(path).read()
-    name = next(l.split(":")[0] for l in s.splitlines() if re.match(r"^_Z\S*:", l) and ksub in l)
-    i = s.index(name + ":")
-    body = s[i:s.index(".Lfunc_end", i)]
-    k = s.index(".amdhsa_kernel " + name)
-    meta = s[k:s.index(".end_amdhsa_kernel", k)]
-    scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", meta).group(1))
-    return scratch, len(re.findall(r"\bscratch_(?:load|store)", body))
+    scratch = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", isa_util.descriptor(s, ksub)).group(1))
+    return scratch, len(re.findall(r"\bscratch_(?:load|store)", isa_util.body(s, ksub)))
 
 
 @pytest.mark.parametrize("kernel", sorted(WHOLE_BUDGET))

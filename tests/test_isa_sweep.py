@@ -3,38 +3,23 @@ cross-compiles gfx950 here).  Every k_sweep instantiation must run without
 scratch memory, and its sweep must read the triangle records with scalar loads
 (a wave-uniform index, DESIGN.md "Triangle sweep"): a change that makes the
 index look divergent to the compiler would turn them into per-lane loads."""
-import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+import isa_util
+
 # k_sweep<MODE, COUNT>: W5E2..W5E5 = 14..17, plain and counting
 KERNELS = [f"k_sweepILi{m}ELb{c}E" for m in (14, 15, 16, 17) for c in (0, 1)]
 
 
 @pytest.fixture(scope="module")
 def device_asm(tmp_path_factory):
-    out = tmp_path_factory.mktemp("isa_sweep") / "rt_sweep.s"
-    cmd = [HIPCC, "-std=c++17", "-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-           "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-bitwise-instead-of-logical",
-           "-fno-slp-vectorize",   # as the Makefile builds rt_sweep.o
-           "-x", "hip", "--cuda-device-only", "-S", os.path.join(ROOT, "02562_raytracer_amd", "csrc", "rt_sweep.hip"),
-           "-o", str(out)]
-    if not os.path.exists(HIPCC):
-        pytest.skip("hipcc not available")
-    subprocess.run(cmd, check=True, capture_output=True, timeout=600)
-    return open(out).read()
+    return open(isa_util.device_asm("rt_sweep.hip", tmp_path_factory.mktemp("isa_sweep"))).read()
 
 
 def kernel_text(s, ksub):
-    name = next(l.split(":")[0] for l in s.splitlines() if re.match(r"^_Z\S*:", l) and ksub in l)
-    i = s.index(name + ":")
-    body = s[i:s.index(".Lfunc_end", i)]
-    k = s.index(".amdhsa_kernel " + name)
-    return body, s[k:s.index(".end_amdhsa_kernel", k)]
+    return isa_util.body(s, ksub), isa_util.descriptor(s, ksub)
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
