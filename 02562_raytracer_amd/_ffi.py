@@ -192,6 +192,7 @@ SIGNATURES = {
     "rt_set_ray_capture": (C.c_int, [vp, vp, vp, C.c_uint64]),
     "rt_ray_capture_count": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "rt_last_counts": (C.c_int, [vp, C.POINTER(RayCounts)]),
+    "rt_last_elided_shadows": (C.c_int, [vp, C.POINTER(C.c_uint64)]),
     "rt_selftest_math": (C.c_int, [vp, C.c_uint32, C.c_float, C.c_float, u32p]),
     "rt_mesh_load_obj": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rt_mesh_from_arrays": (C.c_int, [f32p, f32p, C.c_uint32, u32p, C.c_uint32, C.POINTER(Material), C.c_uint32,

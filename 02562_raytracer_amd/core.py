@@ -482,6 +482,13 @@ class Context:
         self._chk(F.lib().rt_last_counts(self._h, C.byref(cnt)))
         return cnt.asdict()
 
+    def last_elided_shadows(self):
+        """Shadow rays of the last launch that were resolved at shading time, not walked
+        (rt_last_elided_shadows); 0 unless the detail counters are on."""
+        n = C.c_uint64()
+        self._chk(F.lib().rt_last_elided_shadows(self._h, C.byref(n)))
+        return n.value
+
     def timer_start(self):
         self._chk(F.lib().rt_timer_start(self._h))
 

@@ -1791,6 +1791,20 @@ int rt_last_counts(rt_ctx* c, rt_ray_counts* counts)
     return RT_OK;
 }
 
+int rt_last_elided_shadows(rt_ctx* c, uint64_t* elided)
+{
+    if (!c || !elided) return RT_E_INVALID;
+    if (int r = set_dev(c)) return r;
+    // the counter after rt_ray_counts' members (C_ELIDED); the timed instantiations leave it 0
+    static_assert(sizeof(rt_ray_counts) / sizeof(uint64_t) < 32, "counter buffer");
+    unsigned long long h = 0;
+    HIPCHK(c, hipMemcpyAsync(&h, c->counters.as<unsigned long long>() + sizeof(rt_ray_counts) / sizeof(uint64_t),
+                             sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *elided = h;
+    return RT_OK;
+}
+
 int rt_selftest_math(rt_ctx* c, uint32_t n, float lo, float hi, uint32_t* mismatches)
 {
     if (!c || !mismatches || n == 0) return RT_E_INVALID;

@@ -39,7 +39,11 @@ __device__ __forceinline__ float comp(f3 a, uint32_t i) { return i == 0 ? a.x : 
 // ------------------------------------------------------------------ counters
 enum { C_SAMPLES, C_PRIMARY, C_SHADOW, C_BOUNCE, C_INTERIOR, C_LEAF, C_POPS, C_IDS, C_TESTS, C_ACCEPTS,
        C_TRIPS, C_LANE_STEPS, C_LEAF_LANE_STEPS, C_NODE_TRIPS, C_LEAF_TRIPS, C_EXACT_TESTS, C_EXACT_NODES,
-       C_SHADE_PASSES, C_SHADE_LANES, C_TRAV_CYC64, C_SHADE_CYC64, C_MEMWAIT_CYC64, C_CULLS, C_N };
+       C_SHADE_PASSES, C_SHADE_LANES, C_TRAV_CYC64, C_SHADE_CYC64, C_MEMWAIT_CYC64, C_CULLS,
+       // past rt_ray_counts' last member: shadow rays k_path resolved at shading time
+       // (rt_last_elided_shadows)
+       C_ELIDED, C_N };
+static_assert(C_ELIDED == sizeof(rt_ray_counts) / sizeof(uint64_t), "C_ELIDED follows rt_ray_counts' members");
 
 struct Counters {
     uint32_t v[C_N];

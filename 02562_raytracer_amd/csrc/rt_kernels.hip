@@ -760,7 +760,8 @@ __device__ __forceinline__ bool bsp_step_log(const DevScene& S, float* stk, cons
     }
     bool done = false, pop = false;
     if (in_leaf) {
-        // VSH (W9E1): every any-hit ray is a shadow ray of direction (0, 1, 0).  When
+        // VSH: for a caller whose any-hit rays all have direction (0, 1, 0), as W9E1's
+        // shadow rays (k_path no longer asks for it: it elides those rays).  When
         // all of the wave's leaf lanes hold one, the wave takes the tests' VERT form
         // (a uniform branch on a ballot of the any-hit flag; a ballot taken once per
         // check instead, outside the trips, measured slower: profiles/r06/ab_vsh.txt)
@@ -1377,10 +1378,16 @@ k_path(DevScene S, DevLaunch L)
     // walk draws no random numbers, so the PRNG sequence is the reference's, and
     // the direction (3 floats) need not be kept across the walk
     constexpr bool REDRAW = MODE == RT_MODE_W9E1 || MODE == MODE_W9E1_TRANSPARENT;
-    // W9E1: every shadow ray is light_init's (0, 1, 0) (the lambertian branch
-    // below); the BSP walk's leaf tests take their VERT form in the trips whose
-    // leaf lanes all hold one (W9E2 / W9E3 also send other any-hit rays)
-    constexpr bool VSH = REDRAW && TRAV == RT_TRAVERSE_BSP;
+    // Shadow-ray elision: a lambertian hit whose blocked and unblocked sums are the
+    // same bit patterns casts a shadow ray that cannot change the pixel (every W9E1
+    // hit: light_init's l_i is 0; a light sample that contributes exactly 0), so the
+    // walk is skipped.  Exact by construction for any material, +-0 and NaN included.
+    // The W9 modes elide; W7E3 and W8 keep every walk and the code they had (W7E3
+    // sits on its spill budget, tests/test_isa_guard.py; its zero samples are unmeasured).
+    // (W9E1's shadow rays are all light_init's (0, 1, 0), which the walk's VERT leaf
+    // form, trav_step's VSH, served until they were elided: a W9E1 shadow ray that
+    // still walks -- a non-finite material -- takes the general form.)
+    constexpr bool ELIDE = W9;
     const float ETA = W9 ? 0.0001f : 0.01f;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t T = L.shade_threshold;
@@ -1388,8 +1395,9 @@ k_path(DevScene S, DevLaunch L)
 #pragma unroll
     for (int i = 0; i < C_N; i++) cnt.v[i] = 0;
 
-    // lane state: ST_IDLE (no pixel), ST_TRACE (a ray in flight), ST_SHADE (ray done, waiting to shade)
-    enum : uint32_t { ST_IDLE = 0, ST_TRACE = 1, ST_SHADE = 2 };
+    // lane state: ST_IDLE (no pixel), ST_TRACE (a ray in flight), ST_SHADE (ray done, waiting to shade);
+    // within a shading pass ST_FIN (ELIDE): the lambertian hit's shadow ray is resolved, walked or elided
+    enum : uint32_t { ST_IDLE = 0, ST_TRACE = 1, ST_SHADE = 2, ST_FIN = 3 };
     uint32_t st = ST_IDLE;
     bool exhausted = L.spp == 0u, shadow = false, emit = true, survive = false, ao = false, hblk = false;
     uint32_t hph = 0;   // W9E3 holdout: 1 = occlusion ray in flight, 2 = sun ray in flight
@@ -1509,7 +1517,7 @@ k_path(DevScene S, DevLaunch L)
             }
             const bool go = st == ST_TRACE;
             if (go) {
-                if (trav_step<TRAV, COUNT, W9E3, CM, VSH>(S, stk, dp, ro, rd, inv, shadow, tr, cnt, chk)) st = ST_SHADE;
+                if (trav_step<TRAV, COUNT, W9E3, CM>(S, stk, dp, ro, rd, inv, shadow, tr, cnt, chk)) st = ST_SHADE;
             }
             // further steps before the next check: the check (two ballots, a
             // popcount, the compares) is SALU work, and the SALU is a per-CU
@@ -1517,7 +1525,7 @@ k_path(DevScene S, DevLaunch L)
 #pragma unroll
             for (int k = 1; k < (COUNT ? 1 : TRAV == RT_TRAVERSE_BVH ? RT_BVH_TRIPS_PER_CHECK : RT_TRIPS_PER_CHECK); ++k) {
                 if (st == ST_TRACE) {
-                    if (trav_step<TRAV, COUNT, W9E3, CM, VSH>(S, stk, dp, ro, rd, inv, shadow, tr, cnt, chk)) st = ST_SHADE;
+                    if (trav_step<TRAV, COUNT, W9E3, CM>(S, stk, dp, ro, rd, inv, shadow, tr, cnt, chk)) st = ST_SHADE;
                 }
             }
         }
@@ -1548,6 +1556,25 @@ k_path(DevScene S, DevLaunch L)
         // ---- shading phase
         if (st == ST_SHADE) {
             bool sample_done = false;
+            // rest of lambertian once the shadow ray is resolved, then the bounce (an
+            // elided shadow ray's lane runs it in the pass that shaded its hit: tr still
+            // holds that hit's record, which an any-hit walk leaves alone too)
+            const auto lambertian_rest = [&] {
+                if (survive && bounce + 1u < MAXD) {
+                    if (REDRAW) rd = indirect_dir(resolve<TRAV>(S, trav_out(tr), ro, rd, !W9).nrm, rng);
+                    else rd = ndir;   // origin = hit position, already in ro
+                    inv = trav_inv<TRAV>(rd);
+                    trav_start<TRAV>(tr, stk, ETA, ray_tmax<MODE>(ro, rd, ETA));
+                    capture_ray<COUNT>(L, ro, rd, ETA, ray_tmax<MODE>(ro, rd, ETA), false);
+                    emit = false;
+                    bounce++;
+                    shadow = false;
+                    st = ST_TRACE;
+                    cnt.v[C_BOUNCE]++;
+                } else {
+                    sample_done = true;
+                }
+            };
             if (!shadow) {
                 if (tr.found) {
                     // the hit's barycentrics, kept in tr across a shadow walk (REDRAW)
@@ -1599,9 +1626,24 @@ k_path(DevScene S, DevLaunch L)
                         shadow = true;
                         st = ST_TRACE;
                         cnt.v[C_SHADOW]++;
-                        float tpl = Lt.dist - ETA;
-                        if ((W8 && w8_balls(ro, rd, ETA, Lt.dist - ETA).id != 0u) ||
-                            (PLANE && w9_plane(ro, rd, ETA, tpl))) {
+                        // a ball / the plane between the point and the light
+                        const auto analytic_block = [&] {
+                            float tpl = Lt.dist - ETA;
+                            return (W8 && w8_balls(ro, rd, ETA, Lt.dist - ETA).id != 0u) ||
+                                   (PLANE && w9_plane(ro, rd, ETA, tpl));
+                        };
+                        // the two sums are the same bits (W9E1: light_init's l_i = 0): the
+                        // shadow ray decides nothing, so it is counted and captured as the
+                        // shader's ray and not walked; the lane goes on below in this pass
+                        if (ELIDE && ((__float_as_uint(res.x) ^ __float_as_uint(cb.x)) |
+                                      (__float_as_uint(res.y) ^ __float_as_uint(cb.y)) |
+                                      (__float_as_uint(res.z) ^ __float_as_uint(cb.z))) == 0u) {
+                            st = ST_FIN;
+                            if constexpr (COUNT) {   // (the capture stream keeps the rays it held)
+                                cnt.v[C_ELIDED]++;
+                                if (!analytic_block()) capture_ray<COUNT>(L, ro, rd, ETA, Lt.dist - ETA, true);
+                            }
+                        } else if (analytic_block()) {
                             tr.found = true;   // a ball / the plane blocks the light: no mesh walk
                             st = ST_SHADE;
                         } else {
@@ -1755,22 +1797,14 @@ k_path(DevScene S, DevLaunch L)
                 res = add(res, tr.found ? V(0, 0, 0) : mul(env_at<MODE>(L, env, ndir), fac));
                 sample_done = true;
             } else {
-                // shadow ray finished: rest of lambertian, then the bounce
+                // shadow ray finished: the blocked sum if it hit
                 if (tr.found) res = cb;
-                if (survive && bounce + 1u < MAXD) {
-                    if (REDRAW) rd = indirect_dir(resolve<TRAV>(S, trav_out(tr), ro, rd, !W9).nrm, rng);
-                    else rd = ndir;   // origin = hit position, already in ro
-                    inv = trav_inv<TRAV>(rd);
-                    trav_start<TRAV>(tr, stk, ETA, ray_tmax<MODE>(ro, rd, ETA));
-                    capture_ray<COUNT>(L, ro, rd, ETA, ray_tmax<MODE>(ro, rd, ETA), false);
-                    emit = false;
-                    bounce++;
-                    shadow = false;
-                    st = ST_TRACE;
-                    cnt.v[C_BOUNCE]++;
-                } else {
-                    sample_done = true;
-                }
+                if constexpr (ELIDE) st = ST_FIN;
+                else lambertian_rest();
+            }
+            // (with the lanes that elided their shadow ray in this pass)
+            if constexpr (ELIDE) {
+                if (st == ST_FIN) lambertian_rest();
             }
             if (sample_done) {
                 // this iteration's `result` (+ primary id); k_fold accumulates in

@@ -584,6 +584,16 @@ int rt_trace_rays(rt_ctx* ctx, rt_traverse trav, const float* rays, const uint32
 /* Counters of the most recent launch (synchronizes). */
 int rt_last_counts(rt_ctx* ctx, rt_ray_counts* counts);
 
+/* Shadow rays of the most recent launch that the path kernel resolved at shading
+ * time instead of walking (synchronizes): a lambertian hit whose blocked and
+ * unblocked radiance sums are the same bit patterns -- every W9E1 hit, whose light
+ * is light_init()'s l_i = 0 -- casts a shadow ray that cannot change the pixel.
+ * The W9 modes elide such rays.  They stay counted in rt_ray_counts.shadow (the
+ * rays the reference's shader casts), so shadow - elided is what walked the
+ * mesh (less the rays the W9 plane stopped).  Filled by the counting instantiation
+ * only: 0 when RT_OPT_DETAIL_COUNTERS is off. */
+int rt_last_elided_shadows(rt_ctx* ctx, uint64_t* elided);
+
 /* Device-vs-host self check of the pinned f32 math (sqrt, division, the
  * rt_detmath.h transcendentals) over n inputs in [lo, hi]; returns the number
  * of bit mismatches in *mismatches. */

@@ -20,17 +20,24 @@ from collections import defaultdict
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def load(root, ksub=None):
+def load(root, ksub=None, last_only=False):
+    """last_only: of each pass, only the kernel's last dispatch (a short bench run's first
+    step splits its frame into the auto probe's partial launches; the last launch is a
+    whole frame)."""
     per = defaultdict(lambda: defaultdict(float))   # kernel -> counter -> sum over dispatches
     disp = defaultdict(set)
     for f in sorted(glob.glob(f"{root}/**/*counter_collection.csv", recursive=True)):
         with open(f) as fh:
-            for r in csv.DictReader(fh):
-                k = r["Kernel_Name"]
-                if ksub and ksub not in k:
-                    continue
-                per[k][r["Counter_Name"]] += float(r["Counter_Value"])
-                disp[(k, r["Counter_Name"])].add((f, r["Dispatch_Id"]))
+            rows = [r for r in csv.DictReader(fh) if not ksub or ksub in r["Kernel_Name"]]
+        last = {}
+        for r in rows:
+            last[r["Kernel_Name"]] = max(last.get(r["Kernel_Name"], -1), int(r["Dispatch_Id"]))
+        for r in rows:
+            k = r["Kernel_Name"]
+            if last_only and int(r["Dispatch_Id"]) != last[k]:
+                continue
+            per[k][r["Counter_Name"]] += float(r["Counter_Value"])
+            disp[(k, r["Counter_Name"])].add((f, r["Dispatch_Id"]))
     return {k: {c: v / max(1, len(disp[(k, c)])) for c, v in cs.items()} for k, cs in per.items()}
 
 
@@ -59,8 +66,11 @@ if __name__ == "__main__":
     ap.add_argument("--summary")
     ap.add_argument("--source", help="profiles/ path recorded as the summary's source")
     ap.add_argument("--bench-json", help="the bench line of the same build: its roofline.fatbin_sha16 is recorded")
+    ap.add_argument("--last-dispatch", action="store_true",
+                    help="count only the kernel's last dispatch of each pass (the whole-frame launch of a run "
+                         "whose first step holds the auto probe's partial launches)")
     a = ap.parse_args()
-    res = load(a.dir, a.kernel)
+    res = load(a.dir, a.kernel, a.last_dispatch)
     out = {k: {"counters": c, "derived": derived(c)} for k, c in res.items()}
     txt = json.dumps(out, indent=1)
     print(txt)
