@@ -63,6 +63,9 @@ WORKSHEET1_MODES = ("W1E2", "W1E3", "W1E4", "W1E5")
 LINEAR_DISPLAY_MODES = ("W1E2", "W1E3")
 # progressive path tracers (per-iteration samples folded in order)
 PATH_MODES = ("W7E3", "W9E1", "W8E1", "W8E2", "W8E3", "W9E2", "W7E1", "W7E2", "W9E3")
+# ... of which these write per-iteration records (k_path): the modes a noise buffer follows
+# (rt_set_noise_buffer); W7E1 and W7E2 fold inside their kernel
+NOISE_MODES = ("W7E3", "W9E1", "W8E1", "W8E2", "W8E3", "W9E2", "W9E3")
 TRAVERSALS = {"BSP": RT_TRAVERSE_BSP, "BVH": RT_TRAVERSE_BVH, "NONE": RT_TRAVERSE_NONE}
 
 u32p = C.POINTER(C.c_uint32)
@@ -127,6 +130,19 @@ class RayCounts(C.Structure):
         return {n: int(getattr(self, n)) for n in COUNT_FIELDS}
 
 
+class NoiseState(C.Structure):        # include/rt.h rt_noise_state
+    _fields_ = [("mean", C.c_float), ("m2", C.c_float)]
+
+
+class NoiseSummary(C.Structure):      # include/rt.h rt_noise_summary
+    _fields_ = [("pixels", C.c_uint64), ("above", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("max_rel_err", C.c_float), ("reserved", C.c_float)]
+
+    def asdict(self):
+        return {"pixels": int(self.pixels), "above": int(self.above), "nonfinite": int(self.nonfinite),
+                "max_rel_err": float(self.max_rel_err)}
+
+
 class MeshView(C.Structure):
     _fields_ = [("vertices", f32p), ("normals", f32p), ("indices", u32p), ("materials", C.POINTER(Material)),
                 ("lights", u32p), ("nverts", C.c_uint32), ("ntris", C.c_uint32), ("nmats", C.c_uint32),
@@ -182,6 +198,11 @@ SIGNATURES = {
     "rt_render_tiles": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(Tileset), C.c_uint32, C.c_uint32, vp, vp,
                                   C.POINTER(RayCounts)]),
     "rt_tileset_local_tiles": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rt_set_noise_buffer": (C.c_int, [vp, vp]),
+    "rt_noise_accumulate": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, vp]),
+    "rt_noise_map": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_float, vp]),
+    "rt_noise_summarize": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
+                                     C.POINTER(NoiseSummary)]),
     "rt_unpack_tiles": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "rt_comm_unique_id": (C.c_int, [vp]),
     "rt_comm_init": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),

@@ -430,6 +430,29 @@ class Context:
         self._chk(F.lib().rt_unpack_tiles(self._h, width, height, nranks, vpn(packed_accum), vpn(packed_ids),
                                           vpn(frame_accum), vpn(frame_ids)))
 
+    # ---- the noise estimate of the path modes (include/rt.h "noise estimate")
+    def set_noise_buffer(self, state_ptr=None):
+        """rt_set_noise_buffer: the device buffer of rt_noise_state (8 B per output slot,
+        indexed as accum) the path modes' renders update; None turns it off."""
+        self._chk(F.lib().rt_set_noise_buffer(self._h, C.c_void_p(state_ptr) if state_ptr else None))
+
+    def noise_accumulate(self, samples_ptr, npix, spp, pixel_major, first_iter, state_ptr):
+        """rt_noise_accumulate: device records (float4) [pixel][iteration] (pixel_major) or
+        [iteration][pixel] of iterations first_iter.. into the device state."""
+        self._chk(F.lib().rt_noise_accumulate(self._h, C.c_void_p(samples_ptr), npix, spp, int(bool(pixel_major)),
+                                              first_iter, C.c_void_p(state_ptr)))
+
+    def noise_map(self, state_ptr, npix, n, floor, rel_ptr):
+        """rt_noise_map: the relative standard error after n iterations per slot (device pointers)."""
+        self._chk(F.lib().rt_noise_map(self._h, C.c_void_p(state_ptr), npix, n, float(floor), C.c_void_p(rel_ptr)))
+
+    def noise_summary(self, state_ptr, npix, n, threshold, floor=1e-3):
+        """rt_noise_summarize: {pixels, above, nonfinite, max_rel_err}; synchronizes."""
+        s = F.NoiseSummary()
+        self._chk(F.lib().rt_noise_summarize(self._h, C.c_void_p(state_ptr), npix, n, float(threshold), float(floor),
+                                             C.byref(s)))
+        return s.asdict()
+
     # ---- the tile gather over RCCL (include/rt.h "multi-GPU")
     @staticmethod
     def comm_unique_id():

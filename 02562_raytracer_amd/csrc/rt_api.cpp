@@ -156,6 +156,9 @@ struct rt_ctx {
     uint32_t* cap_flags = nullptr;
     uint64_t cap_max = 0;
     DevBuf cap_count;
+    // rt_set_noise_buffer: the path modes' renders update it after every fold (device, caller-owned)
+    rt_noise_state* noise = nullptr;
+    DevBuf noise_sum;   // rt_noise_summarize's 24-B result
     ncclComm_t comm = nullptr;
     uint32_t comm_nranks = 0, comm_rank = 0;
     DevBuf gather_accum, gather_ids;   // rank 0: every rank's packed tiles, rank-major
@@ -1431,6 +1434,9 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
                 HIPCHK(c, hipStreamWaitEvent(c->fold_stream, c->ev_path, 0));
                 const int r = rtk::launch_fold(L, c->fold_stream);
                 if (r) return fail(c, r, std::string("fold launch failed: ") + hipGetErrorString(hipGetLastError()));
+                // (before ev_free[b]: the scratch buffer is not reused under it)
+                if (c->noise && rtk::launch_noise(L, c->noise, c->fold_stream))
+                    return fail(c, RT_E_DEVICE, std::string("noise launch failed: ") + hipGetErrorString(hipGetLastError()));
                 HIPCHK(c, hipEventRecord(c->ev_free[b], c->fold_stream));
                 c->fold_pending = true;
                 continue;
@@ -1439,6 +1445,8 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
             if (int r = probe_launch(c, S, L, mode, trav, slot)) return r;
             const int r = rtk::launch_fold(L, c->stream);
             if (r) return fail(c, r, std::string("fold launch failed: ") + hipGetErrorString(hipGetLastError()));
+            if (c->noise && rtk::launch_noise(L, c->noise, c->stream))
+                return fail(c, RT_E_DEVICE, std::string("noise launch failed: ") + hipGetErrorString(hipGetLastError()));
         }
     } else if (analytic) {
         rtk::AnalyticTex T;
@@ -1538,6 +1546,92 @@ int rt_render_tiles(rt_ctx* c, rt_mode mode, rt_traverse trav, const rt_tileset*
     L.accum = reinterpret_cast<float4*>(accum);
     L.ids = ids;
     return render_common(c, mode, trav, L, counts);
+}
+
+// ---- the noise estimate (rt.h "noise estimate"; rt_noise.hip) -----------------
+int rt_set_noise_buffer(rt_ctx* c, rt_noise_state* state_dev)
+{
+    if (!c) return fail(nullptr, RT_E_INVALID, "rt_set_noise_buffer: null context");
+    if ((uintptr_t)state_dev % 8) return fail(c, RT_E_INVALID, "rt_set_noise_buffer: the state must be 8-byte aligned");
+    c->noise = state_dev;
+    return RT_OK;
+}
+
+int rt_noise_accumulate(rt_ctx* c, const float* samples, uint32_t npix, uint32_t spp, int pixel_major,
+                        uint32_t first_iter, rt_noise_state* state)
+{
+    if (!c) return fail(nullptr, RT_E_INVALID, "rt_noise_accumulate: null context");
+    if (npix == 0 || spp == 0) return RT_OK;
+    if (!samples || !state) return fail(c, RT_E_INVALID, "rt_noise_accumulate: null buffer");
+    if ((uintptr_t)samples % 16 || (uintptr_t)state % 8)
+        return fail(c, RT_E_INVALID, "rt_noise_accumulate: the records must be 16-byte and the state 8-byte aligned");
+    if (int r = set_dev(c)) return r;
+    // k_noise's view of the records: a region of npix x 1 pixels, one pass
+    rtk::DevLaunch L;
+    memset(&L, 0, sizeof L);
+    L.w = npix;
+    L.h = 1;
+    L.nranks = 1;
+    L.tiles_x = (npix + 7) / 8;
+    L.tiles_y = 1;
+    L.nwork = L.tiles_x;
+    L.first_iter = first_iter;
+    L.spp = spp;
+    L.chunk = 1;
+    L.nchunks = spp;
+    L.unit_order = pixel_major ? 1u : 0u;
+    L.stride = npix;
+    L.samples = reinterpret_cast<float4*>(const_cast<float*>(samples));   // (read only)
+    if (rtk::launch_noise(L, state, c->stream))
+        return fail(c, RT_E_DEVICE, std::string("rt_noise_accumulate: launch failed: ") +
+                                        hipGetErrorString(hipGetLastError()));
+    return RT_OK;
+}
+
+static int noise_args(rt_ctx* c, const char* who, const void* state, uint32_t npix, uint32_t n, float floor)
+{
+    if (n < 2) return fail(c, RT_E_INVALID, std::string(who) + ": the standard error needs n >= 2 iterations");
+    if (!(floor > 0.0f)) return fail(c, RT_E_INVALID, std::string(who) + ": floor must be > 0");
+    if (!state && npix) return fail(c, RT_E_INVALID, std::string(who) + ": null state");
+    if ((uintptr_t)state % 8) return fail(c, RT_E_INVALID, std::string(who) + ": the state must be 8-byte aligned");
+    return RT_OK;
+}
+
+int rt_noise_map(rt_ctx* c, const rt_noise_state* state, uint32_t npix, uint32_t n, float floor, float* rel)
+{
+    if (!c) return fail(nullptr, RT_E_INVALID, "rt_noise_map: null context");
+    if (int r = noise_args(c, "rt_noise_map", state, npix, n, floor)) return r;
+    if (!rel && npix) return fail(c, RT_E_INVALID, "rt_noise_map: null map");
+    if (npix == 0) return RT_OK;
+    if (int r = set_dev(c)) return r;
+    if (rtk::launch_noise_map(state, npix, n, floor, rel, c->stream))
+        return fail(c, RT_E_DEVICE, "rt_noise_map: launch failed");
+    return RT_OK;
+}
+
+int rt_noise_summarize(rt_ctx* c, const rt_noise_state* state, uint32_t npix, uint32_t n, float threshold,
+                       float floor, rt_noise_summary* out)
+{
+    if (!c) return fail(nullptr, RT_E_INVALID, "rt_noise_summarize: null context");
+    if (!out) return fail(c, RT_E_INVALID, "rt_noise_summarize: null summary");
+    if (int r = noise_args(c, "rt_noise_summarize", state, npix, n, floor)) return r;
+    if (threshold != threshold) return fail(c, RT_E_INVALID, "rt_noise_summarize: the threshold is NaN");
+    memset(out, 0, sizeof *out);
+    out->pixels = npix;
+    if (npix == 0) return RT_OK;
+    if (int r = set_dev(c)) return r;
+    HIPCHK(c, c->noise_sum.ensure(32));
+    HIPCHK(c, hipMemsetAsync(c->noise_sum.p, 0, 32, c->stream));
+    if (rtk::launch_noise_summary(state, npix, n, threshold, floor, c->noise_sum.as<unsigned long long>(), c->stream))
+        return fail(c, RT_E_DEVICE, "rt_noise_summarize: launch failed");
+    unsigned long long h[3] = {0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(h, c->noise_sum.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out->above = h[0];
+    out->nonfinite = h[1];
+    const uint32_t bits = (uint32_t)h[2];
+    memcpy(&out->max_rel_err, &bits, 4);
+    return RT_OK;
 }
 
 // The 255 thresholds of 8-bit sRGB codes: code k+1 starts where

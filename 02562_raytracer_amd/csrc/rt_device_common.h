@@ -1,5 +1,5 @@
 // rt_device_common.h -- device helpers shared by the kernel translation units
-// (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip): the f32 vector
+// (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip, rt_noise.hip): the f32 vector
 // math of the WGSL builtins, the per-launch counters and the wave sum, the camera ray
 // of get_camera_ray and the work mapping of one 8x8 tile per wave.  Not part of the
 // public ABI.

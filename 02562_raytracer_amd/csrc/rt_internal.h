@@ -1,5 +1,5 @@
 // rt_internal.h -- launch interface between the C ABI layer (rt_api.cpp) and
-// the gfx950 kernels (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip),
+// the gfx950 kernels (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip, rt_noise.hip),
 // and what the launchers of the flat modes share: their grid and the expansion of a
 // run-time (mode, detail) into template constants.  Not part of the public ABI.
 #pragma once
@@ -197,6 +197,17 @@ int launch_trace_batch(const DevScene& s, const float* rays, const uint32_t* fla
 
 // Progressive average of one pass's per-iteration samples into accum/ids (after k_path).
 int launch_fold(const DevLaunch& l, hipStream_t stream);
+
+// The noise estimate (rt_noise.hip; rt.h "noise estimate").  launch_noise: the luminance of the
+// same pass's records into state's running mean and m2, slot for slot as k_fold addresses
+// accum (after launch_fold, on its stream; l.first_iter == 0 starts from {0, 0}).
+int launch_noise(const DevLaunch& l, rt_noise_state* state, hipStream_t stream);
+// rel[i] = the relative standard error of state[i] after n iterations (0x7FC00000: non-finite state)
+int launch_noise_map(const rt_noise_state* state, uint32_t npix, uint32_t n, float floor, float* rel,
+                     hipStream_t stream);
+// out (device, 24 B, zeroed before the launch): u64 above, u64 nonfinite, u32 bits of the largest finite pixel's rel
+int launch_noise_summary(const rt_noise_state* state, uint32_t npix, uint32_t n, float threshold, float floor,
+                         unsigned long long* out, hipStream_t stream);
 
 // display frame: RGBA32F accum -> 8-bit sRGB (thr: 255 device floats, srgb_code_thresholds)
 int launch_frame(const float4* accum, uint32_t npix, const float* thr, uchar4* out, hipStream_t stream);

@@ -1,0 +1,161 @@
+// rt_noise.hip -- the per-pixel noise estimate of the path modes (rt.h "noise estimate",
+// DESIGN.md section 4): a running mean and sum of squared deviations (Welford) of every
+// iteration's luminance, read from the per-iteration records k_path wrote and k_fold
+// averaged, the relative standard error of the mean per pixel, and a frame summary.
+// Its own translation unit, so that the register allocation of rt_kernels.hip's kernels
+// does not move with it (tests/test_isa_guard.py).
+//
+// The arithmetic is pinned (f32, no contraction, correctly rounded / and sqrt; the
+// Makefile's NUMFLAGS), one operation per line of rt.h's definition, so that
+// tests/noise_ref.py restates it in numpy bit for bit.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rt_device_common.h"
+
+namespace rtk {
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+// one record into the state: it = the iteration's global index
+__device__ __forceinline__ void noise1(float& mean, float& m2, const v4f x, uint32_t it)
+{
+    const float y = (0.2126f * x.x + 0.7152f * x.y) + 0.0722f * x.z;
+    const float n = (float)(it + 1u);
+    const float d = y - mean;
+    mean = mean + d / n;
+    m2 = m2 + d * (y - mean);
+}
+
+// ------------------------------------------------------------------ state update
+// After k_fold, over the same records and with the same addressing (rt_kernels.hip
+// k_fold): one thread per output slot.  [pixel][iteration] records are the thread's own
+// contiguous run, loaded eight (128 B, one line) at a time; [iteration][pixel] records
+// are 1 KiB contiguous per wave and iteration.  The records are not read again after
+// this kernel, the state is: streaming loads for the chunk-major layout as in k_fold.
+// spp x 16 B read and 8 B written per pixel (8 B more read when first_iter > 0).
+__global__ void __launch_bounds__(256) k_noise(DevLaunch L, rt_noise_state* __restrict__ state)
+{
+    const uint32_t nout = L.tileset ? L.nwork * 64u : L.w * L.h;
+    for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < nout; o += gridDim.x * blockDim.x) {
+        if (L.tileset && !map_pixel(L, o >> 6, o & 63u).valid) continue;
+        v2f* const st = reinterpret_cast<v2f*>(state + o);
+        float mean = 0.0f, m2 = 0.0f;
+        if (L.first_iter > 0u) {
+            const v2f s = *st;
+            mean = s.x;
+            m2 = s.y;
+        }
+        uint32_t i = 0;
+        if (L.unit_order) {
+            const v4f* sp = reinterpret_cast<const v4f*>(L.samples + (size_t)o * L.spp);
+            for (; i + 8u <= L.spp; i += 8u) {
+                v4f q[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) q[k] = sp[i + k];
+#pragma unroll
+                for (int k = 0; k < 8; k++) noise1(mean, m2, q[k], L.first_iter + i + k);
+            }
+            for (; i < L.spp; i++) noise1(mean, m2, sp[i], L.first_iter + i);
+        } else {
+            const v4f* sp = reinterpret_cast<const v4f*>(L.samples + o);
+            for (; i < L.spp; i++)
+                noise1(mean, m2, __builtin_nontemporal_load(sp + (size_t)i * L.stride), L.first_iter + i);
+        }
+        const v2f s = {mean, m2};
+        *st = s;
+    }
+}
+
+// ------------------------------------------------------------------ map and summary
+__device__ __forceinline__ bool finitef(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+
+// the relative standard error of the mean of a finite state after n >= 2 iterations
+// (denom = nf * (nf - 1)); never NaN: m2 is clamped, denom and the floor are positive
+__device__ __forceinline__ float noise_rel(float mean, float m2, float denom, float floor)
+{
+    const float var = (m2 < 0.0f ? 0.0f : m2) / denom;
+    const float a = rt_absf(mean);
+    return rt_det_sqrtf(var) / (a < floor ? floor : a);
+}
+
+__global__ void __launch_bounds__(256) k_noise_map(const rt_noise_state* __restrict__ state, uint32_t npix, float nf,
+                                                   float floor, uint32_t* __restrict__ rel)
+{
+    const float denom = nf * (nf - 1.0f);
+    for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < npix; o += gridDim.x * blockDim.x) {
+        const v2f s = *reinterpret_cast<const v2f*>(state + o);
+        // a non-finite state: the canonical quiet NaN, whatever the state's payload
+        rel[o] = finitef(s.x) && finitef(s.y) ? __float_as_uint(noise_rel(s.x, s.y, denom, floor)) : 0x7FC00000u;
+    }
+}
+
+// out: {above, nonfinite} as u64 and the bits of the largest rel as u32 at out + 2, zeroed
+// before the launch.  Deterministic: the counts are integer sums (per wave, then one
+// atomic each), and the maximum is an integer maximum of the bit patterns, which order
+// non-negative floats (+inf included) as their values do.
+__global__ void __launch_bounds__(256) k_noise_summary(const rt_noise_state* __restrict__ state, uint32_t npix,
+                                                       float nf, float threshold, float floor,
+                                                       unsigned long long* __restrict__ out)
+{
+    const float denom = nf * (nf - 1.0f);
+    unsigned long long above = 0, nonfinite = 0;
+    uint32_t mx = 0;
+    for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < npix; o += gridDim.x * blockDim.x) {
+        const v2f s = *reinterpret_cast<const v2f*>(state + o);
+        if (finitef(s.x) && finitef(s.y)) {
+            const float r = noise_rel(s.x, s.y, denom, floor);
+            if (r > threshold) above++;
+            const uint32_t b = __float_as_uint(r) & 0x7FFFFFFFu;   // (-0 cannot occur; kept an unsigned order)
+            mx = b > mx ? b : mx;
+        } else {
+            nonfinite++;
+        }
+    }
+    above = wave_sum(above);
+    nonfinite = wave_sum(nonfinite);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t other = __shfl_xor(mx, off, 64);
+        mx = other > mx ? other : mx;
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (above) atomicAdd(out + 0, above);
+        if (nonfinite) atomicAdd(out + 1, nonfinite);
+        if (mx) atomicMax(reinterpret_cast<uint32_t*>(out + 2), mx);
+    }
+}
+
+// ------------------------------------------------------------------ launchers
+static uint32_t stream_blocks(uint64_t n, uint64_t cap)
+{
+    const uint64_t b = (n + 255) / 256;
+    return (uint32_t)(b > cap ? cap : b ? b : 1);
+}
+
+int launch_noise(const DevLaunch& l, rt_noise_state* state, hipStream_t stream)
+{
+    // k_fold's grid (launch_fold): the two kernels stream the same records
+    const uint64_t nout = l.tileset ? (uint64_t)l.nwork * 64u : (uint64_t)l.w * l.h;
+    hipLaunchKernelGGL(k_noise, dim3(stream_blocks(nout, 16384)), dim3(256), 0, stream, l, state);
+    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
+}
+
+int launch_noise_map(const rt_noise_state* state, uint32_t npix, uint32_t n, float floor, float* rel,
+                     hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_noise_map, dim3(stream_blocks(npix, 2048)), dim3(256), 0, stream, state, npix, (float)n, floor,
+                       reinterpret_cast<uint32_t*>(rel));
+    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
+}
+
+int launch_noise_summary(const rt_noise_state* state, uint32_t npix, uint32_t n, float threshold, float floor,
+                         unsigned long long* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_noise_summary, dim3(stream_blocks(npix, 2048)), dim3(256), 0, stream, state, npix, (float)n,
+                       threshold, floor, out);
+    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
+}
+
+}  // namespace rtk

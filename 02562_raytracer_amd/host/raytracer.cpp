@@ -4,6 +4,7 @@
 // INTEGRATION.md would make them.
 #include "raytracer.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <sys/stat.h>
@@ -362,12 +363,85 @@ void RenderState::release()
     if (ids_) rt_device_free(gpu_.ctx(), ids_);
     if (tile_accum_) rt_device_free(gpu_.ctx(), tile_accum_);
     if (tile_ids_) rt_device_free(gpu_.ctx(), tile_ids_);
-    accum_ = ids_ = tile_accum_ = tile_ids_ = nullptr;
+    if (noise_) {
+        rt_set_noise_buffer(gpu_.ctx(), nullptr);
+        rt_device_free(gpu_.ctx(), noise_);
+    }
+    accum_ = ids_ = tile_accum_ = tile_ids_ = noise_ = nullptr;
+}
+
+static bool writes_records(rt_mode m)   // the k_path modes (rt.h "noise estimate")
+{
+    return m == RT_MODE_W7E3 || m == RT_MODE_W9E1 || m == RT_MODE_W8E1 || m == RT_MODE_W8E2 || m == RT_MODE_W8E3 ||
+           m == RT_MODE_W9E2 || m == RT_MODE_W9E3;
+}
+
+void RenderState::enable_noise()
+{
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, "enable_noise is for an untiled state: a tiled render (set_tiling, any rank count) keeps its states packed per tile");
+    if (!writes_records(mode_))
+        throw Error(RT_E_UNSUPPORTED, "enable_noise: the mode writes no per-iteration records");
+    if (iteration_) throw Error(RT_E_INVALID, "enable_noise: the estimate starts at iteration 0");
+    rt_ctx* c = gpu_.ctx();
+    if (!noise_) {
+        const size_t npx = (size_t)width_ * height_;
+        gpu_.check(rt_device_alloc(c, npx * sizeof(rt_noise_state), &noise_), "noise buffer");
+        gpu_.check(rt_memset_device(c, noise_, 0, npx * sizeof(rt_noise_state)), "clear noise buffer");
+    }
+    gpu_.check(rt_set_noise_buffer(c, static_cast<rt_noise_state*>(noise_)), "set noise buffer");
+}
+
+std::vector<float> RenderState::noise_map(float floor) const
+{
+    if (!noise_) throw Error(RT_E_NOT_READY, "noise_map: enable_noise() first");
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, "noise_map is for an untiled state: a tiled render (set_tiling, any rank count) keeps its states packed per tile");
+    const size_t npx = (size_t)width_ * height_;
+    void* d = nullptr;
+    gpu_.check(rt_device_alloc(gpu_.ctx(), npx * 4, &d), "noise map buffer");
+    std::vector<float> out(npx);
+    int rc = rt_noise_map(gpu_.ctx(), static_cast<const rt_noise_state*>(noise_), (uint32_t)npx, iteration_, floor,
+                          static_cast<float*>(d));
+    if (rc == RT_OK) rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), d, npx * 4);
+    rt_device_free(gpu_.ctx(), d);
+    gpu_.check(rc, "noise_map");
+    return out;
+}
+
+rt_noise_summary RenderState::noise_summary(float threshold, float floor) const
+{
+    if (!noise_) throw Error(RT_E_NOT_READY, "noise_summary: enable_noise() first");
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, "noise_summary is for an untiled state: a tiled render (set_tiling, any rank count) keeps its states packed per tile");
+    rt_noise_summary s;
+    gpu_.check(rt_noise_summarize(gpu_.ctx(), static_cast<const rt_noise_state*>(noise_),
+                                  (uint32_t)((size_t)width_ * height_), iteration_, threshold, floor, &s),
+               "noise_summary");
+    return s;
+}
+
+uint32_t RenderState::render_until(float target, uint32_t max_samples, uint32_t batch, double allow, float floor,
+                                   rt_noise_summary* summary)
+{
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, "render_until is for an untiled state: a tiled render (set_tiling, any rank count) keeps its states packed per tile");
+    if (!progressive_) throw Error(RT_E_INVALID, "render_until needs progressive rendering");
+    if (batch == 0) throw Error(RT_E_INVALID, "render_until: batch must be at least 1");
+    if (!noise_) enable_noise();
+    rt_noise_summary s{};
+    while (iteration_ < max_samples) {
+        render(std::min(batch, max_samples - iteration_));
+        if (iteration_ >= 2) {
+            s = noise_summary(target, floor);
+            if ((double)s.above <= allow * (double)s.pixels) break;
+        }
+    }
+    if (summary) *summary = s;
+    return iteration_;
 }
 
 void RenderState::set_tiling(uint32_t nranks, uint32_t rank, const uint8_t comm_id[RT_COMM_ID_BYTES])
 {
     if (tiled_) throw Error(RT_E_INVALID, "set_tiling: already tiled");
+    // the noise buffer is width x height states, row-major; tile renders would write it packed per tile
+    if (noise_) throw Error(RT_E_UNSUPPORTED, "set_tiling: the noise estimate is enabled (it is for an untiled state)");
     gpu_.check(rt_comm_init(gpu_.ctx(), nranks, rank, comm_id), "communicator");
     nranks_ = nranks;
     rank_ = rank;
@@ -448,6 +522,7 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
     }
     gpu_.check(rt_set_environment(c, opts_.environment.data()), "environment");
     gpu_.check(rt_set_environment_map(c, nullptr, 0, 0), "environment map");
+    const bool had_noise = noise_ != nullptr;
     release();
     const size_t npx = (size_t)width_ * height_;
     gpu_.check(rt_device_alloc(c, npx * 16, &accum_), "accumulation buffer");
@@ -455,6 +530,7 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
     gpu_.check(rt_memset_device(c, accum_, 0, npx * 16), "clear accumulation");
     alloc_tiles();
     iteration_ = 0;
+    if (had_noise && writes_records(mode_)) enable_noise();   // the buffer follows the scene
     update();
 }
 

@@ -9,6 +9,14 @@
 //             [--subdiv K] [--camera-constant C] [--device-build]
 //             [--env-rgba FILE --env-size WxH] [--tex-rgba FILE --tex-size WxH]
 //             [--models DIR] [--out PREFIX]
+//             [--noise-target T [--noise-batch B] [--noise-allow F]]
+//                                        (a path-mode scene: render B (16) iterations at a time
+//                                        until at most F (0) x pixels have a relative standard
+//                                        error above T, or --samples / --spp (1024) iterations
+//                                        are done; the JSON line gains "noise": {iterations,
+//                                        pixels, above, nonfinite, max_rel_err}, and --out
+//                                        writes PREFIX.noise.f32, the H*W map; an untiled
+//                                        render only: refused with --comm-file / --nranks)
 //   rt_render ... --nranks N --rank R --comm-file PATH [--comm-token T] [--device D]
 //                                        (one process per GPU: rank R renders its
 //                                        interleaved tiles, rank 0 gathers the frame
@@ -225,6 +233,10 @@ int main(int argc, char** argv)
         const uint32_t rank = arg("--rank") ? (uint32_t)std::atoi(arg("--rank")->c_str()) : 0;
         if (nranks == 0 || rank >= nranks) throw Error(RT_E_INVALID, "--rank must be below --nranks");
         if (nranks > 1 && !arg("--comm-file")) throw Error(RT_E_INVALID, "--nranks needs --comm-file PATH");
+        // the noise estimate is for an untiled state: --comm-file tiles the render for any rank count
+        // (--nranks 1 too), and its states would be packed per tile, not the H x W map
+        if (arg("--noise-target") && (nranks > 1 || arg("--comm-file")))
+            throw Error(RT_E_UNSUPPORTED, "--noise-target does not go with --comm-file / --nranks (a tiled render)");
         GpuHandles gpu(arg("--device") ? std::atoi(arg("--device")->c_str()) : (int)rank);
         RenderState rs(gpu, find_scene(*name), opt);
         if (const std::string* cf = arg("--comm-file")) {
@@ -274,7 +286,30 @@ int main(int argc, char** argv)
             rs.update();
         }
         uint32_t frames = 0;
-        if (const std::string* s = arg("--samples")) {   // the progressive loop, SetSamples
+        std::string noise_json;
+        if (const std::string* t = arg("--noise-target")) {   // render until converged (render_until)
+            const uint32_t cap = arg("--samples") ? (uint32_t)std::atoi(arg("--samples")->c_str())
+                                 : arg("--spp")   ? (uint32_t)std::atoi(arg("--spp")->c_str())
+                                                  : 1024u;
+            const uint32_t batch = arg("--noise-batch") ? (uint32_t)std::atoi(arg("--noise-batch")->c_str()) : 16u;
+            const double allow = arg("--noise-allow") ? std::atof(arg("--noise-allow")->c_str()) : 0.0;
+            rt_noise_summary ns;
+            const uint32_t its = rs.render_until((float)std::atof(t->c_str()), cap, batch, allow, 1e-3f, &ns);
+            frames = (its + batch - 1) / batch;
+            if (const std::string* out = arg("--out")) {
+                if (its >= 2) {
+                    const auto nm = rs.noise_map();
+                    write_file(*out + ".noise.f32", nm.data(), nm.size() * 4);
+                }
+            }
+            char b[256];
+            std::snprintf(b, sizeof b,
+                          ",\"noise\":{\"iterations\":%u,\"pixels\":%llu,\"above\":%llu,\"nonfinite\":%llu,"
+                          "\"max_rel_err\":%s}",
+                          its, (unsigned long long)ns.pixels, (unsigned long long)ns.above,
+                          (unsigned long long)ns.nonfinite, hexf(ns.max_rel_err).c_str());
+            noise_json = b;
+        } else if (const std::string* s = arg("--samples")) {   // the progressive loop, SetSamples
             rs.set_samples((uint32_t)std::atoi(s->c_str()), true);
             while (rs.step()) frames++;
         } else {
@@ -293,10 +328,11 @@ int main(int argc, char** argv)
             write_file(*out + ".rgba8", rgba.data(), rgba.size());
         }
         std::printf("{\"scene\":%s,\"mode\":%s,\"width\":%u,\"height\":%u,\"iteration\":%u,\"frames\":%u,"
-                    "\"last_launch\":{\"samples\":%llu,\"primary\":%llu,\"shadow\":%llu,\"bounce\":%llu},\"camera\":%s}\n",
+                    "\"last_launch\":{\"samples\":%llu,\"primary\":%llu,\"shadow\":%llu,\"bounce\":%llu},\"camera\":%s%s}\n",
                     jstr(rs.scene().name).c_str(), jstr(mode_name(rs.mode())).c_str(), rs.width(), rs.height(),
                     rs.iteration(), frames, (unsigned long long)c.samples, (unsigned long long)c.primary,
-                    (unsigned long long)c.shadow, (unsigned long long)c.bounce, cam_json(rs.camera()).c_str());
+                    (unsigned long long)c.shadow, (unsigned long long)c.bounce, cam_json(rs.camera()).c_str(),
+                    noise_json.c_str());
         return 0;
     } catch (const Error& e) {
         std::fprintf(stderr, "rt_render: error %d: %s\n", e.code, e.what());

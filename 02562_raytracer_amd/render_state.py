@@ -47,6 +47,7 @@ class RenderState:
         self.max_iterations = 2   # Uniform::max_iterations, SetSamples (lib.rs:472-479)
         self.subdivision_level = 1   # Uniform.subdivision_level (uniform.rs:122-129)
         self.camera_controller = CameraController()
+        self.noise = None   # enable_noise(): the device buffer of rt_noise_state
         self.setup_rendering(scene)
 
     def _background(self, scene):
@@ -115,6 +116,11 @@ class RenderState:
         self.accum.zero()
         self.ids = self.ctx.alloc(npx * 4)
         self.iteration = 0
+        if self.noise is not None:
+            # the noise buffer follows the scene: a new one for a path mode, none otherwise
+            self.disable_noise()
+            if self.mode in F.NOISE_MODES:
+                self.enable_noise()
         self.update()
 
     def _load_model(self, model):
@@ -197,6 +203,69 @@ class RenderState:
     def reset_iteration(self):
         self.iteration = 0
         self.update()
+
+    # ---- the noise estimate (include/rt.h "noise estimate"; single process, no tiles)
+    def enable_noise(self):
+        """Keep the per-pixel running mean and variance of the iterations' luminance
+        (rt_set_noise_buffer) from iteration 0 on; reallocated by load_scene."""
+        if self.mode not in F.NOISE_MODES:
+            raise ValueError(f"{self.mode} writes no per-iteration records: the noise estimate follows "
+                             f"{', '.join(F.NOISE_MODES)}")
+        if self.iteration:
+            raise ValueError("enable_noise: the estimate starts at iteration 0 (reset_iteration() first)")
+        if self.noise is None:
+            self.noise = self.ctx.alloc(self.width * self.height * 8)
+            self.noise.zero()
+        self.ctx.set_noise_buffer(self.noise.ptr)
+
+    def disable_noise(self):
+        self.ctx.set_noise_buffer(None)
+        if self.noise is not None:
+            self.noise.free()   # (rt_device_free waits for the renders that wrote it)
+            self.noise = None
+
+    def _noise_or_raise(self):
+        if self.noise is None:
+            raise ValueError("no noise buffer: enable_noise() before the first iteration")
+        return self.noise.ptr
+
+    def noise_map(self, floor=1e-3):
+        """The relative standard error of every pixel's mean luminance after the
+        iterations rendered so far (at least 2): float32 [H, W], NaN where a sample was
+        not finite (rt_noise_map)."""
+        npx = self.width * self.height
+        out = self.ctx.alloc(npx * 4)
+        try:
+            self.ctx.noise_map(self._noise_or_raise(), npx, self.iteration, floor, out.ptr)
+            return out.to_numpy(np.float32, (self.height, self.width))
+        finally:
+            out.free()
+
+    def noise_summary(self, threshold, floor=1e-3):
+        """{pixels, above, nonfinite, max_rel_err} of the frame (rt_noise_summarize): above
+        counts the finite pixels whose relative standard error exceeds threshold."""
+        return self.ctx.noise_summary(self._noise_or_raise(), self.width * self.height, self.iteration, threshold,
+                                      floor)
+
+    def render_until(self, target, max_samples, batch=16, allow=0.0, floor=1e-3):
+        """Render `batch` iterations at a time (the last batch clipped to max_samples)
+        until at most allow x pixels lie above the relative standard error `target`, or
+        max_samples iterations are done.  Returns (iterations, summary); the summary is
+        None when fewer than 2 iterations were rendered."""
+        if not self.progressive:
+            raise ValueError("render_until needs progressive rendering (set_samples(.., True))")
+        if batch < 1:
+            raise ValueError("render_until: batch must be at least 1")
+        if self.noise is None:
+            self.enable_noise()
+        summary = None
+        while self.iteration < max_samples:
+            self.render(min(int(batch), int(max_samples) - self.iteration))
+            if self.iteration >= 2:
+                summary = self.noise_summary(target, floor)
+                if summary["above"] <= allow * summary["pixels"]:
+                    break
+        return self.iteration, summary
 
     def frame(self):
         """Linear accumulation [H, W, 4] float32 (the RenderDestination texture)."""

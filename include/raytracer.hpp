@@ -189,6 +189,24 @@ public:
      * calls it, then render()/step() in lockstep; frame()/hit_ids() are rank 0's. */
     void set_tiling(uint32_t nranks, uint32_t rank, const uint8_t comm_id[RT_COMM_ID_BYTES]);
 
+    /* The noise estimate of the path modes (rt.h "noise estimate"): from iteration 0 on, every
+     * render keeps each pixel's running mean and variance of the iterations' luminance
+     * (rt_set_noise_buffer; the buffer is reallocated by load_scene).  Throws for a mode that
+     * writes no per-iteration records, after iteration 0, and on a tiled state: after set_tiling
+     * (any rank count, 1 included) the renders index their outputs packed per tile, not as the
+     * width x height buffer this allocates, and a summary across ranks is out of scope.  The
+     * other noise calls throw on a tiled state too, and set_tiling throws once this is enabled. */
+    void enable_noise();
+    /* the relative standard error of every pixel after iteration() >= 2 iterations, H x W */
+    std::vector<float> noise_map(float floor = 1e-3f) const;
+    rt_noise_summary noise_summary(float threshold, float floor = 1e-3f) const;
+    /* Render `batch` iterations at a time (the last batch clipped to max_samples) until at
+     * most allow x pixels lie above the relative standard error `target` or max_samples
+     * iterations are done.  Returns the iteration count; *summary (if given) receives the last
+     * summary (zeroed when fewer than 2 iterations were rendered). */
+    uint32_t render_until(float target, uint32_t max_samples, uint32_t batch = 16, double allow = 0.0,
+                          float floor = 1e-3f, rt_noise_summary* summary = nullptr);
+
     std::vector<float> frame() const;        /* linear RGBA32F accumulation, H x W x 4 */
     std::vector<uint32_t> hit_ids() const;   /* primary-hit triangle ids, H x W */
     /* the sRGB surface frame, H x W x 4 (rt_frame_rgba8_mode: W1E2 and W1E3 without the pow) */
@@ -225,6 +243,7 @@ private:
     bool tiled_ = false;
     void* tile_accum_ = nullptr;       // this rank's packed tiles (rt_render_tiles)
     void* tile_ids_ = nullptr;
+    void* noise_ = nullptr;            // enable_noise: width x height rt_noise_state
 };
 
 }  // namespace raytracer

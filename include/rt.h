@@ -500,6 +500,67 @@ int rt_unpack_tiles(rt_ctx* ctx, uint32_t width, uint32_t height, uint32_t nrank
                     const float* packed_accum, const uint32_t* packed_ids,
                     float* frame_accum, uint32_t* frame_ids);
 
+/* ---- noise estimate of the path modes (DESIGN.md section 4 "Noise estimate") ----
+ * The seven path modes (W7E3, W9E1, W8E1..W8E3, W9E2, W9E3) write every iteration's
+ * radiance as a record before the fold averages them.  With a noise buffer set, their
+ * renders also keep, per output slot, the running mean and the sum of squared
+ * deviations (Welford) of the iterations' luminance -- no reference counterpart: the
+ * reference's sample count is a number the user guesses.  Pinned f32 arithmetic (no
+ * contraction, correctly rounded / and sqrt).  For the record x of iteration `it`
+ * (global index), in iteration order:
+ *     y = (0.2126f*x.x + 0.7152f*x.y) + 0.0722f*x.z     the raw result, not the max(., 0) average
+ *     n = (float)(it + 1)
+ *     d = y - mean;  mean = mean + d / n;  m2 = m2 + d * (y - mean)
+ * A pass with first_iter == 0 starts from {0, 0}; one with first_iter > 0 continues the
+ * stored state (the caller keeps the iterations contiguous, as for accum).  Non-finite
+ * samples propagate.  The state does not depend on how a render is split into launches,
+ * passes, work units or tiles.  The relative standard error of the mean after n >= 2
+ * iterations, with nf = (float)n and a floor > 0, is
+ *     rel = sqrtf((m2 < 0 ? 0 : m2) / (nf * (nf - 1.0f))) / max(|mean|, floor)
+ * A state with a non-finite field is "non-finite": its rel is the quiet NaN 0x7FC00000.
+ * Alignment: the kernels move a state as one 8-byte word and a record as one 16-byte word,
+ * so every state_dev pointer below must be 8-byte aligned and samples_rgba_dev 16-byte
+ * aligned (RT_E_INVALID otherwise).  rt_device_alloc's pointers are; a sub-buffer at an
+ * offset that is no multiple of 8 (16) bytes is not. */
+typedef struct rt_noise_state {
+    float mean, m2;
+} rt_noise_state;
+
+typedef struct rt_noise_summary {
+    uint64_t pixels;       /* npix */
+    uint64_t above;        /* finite pixels with rel > threshold (rel == threshold is not above) */
+    uint64_t nonfinite;    /* non-finite pixels */
+    float max_rel_err;     /* the largest rel of the finite pixels (0 when there is none) */
+    float reserved;        /* 0 */
+} rt_noise_summary;
+
+/* The DEVICE buffer the path modes' renders update: indexed exactly as accum_rgba32f
+ * (rt_render: region.w*region.h states, row-major over the region; rt_render_tiles:
+ * rt_tileset_local_tiles()*64 packed states, padding slots neither read nor written).
+ * It is updated after every fold, on the fold's stream (RT_OPT_ASYNC_FOLD: read it as
+ * accum is read).  NULL: off (the default; a render then issues the launches it issues
+ * without this call).  Every other mode leaves the buffer untouched, W7E1 and W7E2
+ * (which fold inside their kernel and write no records) included. */
+int rt_set_noise_buffer(rt_ctx* ctx, rt_noise_state* state_dev);
+
+/* The same kernel over caller-supplied DEVICE records (float4 each: rgb, w ignored) of
+ * iterations first_iter .. first_iter+spp-1 for npix pixels: [pixel][iteration] when
+ * pixel_major is non-zero, else [iteration][pixel] with stride npix.  npix == 0 or
+ * spp == 0: no-op.  Asynchronous on the context stream. */
+int rt_noise_accumulate(rt_ctx* ctx, const float* samples_rgba_dev, uint32_t npix, uint32_t spp,
+                        int pixel_major, uint32_t first_iter, rt_noise_state* state_dev);
+
+/* rel_dev[i] (DEVICE, npix floats) = rel of state_dev[i] after n iterations.  RT_E_INVALID
+ * for n < 2 or a floor that is not > 0.  Asynchronous on the context stream. */
+int rt_noise_map(rt_ctx* ctx, const rt_noise_state* state_dev, uint32_t npix, uint32_t n, float floor,
+                 float* rel_dev);
+
+/* The frame's summary into *out (host; synchronizes).  Deterministic: integer counts and
+ * an integer maximum of bit patterns, no float atomics.  RT_E_INVALID for n < 2, a floor
+ * that is not > 0 or a NaN threshold. */
+int rt_noise_summarize(rt_ctx* ctx, const rt_noise_state* state_dev, uint32_t npix, uint32_t n,
+                       float threshold, float floor, rt_noise_summary* out);
+
 /* ---- multi-GPU: the tile gather over RCCL -----------------
  * One process per GPU, each with its own context: every rank renders its
  * interleaved tiles (rt_render_tiles with rt_tileset {rank, nranks}), then
