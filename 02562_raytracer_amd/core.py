@@ -512,6 +512,28 @@ class Context:
         self._chk(F.lib().rt_last_elided_shadows(self._h, C.byref(n)))
         return n.value
 
+    def last_elided_primaries(self):
+        """Camera rays of the last render that RT_OPT_EMPTY_PIXELS did not cast
+        (rt_last_elided_primaries): its flagged pixels x its iterations."""
+        n = C.c_uint64()
+        self._chk(F.lib().rt_last_elided_primaries(self._h, C.byref(n)))
+        return n.value
+
+    def empty_pixels_in_use(self):
+        """(pixels flagged, build ms) of the empty-pixel mask the last render used
+        (rt_empty_pixels_in_use); 0 pixels when it used none."""
+        n = C.c_uint64()
+        ms = C.c_float()
+        self._chk(F.lib().rt_empty_pixels_in_use(self._h, C.byref(n), C.byref(ms)))
+        return n.value, ms.value
+
+    def download_empty_mask(self, width, height):
+        """The last render's empty-pixel mask as a (height, width) bool array
+        (rt_download_empty_mask); all False when it used none."""
+        words = np.zeros((width * height + 31) // 32, np.uint32)
+        self._chk(F.lib().rt_download_empty_mask(self._h, F.as_u32p(words), words.size))
+        return _mask_bits(words, width, height)
+
     def timer_start(self):
         self._chk(F.lib().rt_timer_start(self._h))
 
@@ -568,6 +590,26 @@ class Context:
         bad = C.c_uint32()
         self._chk(F.lib().rt_selftest_math(self._h, n, lo, hi, C.byref(bad)))
         return bad.value
+
+
+def _mask_bits(words, width, height):
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")[:width * height]
+    return bits.reshape(height, width).astype(bool)
+
+
+def empty_mask_host(mesh, uniform):
+    """The empty-pixel mask of RT_OPT_EMPTY_PIXELS computed on the host, no device
+    (rt_empty_mask_host): a (height, width) bool array, True = no camera ray of the
+    pixel can hit the mesh.  The device mask of the same mesh and uniforms is the same bits."""
+    V, _, I, _, _ = mesh.arrays()
+    V = np.ascontiguousarray(V, np.float32)
+    I = np.ascontiguousarray(I, np.uint32)
+    W, H = int(uniform.resolution[0]), int(uniform.resolution[1])
+    words = np.zeros((W * H + 31) // 32, np.uint32)
+    n = C.c_uint64()
+    F.check(F.lib().rt_empty_mask_host(F.as_f32p(V), V.shape[0], F.as_u32p(I), I.shape[0], C.byref(uniform),
+                                       F.as_u32p(words), C.byref(n)))
+    return _mask_bits(words, W, H)
 
 
 def load_texture_rgba8(path):

@@ -159,6 +159,25 @@ struct rt_ctx {
     // rt_set_noise_buffer: the path modes' renders update it after every fold (device, caller-owned)
     rt_noise_state* noise = nullptr;
     DevBuf noise_sum;   // rt_noise_summarize's 24-B result
+    // RT_OPT_EMPTY_PIXELS (ensure_empty; rt_empty.hip): the mask of empty_cam -- the camera
+    // terms and the resolution the iterations are counted for -- once empty_iters reaches
+    // kEmptyBuildIters; empty_tried: built or given up (over budget) for this camera.  The
+    // active list of one launch geometry (act_key) is cached beside it.
+    uint32_t empty_opt = 1;   // 0 off, 1 on, 2 on and built at the first render
+    float mesh_scale = 0.0f;  // the mesh's coordinate magnitude (the margin's absolute term)
+    float empty_cam[16] = {};
+    bool empty_has_cam = false, empty_valid = false, empty_tried = false;
+    uint64_t empty_iters = 0, empty_flagged = 0;
+    float empty_build_ms = 0.0f;
+    hipEvent_t empty_ev[2] = {nullptr, nullptr};
+    DevBuf empty_mask, empty_hit, empty_cnt, empty_big;
+    DevBuf act_list, act_flags, act_offs, act_scan;
+    uint32_t act_key[8] = {};
+    uint32_t act_n = 0, act_flagged = 0;
+    bool act_valid = false;
+    // the most recent render: did it use the mask, and the camera rays it did not cast
+    bool empty_used = false;
+    uint64_t elided_primaries = 0;
     ncclComm_t comm = nullptr;
     uint32_t comm_nranks = 0, comm_rank = 0;
     DevBuf gather_accum, gather_ids;   // rank 0: every rank's packed tiles, rank-major
@@ -325,6 +344,8 @@ void rt_destroy(rt_ctx* c)
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->auto_ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->empty_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->own) (void)hipStreamDestroy(c->own);
     delete c;
 }
@@ -394,6 +415,11 @@ int rt_set_option(rt_ctx* c, int option, int64_t value)
                 HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
         }
         c->async_fold = value != 0;
+        return RT_OK;
+    case RT_OPT_EMPTY_PIXELS:
+        if (value < 0 || value > 2)
+            return fail(c, RT_E_INVALID, "empty pixels must be 0 (off), 1 (on) or 2 (on, built at the first render)");
+        c->empty_opt = (uint32_t)value;
         return RT_OK;
     case RT_OPT_SAMPLE_BUDGET_MB:
         if (value < 1 || value > (1 << 20)) return fail(c, RT_E_INVALID, "sample budget must be in [1,2^20] MiB");
@@ -531,6 +557,14 @@ int rt_upload_mesh(rt_ctx* c, const float* pos_vec4, const float* nrm_vec4, uint
     c->nmats = nmats;
     c->nlights = (uint32_t)lights.size();
     c->has_mesh = true;
+    // (as rt_empty_mask_host: the finite coordinates' largest magnitude)
+    c->mesh_scale = 0.0f;
+    for (size_t v = 0; v < nverts; v++)
+        for (int a = 0; a < 3; a++) {
+            const float x = c->h_pos[4 * v + a];
+            if (x - x == 0.0f) c->mesh_scale = std::max(c->mesh_scale, x < 0 ? -x : x);
+        }
+    c->empty_has_cam = false;   // a new mesh: the empty-pixel mask starts over
     return RT_OK;
 }
 
@@ -544,6 +578,7 @@ static int repack_bsp(rt_ctx* c, uint32_t nnodes, uint32_t nids, size_t rec_off,
     c->hcam_valid = false;
     c->auto_cull = 0;   // (a new scene: RT_BSP_CULL_AUTO probes again)
     c->probe_n = 0;
+    c->empty_has_cam = false;   // (and the empty-pixel mask starts over)
     HIPCHK(c, c->bsp_nodes.alloc(total));
     DevBuf boxes;
     HIPCHK(c, boxes.alloc((size_t)nnodes * 64));
@@ -1264,6 +1299,129 @@ int rt_bsp_cull_in_use(rt_ctx* c, int* mode, float* probe_ms, uint32_t* probes)
 
 static const char* const kLaunchFailed = "kernel launch failed: ";
 
+// ---- RT_OPT_EMPTY_PIXELS (rt.h; DESIGN.md section 4 "Empty pixels") ----------
+// The mask pays once its build is below about 5 % of the iterations it serves: 96 of
+// them (measured on config 3, 0.86 ms against 96 x 0.19 ms: profiles/r09/ab_empty_pixels.txt).  Its work is capped at
+// 64 predicate evaluations per pixel of the frame on average; a camera whose triangles'
+// rectangles add up to more gets no mask (nothing is flagged).
+constexpr uint64_t kEmptyBuildIters = 96;
+constexpr uint64_t kEmptyBudgetPerPixel = 64;
+
+// Does the option cover this render?  (W9E1 on the BSP walk, both shaders; the constant
+// environment; a finite eye; no jitter table; no ray capture, which wants every ray.)
+static bool empty_applies(const rt_ctx* c, rt_mode mode, rt_traverse trav)
+{
+    if (!c->empty_opt || mode != RT_MODE_W9E1 || trav != RT_TRAVERSE_BSP) return false;
+    if (c->env_w || c->cap_rays || c->has_jitter || c->u.subdivision_level > 1u) return false;
+    const float* e = c->u.camera_pos;
+    return std::isfinite(e[0]) && std::isfinite(e[1]) && std::isfinite(e[2]);
+}
+
+// Count this render's iterations for its camera and build the camera's mask when they
+// reach the build count.  *use: the mask is valid for this render and flags something.
+static int ensure_empty(rt_ctx* c, const float cam14[14], uint32_t spp, bool* use)
+{
+    *use = false;
+    float key[16];
+    memcpy(key, cam14, 14 * sizeof(float));
+    memcpy(&key[14], &c->u.resolution[0], 4);
+    memcpy(&key[15], &c->u.resolution[1], 4);
+    if (!c->empty_has_cam || memcmp(key, c->empty_cam, sizeof key) != 0) {
+        memcpy(c->empty_cam, key, sizeof key);
+        c->empty_has_cam = true;
+        c->empty_valid = c->empty_tried = false;
+        c->empty_iters = 0;
+        c->act_valid = false;
+    }
+    c->empty_iters += spp;
+    if (!c->empty_tried && (c->empty_opt == 2 || c->empty_iters >= kEmptyBuildIters)) {
+        c->empty_tried = true;
+        // (a fold still pending on the fold stream reads the previous camera's mask)
+        if (c->fold_pending)
+            if (int r = set_dev(c)) return r;
+        const uint32_t W = c->u.resolution[0], H = c->u.resolution[1];
+        const size_t npix = (size_t)W * H;
+        HIPCHK(c, c->empty_cnt.ensure(16));
+        unsigned long long* area_d = c->empty_cnt.as<unsigned long long>();
+        uint32_t* flagged_d = c->empty_cnt.as<uint32_t>() + 2;
+        uint32_t* nbig_d = c->empty_cnt.as<uint32_t>() + 3;
+        HIPCHK(c, c->empty_big.ensure((size_t)std::max<uint32_t>(c->ntris, 1u) * 4));
+        if (rtk::launch_empty_area(c->pos.as<float4>(), c->idx.as<uint4>(), c->nverts, c->ntris, cam14, W, H,
+                                   c->mesh_scale, area_d, c->empty_big.as<uint32_t>(), nbig_d, c->stream))
+            return fail(c, RT_E_DEVICE, "empty-pixel mask: launch failed");
+        unsigned long long area = 0;
+        uint32_t nbig = 0;
+        HIPCHK(c, hipMemcpyAsync(&area, area_d, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&nbig, nbig_d, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (area <= kEmptyBudgetPerPixel * npix) {
+            HIPCHK(c, c->empty_hit.ensure(npix));
+            HIPCHK(c, c->empty_mask.ensure((npix + 31) / 32 * 4));
+            for (hipEvent_t& e : c->empty_ev)
+                if (!e) HIPCHK(c, hipEventCreate(&e));
+            HIPCHK(c, hipEventRecord(c->empty_ev[0], c->stream));
+            if (rtk::launch_empty_mask(c->pos.as<float4>(), c->idx.as<uint4>(), c->nverts, c->ntris, cam14, W, H,
+                                       c->mesh_scale, c->empty_big.as<uint32_t>(), std::min(nbig, c->ntris),
+                                       c->empty_hit.as<uint8_t>(), c->empty_mask.as<uint32_t>(), flagged_d, c->stream))
+                return fail(c, RT_E_DEVICE, "empty-pixel mask: launch failed");
+            HIPCHK(c, hipEventRecord(c->empty_ev[1], c->stream));
+            uint32_t flagged = 0;
+            HIPCHK(c, hipMemcpyAsync(&flagged, flagged_d, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipEventElapsedTime(&c->empty_build_ms, c->empty_ev[0], c->empty_ev[1]));
+            c->empty_flagged = flagged;
+            c->empty_valid = true;
+            c->act_valid = false;
+            // RT_BSP_CULL_AUTO: a probe under way timed launches that walked other samples
+            if (!c->auto_cull) c->probe_n = 0;
+        }
+    }
+    *use = c->empty_valid && c->empty_flagged > 0;
+    return RT_OK;
+}
+
+// the valid pixels of a launch's slots (rt_device_common.h map_pixel's tiles, clipped)
+static uint64_t launch_valid_pixels(const rtk::DevLaunch& L)
+{
+    if (!L.tileset) return (uint64_t)L.w * L.h;
+    const uint32_t W = L.u.resolution[0], H = L.u.resolution[1];
+    uint64_t n = 0;
+    for (uint32_t work = 0; work < L.nwork; work++) {
+        const uint64_t t = (uint64_t)work * L.nranks + L.rank;
+        if (t >= (uint64_t)L.tiles_x * L.tiles_y) continue;
+        const uint32_t ty = (uint32_t)(t / L.tiles_x);
+        uint32_t tx = (uint32_t)(t - (uint64_t)ty * L.tiles_x) + (L.tiles_x >= 8u ? (ty & 7u) : 0u);
+        tx = tx >= L.tiles_x ? tx - L.tiles_x : tx;
+        n += (uint64_t)std::min(8u, W - tx * 8u) * std::min(8u, H - ty * 8u);
+    }
+    return n;
+}
+
+// The active list of L's pixel slots under the valid mask: L.active and L.nactive,
+// cached per launch geometry.
+static int ensure_active(rt_ctx* c, rtk::DevLaunch& L)
+{
+    const uint32_t key[8] = {L.tileset, L.x0, L.y0, L.w, L.h, L.rank, L.nranks, L.nwork};
+    if (!c->act_valid || memcmp(key, c->act_key, sizeof key) != 0) {
+        const size_t nslots = (size_t)L.nwork * 64;
+        HIPCHK(c, c->act_list.ensure(nslots * 4));
+        HIPCHK(c, c->act_flags.ensure(nslots * 4));
+        HIPCHK(c, c->act_offs.ensure(nslots * 4));
+        HIPCHK(c, c->act_scan.ensure(rtk::scan_scratch_words((uint32_t)nslots) * 4));
+        uint32_t n = 0;
+        if (rtk::build_active_list(L, c->empty_mask.as<uint32_t>(), c->act_flags.as<uint32_t>(), c->act_offs.as<uint32_t>(),
+                                   c->act_scan.as<uint32_t>(), c->act_list.as<uint32_t>(), &n, c->stream))
+            return fail(c, RT_E_DEVICE, "empty-pixel active list: launch failed");
+        memcpy(c->act_key, key, sizeof key);
+        c->act_n = n;
+        c->act_flagged = (uint32_t)(launch_valid_pixels(L) - n);
+        c->act_valid = true;
+    }
+    L.active = c->act_list.as<uint32_t>();
+    L.nactive = c->act_n;
+    return RT_OK;
+}
+
 // the tree-walk kernel of (mode, trav)
 static int launch_walk(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_mode mode, rt_traverse trav)
 {
@@ -1286,7 +1444,8 @@ static int probe_launch(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch&
     HIPCHK(c, hipEventRecord(c->auto_ev[2 * slot], c->stream));
     if (int r = launch_walk(c, S, L, mode, trav)) return r;
     HIPCHK(c, hipEventRecord(c->auto_ev[2 * slot + 1], c->stream));
-    c->probe_samples[slot] = (uint64_t)L.stride * L.spp;
+    // (both kernels by the samples they walk: the active slots' under RT_OPT_EMPTY_PIXELS)
+    c->probe_samples[slot] = (uint64_t)(L.active ? L.nactive : L.stride) * L.spp;
     c->probe_n = (uint32_t)slot + 1;
     c->probe_launches++;
     return RT_OK;
@@ -1375,9 +1534,10 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
     const bool sil = has_silhouette(c, mode, trav);
     S.bsp_cull_mode = cull_in_use(c, sil);
     L.shade_threshold = default_threshold(c, mode, trav, S.bsp_cull_mode);
-    L.reserved0 = 0;
     L.counters = c->counters.as<unsigned long long>();
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, 32 * sizeof(unsigned long long), c->stream));
+    c->empty_used = false;
+    c->elided_primaries = 0;
     if (L.nwork == 0 || (L.spp == 0 && (path || direct_prog))) {
         if (counts) return rt_last_counts(c, counts);
         return RT_OK;
@@ -1386,6 +1546,21 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
         // passes of pass_spp iterations: k_path writes per-iteration samples,
         // k_fold applies the progressive average in order
         L.stride = L.tileset ? L.nwork * 64u : L.w * L.h;
+        // RT_OPT_EMPTY_PIXELS: k_path deals the active slots only, and k_fold / k_noise
+        // take the constant for the flagged pixels; with no active slot k_path is not
+        // launched at all (a persistent kernel is never started on an empty queue)
+        bool ep = false;
+        if (empty_applies(c, mode, trav)) {
+            if (int r = ensure_empty(c, L.cam, L.spp, &ep)) return r;
+            if (ep)
+                if (int r = ensure_active(c, L)) return r;
+            if (ep) {
+                c->empty_used = true;
+                c->elided_primaries = (uint64_t)c->act_flagged * L.spp;
+            }
+        }
+        const bool nothing_active = ep && L.nactive == 0;
+        const uint32_t* emask = ep ? c->empty_mask.as<uint32_t>() : nullptr;
         const uint64_t per_it = (uint64_t)L.stride * sizeof(float4);
         const uint64_t budget = c->sample_budget_mb << 20;
         uint32_t pass_spp = (uint32_t)std::min<uint64_t>(L.spp, std::max<uint64_t>(1, budget / per_it));
@@ -1395,7 +1570,7 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
         if (async && c->samples2.n < need) HIPCHK(c, c->samples2.alloc(need));
         L.samples = c->samples.as<float4>();
         // (a counting render, RT_OPT_DETAIL_COUNTERS, runs other kernels: it never probes)
-        const bool autop = sil && c->bsp_cull == RT_BSP_CULL_AUTO && c->hcam_valid && !c->detail;
+        const bool autop = sil && c->bsp_cull == RT_BSP_CULL_AUTO && c->hcam_valid && !c->detail && !nothing_active;
         if (autop)
             if (int r = probe_begin(c)) return r;
         if (async) {   // the folds follow the context stream's work up to here
@@ -1429,23 +1604,25 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
                 L.samples = (b ? c->samples2 : c->samples).as<float4>();
                 HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_free[b], 0));
                 HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
-                if (int r = probe_launch(c, S, L, mode, trav, slot)) return r;
+                if (!nothing_active)
+                    if (int r = probe_launch(c, S, L, mode, trav, slot)) return r;
                 HIPCHK(c, hipEventRecord(c->ev_path, c->stream));
                 HIPCHK(c, hipStreamWaitEvent(c->fold_stream, c->ev_path, 0));
-                const int r = rtk::launch_fold(L, c->fold_stream);
+                const int r = rtk::launch_fold(L, emask, c->fold_stream);
                 if (r) return fail(c, r, std::string("fold launch failed: ") + hipGetErrorString(hipGetLastError()));
                 // (before ev_free[b]: the scratch buffer is not reused under it)
-                if (c->noise && rtk::launch_noise(L, c->noise, c->fold_stream))
+                if (c->noise && rtk::launch_noise(L, emask, c->noise, c->fold_stream))
                     return fail(c, RT_E_DEVICE, std::string("noise launch failed: ") + hipGetErrorString(hipGetLastError()));
                 HIPCHK(c, hipEventRecord(c->ev_free[b], c->fold_stream));
                 c->fold_pending = true;
                 continue;
             }
             HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
-            if (int r = probe_launch(c, S, L, mode, trav, slot)) return r;
-            const int r = rtk::launch_fold(L, c->stream);
+            if (!nothing_active)
+                if (int r = probe_launch(c, S, L, mode, trav, slot)) return r;
+            const int r = rtk::launch_fold(L, emask, c->stream);
             if (r) return fail(c, r, std::string("fold launch failed: ") + hipGetErrorString(hipGetLastError()));
-            if (c->noise && rtk::launch_noise(L, c->noise, c->stream))
+            if (c->noise && rtk::launch_noise(L, emask, c->noise, c->stream))
                 return fail(c, RT_E_DEVICE, std::string("noise launch failed: ") + hipGetErrorString(hipGetLastError()));
         }
     } else if (analytic) {
@@ -1582,7 +1759,7 @@ int rt_noise_accumulate(rt_ctx* c, const float* samples, uint32_t npix, uint32_t
     L.unit_order = pixel_major ? 1u : 0u;
     L.stride = npix;
     L.samples = reinterpret_cast<float4*>(const_cast<float*>(samples));   // (read only)
-    if (rtk::launch_noise(L, state, c->stream))
+    if (rtk::launch_noise(L, nullptr, state, c->stream))
         return fail(c, RT_E_DEVICE, std::string("rt_noise_accumulate: launch failed: ") +
                                         hipGetErrorString(hipGetLastError()));
     return RT_OK;
@@ -1881,6 +2058,9 @@ int rt_last_counts(rt_ctx* c, rt_ray_counts* counts)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     uint64_t* dst = reinterpret_cast<uint64_t*>(counts);
     for (size_t i = 0; i < sizeof(rt_ray_counts) / sizeof(uint64_t); i++) dst[i] = h[i];
+    // the camera rays RT_OPT_EMPTY_PIXELS did not cast are rays the reference's shader casts
+    counts->samples += c->elided_primaries;
+    counts->primary += c->elided_primaries;
     c->last = *counts;
     return RT_OK;
 }
@@ -1896,6 +2076,34 @@ int rt_last_elided_shadows(rt_ctx* c, uint64_t* elided)
                              sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *elided = h;
+    return RT_OK;
+}
+
+int rt_last_elided_primaries(rt_ctx* c, uint64_t* elided)
+{
+    if (!c || !elided) return RT_E_INVALID;
+    *elided = c->elided_primaries;
+    return RT_OK;
+}
+
+int rt_empty_pixels_in_use(rt_ctx* c, uint64_t* pixels_flagged, float* build_ms)
+{
+    if (!c) return RT_E_INVALID;
+    if (pixels_flagged) *pixels_flagged = c->empty_used ? c->empty_flagged : 0;
+    if (build_ms) *build_ms = c->empty_build_ms;
+    return RT_OK;
+}
+
+int rt_download_empty_mask(rt_ctx* c, uint32_t* mask_words, uint64_t nwords)
+{
+    if (!c || !mask_words) return RT_E_INVALID;
+    memset(mask_words, 0, (size_t)nwords * 4);
+    if (!c->empty_used) return RT_OK;
+    if (int r = set_dev(c)) return r;
+    const uint64_t have = ((uint64_t)c->u.resolution[0] * c->u.resolution[1] + 31) / 32;
+    HIPCHK(c, hipMemcpyAsync(mask_words, c->empty_mask.p, (size_t)std::min(have, nwords) * 4, hipMemcpyDeviceToHost,
+                             c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return RT_OK;
 }
 

@@ -153,6 +153,52 @@ __device__ __forceinline__ uint32_t fetch_work(uint32_t* ctr, uint32_t lane)
     if (lane == 0) v = atomicAdd(ctr, 1u);
     return __shfl(v, 0, 64);
 }
+// ------------------------------------------------------------------ records of flagged pixels
+// RT_OPT_EMPTY_PIXELS: k_path writes no record for a pixel whose bit is set in
+// the launch's empty mask (no camera ray of it can hit the mesh, rt_empty.h).  k_fold and k_noise
+// read every record through path_record: the stored one, or for a flagged pixel what
+// each of its iterations would have stored -- W9E1's miss with the constant
+// environment, result = vec3(0) + env * factor with factor = vec3(1), primary id none.
+typedef float rec4 __attribute__((ext_vector_type(4)));
+// is output slot o of the launch (p: its pixel in tileset mode) a flagged pixel?
+__device__ __forceinline__ bool out_flagged(const DevLaunch& L, const uint32_t* empty_mask, uint32_t o, const Pix& p)
+{
+    if (!empty_mask) return false;
+    uint32_t x = p.x, y = p.y;
+    if (L.tileset == 0) {
+        const uint32_t ry = o / L.w;
+        x = L.x0 + (o - ry * L.w);
+        y = L.y0 + ry;
+    }
+    const uint32_t i = y * L.u.resolution[0] + x;
+    return (empty_mask[i >> 5] >> (i & 31u)) & 1u;
+}
+__device__ __forceinline__ rec4 empty_record(const DevLaunch& L)
+{
+    const f3 r = add(V(0, 0, 0), mul(V(L.env[0], L.env[1], L.env[2]), V(1, 1, 1)));
+    const rec4 c = {r.x, r.y, r.z, __uint_as_float(0xFFFFFFFFu)};
+    return c;
+}
+// N consecutive records at p (one branch around all N loads, so that an unflagged
+// pixel's loads are issued together as before)
+template <int N>
+__device__ __forceinline__ void path_records(bool flagged, const rec4 cst, const rec4* p, rec4 (&q)[N])
+{
+    if (flagged) {
+#pragma unroll
+        for (int k = 0; k < N; k++) q[k] = cst;
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) q[k] = p[k];
+    }
+}
+template <bool STREAM = false>
+__device__ __forceinline__ rec4 path_record(bool flagged, const rec4 cst, const rec4* p)
+{
+    if (flagged) return cst;
+    return STREAM ? __builtin_nontemporal_load(p) : *p;
+}
+
 __device__ __forceinline__ void pixel_uv(const rt_uniform& u, uint32_t x, uint32_t y, float& ux, float& uy)
 {
     ux = ((float)x + 0.5f) / (float)u.resolution[0] - 0.5f;

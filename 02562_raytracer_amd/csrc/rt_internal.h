@@ -91,7 +91,9 @@ struct DevLaunch {
     uint32_t nwork;               // work items (tiles) in this launch
     uint32_t first_iter, spp;     // this pass: iterations first_iter .. first_iter+spp-1
     uint32_t shade_threshold;     // k_path: shade when <= this many lanes still trace
-    uint32_t reserved0;           // (was the retired trip-half postponement; kept for the argument layout)
+    // RT_OPT_EMPTY_PIXELS: the entries of `active` (in the slot of the retired trip-half
+    // postponement: no new field -- the kernel-argument block of every kernel keeps its size)
+    uint32_t nactive;
     // k_path work units: (chunk of `chunk` iterations, pixel slot), chunk-major;
     // per-iteration radiance + primary id go to samples[(it - first_iter) * stride + out]
     // and k_fold applies the progressive average in order (w7e3.wgsl:261-271)
@@ -103,7 +105,13 @@ struct DevLaunch {
     uint32_t* ids;
     uint32_t* work_counter;       // zeroed before launch
     unsigned long long* counters; // 32 x u64, zeroed before launch (rt_ray_counts order)
-    uint32_t* bvh_deep;           // BVH stack entries beyond the LDS share: (50 - K) x grid lanes
+    union {
+        uint32_t* bvh_deep;       // BVH walk: stack entries beyond the LDS share, (50 - K) x grid lanes
+        // BSP walk of W9E1 (RT_OPT_EMPTY_PIXELS, rt_empty.hip): the launch's pixel slots that
+        // are valid and not flagged empty, ascending, nactive of them; null: k_path deals
+        // every slot of the launch
+        const uint32_t* active;
+    };
     // ray capture (rt_set_ray_capture; the counting instantiation only): every ray
     // the path kernel's walks trace, appended as {o.xyz, w.xyz, tmin, tmax} + flags
     // (bit 0 any-hit); cap_count counts them all, cap_max bounds what is written
@@ -196,12 +204,14 @@ int launch_trace_batch(const DevScene& s, const float* rays, const uint32_t* fla
                        uint32_t* work, uint32_t threshold, int num_cus, hipStream_t stream);
 
 // Progressive average of one pass's per-iteration samples into accum/ids (after k_path).
-int launch_fold(const DevLaunch& l, hipStream_t stream);
+// empty_mask (RT_OPT_EMPTY_PIXELS): one bit per full-frame pixel, bit y * width + x set = no
+// camera ray of the pixel can hit the mesh and k_path wrote no records for it, or null
+int launch_fold(const DevLaunch& l, const uint32_t* empty_mask, hipStream_t stream);
 
 // The noise estimate (rt_noise.hip; rt.h "noise estimate").  launch_noise: the luminance of the
 // same pass's records into state's running mean and m2, slot for slot as k_fold addresses
 // accum (after launch_fold, on its stream; l.first_iter == 0 starts from {0, 0}).
-int launch_noise(const DevLaunch& l, rt_noise_state* state, hipStream_t stream);
+int launch_noise(const DevLaunch& l, const uint32_t* empty_mask, rt_noise_state* state, hipStream_t stream);
 // rel[i] = the relative standard error of state[i] after n iterations (0x7FC00000: non-finite state)
 int launch_noise_map(const rt_noise_state* state, uint32_t npix, uint32_t n, float floor, float* rel,
                      hipStream_t stream);
@@ -266,6 +276,25 @@ int radix_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uin
 size_t radix_hist_words(uint32_t n);
 
 int launch_selftest_math(const float* in, float* out, uint32_t n, hipStream_t stream);
+
+// RT_OPT_EMPTY_PIXELS (rt_empty.hip, rt_empty.h).  cam14: camera_basis's terms.
+// launch_empty_area: *area (device u64, zeroed here) = the predicate evaluations the mask
+// of this camera costs (the sum of the triangles' pixel rectangles): the build's budget.
+// big (device, ntris words) / *nbig (device u32, zeroed here): the triangles whose rectangle
+// is large, which launch_empty_mask spreads over several blocks each
+int launch_empty_area(const float4* pos, const uint4* idx, uint32_t nverts, uint32_t ntris, const float cam14[14],
+                      uint32_t W, uint32_t H, float scale, unsigned long long* area, uint32_t* big, uint32_t* nbig,
+                      hipStream_t stream);
+// hit: W x H bytes of scratch; mask: ceil(W H / 32) words, bit y * W + x set = empty;
+// *flagged (device u32, zeroed here) = the set bits
+int launch_empty_mask(const float4* pos, const uint4* idx, uint32_t nverts, uint32_t ntris, const float cam14[14],
+                      uint32_t W, uint32_t H, float scale, const uint32_t* big, uint32_t nbig, uint8_t* hit,
+                      uint32_t* mask, uint32_t* flagged, hipStream_t stream);
+// the active list of l's pixel slots under the mask: flags and offs hold l.nwork * 64
+// words each, scan: scan_scratch_words(l.nwork * 64); active: l.nwork * 64 words;
+// *nactive (host) is read back, which synchronises the stream
+int build_active_list(const DevLaunch& l, const uint32_t* empty_mask, uint32_t* flags, uint32_t* offs, uint32_t* scan, uint32_t* active,
+                      uint32_t* nactive, hipStream_t stream);
 
 // get_camera_ray's basis from the uniforms (host, same f32 operations as the shader)
 void camera_basis(const rt_uniform& u, float cam[14]);

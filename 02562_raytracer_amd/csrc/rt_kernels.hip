@@ -1388,6 +1388,9 @@ k_path(DevScene S, DevLaunch L)
     // form, trav_step's VSH, served until they were elided: a W9E1 shadow ray that
     // still walks -- a non-finite material -- takes the general form.)
     constexpr bool ELIDE = W9;
+    // RT_OPT_EMPTY_PIXELS: W9E1's BSP walk deals no work unit for a pixel that no camera
+    // ray can leave with a hit (the refill's active list; rt_empty.hip)
+    constexpr bool EMPTYPX = REDRAW && TRAV == RT_TRAVERSE_BSP;
     const float ETA = W9 ? 0.0001f : 0.01f;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t T = L.shade_threshold;
@@ -1550,7 +1553,9 @@ k_path(DevScene S, DevLaunch L)
         const uint32_t light_tris = S.nlights - 1u;
         const uint32_t sel = W9 ? L.u.selection1 : 0u;
         const uint32_t it_end = L.first_iter + L.spp;
-        const uint32_t pslots = L.nwork * 64u;            // pixel slots
+        // pixel slots: all of the launch's, or (RT_OPT_EMPTY_PIXELS, W9E1's BSP walk) the
+        // active list's -- the slots whose pixel is not flagged empty
+        const uint32_t pslots = (EMPTYPX && L.active) ? L.nactive : L.nwork * 64u;
         const uint32_t nslots = pslots * L.nchunks;       // work units (host keeps this < 2^31)
         const f3 env = V(L.env[0], L.env[1], L.env[2]);
         // ---- shading phase
@@ -1874,13 +1879,21 @@ k_path(DevScene S, DevLaunch L)
                     // pixels at the same iteration; pixel-major (1): the iterations
                     // of one pixel side by side
                     uint32_t ch, ps;
-                    const uint32_t psl = sopaque(L.nwork) * 64u, nch = sopaque(L.nchunks);
+                    uint32_t psl = sopaque(L.nwork) * 64u;
+                    const uint32_t nch = sopaque(L.nchunks);
+                    if constexpr (EMPTYPX) {
+                        if (L.active) psl = sopaque(L.nactive);
+                    }
                     if (L.unit_order == 0u) {
                         ch = slot / psl;
                         ps = slot - ch * psl;
                     } else {
                         ps = slot / nch;
                         ch = slot - ps * nch;
+                    }
+                    // the ps-th active slot's pixel (ps < nactive: slot < nslots)
+                    if constexpr (EMPTYPX) {
+                        if (L.active) ps = L.active[ps];
                     }
                     const Pix p = map_pixel(L, ps >> 6, ps & 63u);
                     if (p.valid) {
@@ -1926,11 +1939,16 @@ k_path(DevScene S, DevLaunch L)
 // as [pixel][iteration], so k_path's 16-B records land in whole lines and a
 // thread here streams its own pixel's records.  ids = primary hit of the last
 // iteration.
-__global__ void __launch_bounds__(256) k_fold(DevLaunch L)
+__global__ void __launch_bounds__(256) k_fold(DevLaunch L, const uint32_t* empty_mask)
 {
     const uint32_t nout = L.tileset ? L.nwork * 64u : L.w * L.h;
     for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < nout; o += gridDim.x * blockDim.x) {
-        if (L.tileset && !map_pixel(L, o >> 6, o & 63u).valid) continue;
+        Pix px{0, 0, 0, true};
+        if (L.tileset) px = map_pixel(L, o >> 6, o & 63u);
+        if (!px.valid) continue;
+        // a flagged pixel (RT_OPT_EMPTY_PIXELS) has no records: the same average over the constant
+        const bool fl = out_flagged(L, empty_mask, o, px);
+        const v4f cst = empty_record(L);
         float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f;
         if (L.first_iter > 0u) {
             const float4 pa = L.accum[o];
@@ -1957,21 +1975,20 @@ __global__ void __launch_bounds__(256) k_fold(DevLaunch L)
 #endif
             for (; i + RT_FOLD_BATCH <= L.spp; i += RT_FOLD_BATCH) {
                 v4f q[RT_FOLD_BATCH];
-#pragma unroll
-                for (int k = 0; k < RT_FOLD_BATCH; k++) q[k] = sp[i + k];
+                path_records(fl, cst, sp + i, q);
 #pragma unroll
                 for (int k = 0; k < RT_FOLD_BATCH; k++) fold1(q[k], i + k);
                 r = q[RT_FOLD_BATCH - 1];
             }
             for (; i < L.spp; i++) {
-                r = sp[i];
+                r = path_record(fl, cst, sp + i);
                 fold1(r, i);
             }
         } else {
             // [iteration][pixel]: a wave reads 1 KiB contiguous per iteration
             const v4f* sp = reinterpret_cast<const v4f*>(L.samples + o);
             for (; i < L.spp; i++) {
-                r = __builtin_nontemporal_load(sp + (size_t)i * L.stride);
+                r = path_record<true>(fl, cst, sp + (size_t)i * L.stride);
                 fold1(r, i);
             }
         }
@@ -2757,13 +2774,13 @@ int launch_trace_batch(const DevScene& s, const float* rays, const uint32_t* fla
     return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
 }
 
-int launch_fold(const DevLaunch& l, hipStream_t stream)
+int launch_fold(const DevLaunch& l, const uint32_t* empty_mask, hipStream_t stream)
 {
     const uint64_t nout = l.tileset ? (uint64_t)l.nwork * 64u : (uint64_t)l.w * l.h;
     uint64_t blocks = (nout + 255) / 256;
     if (blocks > 16384) blocks = 16384;
     if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(k_fold, dim3((uint32_t)blocks), dim3(256), 0, stream, l);
+    hipLaunchKernelGGL(k_fold, dim3((uint32_t)blocks), dim3(256), 0, stream, l, empty_mask);
     return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
 }
 

@@ -35,11 +35,16 @@ __device__ __forceinline__ void noise1(float& mean, float& m2, const v4f x, uint
 // are 1 KiB contiguous per wave and iteration.  The records are not read again after
 // this kernel, the state is: streaming loads for the chunk-major layout as in k_fold.
 // spp x 16 B read and 8 B written per pixel (8 B more read when first_iter > 0).
-__global__ void __launch_bounds__(256) k_noise(DevLaunch L, rt_noise_state* __restrict__ state)
+__global__ void __launch_bounds__(256) k_noise(DevLaunch L, const uint32_t* empty_mask, rt_noise_state* __restrict__ state)
 {
     const uint32_t nout = L.tileset ? L.nwork * 64u : L.w * L.h;
     for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < nout; o += gridDim.x * blockDim.x) {
-        if (L.tileset && !map_pixel(L, o >> 6, o & 63u).valid) continue;
+        Pix px{0, 0, 0, true};
+        if (L.tileset) px = map_pixel(L, o >> 6, o & 63u);
+        if (!px.valid) continue;
+        // a flagged pixel (RT_OPT_EMPTY_PIXELS) has no records: the constant, as in k_fold
+        const bool fl = out_flagged(L, empty_mask, o, px);
+        const v4f cst = empty_record(L);
         v2f* const st = reinterpret_cast<v2f*>(state + o);
         float mean = 0.0f, m2 = 0.0f;
         if (L.first_iter > 0u) {
@@ -52,16 +57,15 @@ __global__ void __launch_bounds__(256) k_noise(DevLaunch L, rt_noise_state* __re
             const v4f* sp = reinterpret_cast<const v4f*>(L.samples + (size_t)o * L.spp);
             for (; i + 8u <= L.spp; i += 8u) {
                 v4f q[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) q[k] = sp[i + k];
+                path_records(fl, cst, sp + i, q);
 #pragma unroll
                 for (int k = 0; k < 8; k++) noise1(mean, m2, q[k], L.first_iter + i + k);
             }
-            for (; i < L.spp; i++) noise1(mean, m2, sp[i], L.first_iter + i);
+            for (; i < L.spp; i++) noise1(mean, m2, path_record(fl, cst, sp + i), L.first_iter + i);
         } else {
             const v4f* sp = reinterpret_cast<const v4f*>(L.samples + o);
             for (; i < L.spp; i++)
-                noise1(mean, m2, __builtin_nontemporal_load(sp + (size_t)i * L.stride), L.first_iter + i);
+                noise1(mean, m2, path_record<true>(fl, cst, sp + (size_t)i * L.stride), L.first_iter + i);
         }
         const v2f s = {mean, m2};
         *st = s;
@@ -134,11 +138,11 @@ static uint32_t stream_blocks(uint64_t n, uint64_t cap)
     return (uint32_t)(b > cap ? cap : b ? b : 1);
 }
 
-int launch_noise(const DevLaunch& l, rt_noise_state* state, hipStream_t stream)
+int launch_noise(const DevLaunch& l, const uint32_t* empty_mask, rt_noise_state* state, hipStream_t stream)
 {
     // k_fold's grid (launch_fold): the two kernels stream the same records
     const uint64_t nout = l.tileset ? (uint64_t)l.nwork * 64u : (uint64_t)l.w * l.h;
-    hipLaunchKernelGGL(k_noise, dim3(stream_blocks(nout, 16384)), dim3(256), 0, stream, l, state);
+    hipLaunchKernelGGL(k_noise, dim3(stream_blocks(nout, 16384)), dim3(256), 0, stream, l, empty_mask, state);
     return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
 }
 

@@ -252,6 +252,20 @@ typedef struct rt_ray_counts {
                                      kernel must be 5 % faster to be chosen), until the BSP or this option changes
                                      or the eye's reach (farthest distance to the scene box) leaves [1/2, 2] of the
                                      reach the probe ran at.  rt_bsp_cull_in_use reports the choice */
+#define RT_OPT_EMPTY_PIXELS   11  /* 1 (default) / 0: W9E1 on the BSP walk, with the constant environment (no
+                                     rt_set_environment_map), a finite eye, no jitter table and no ray capture,
+                                     casts no camera ray for a pixel that PROVABLY misses the mesh at every
+                                     iteration: per camera, one bit per pixel says that intersect_triangle can accept
+                                     no triangle for any direction of the pixel's footprint (grown by a whole pixel),
+                                     by the certified margin of RT_BSP_CULL_CERTIFIED bounded over that footprint
+                                     (DESIGN.md section 4 "Empty pixels").  Such a pixel's iterations all store
+                                     vec3(0) + env * vec3(1) with primary id none; the fold and the noise estimate
+                                     take that constant instead of reading records, so accum, ids, the noise state
+                                     and rt_ray_counts (primary = the rays the reference's shader casts) are the
+                                     same bits as with 0.  The mask is built once the iterations rendered with an
+                                     unchanged camera, the call's own included, reach 96 (a 256-spp call builds it
+                                     at once, a camera that moves every 1-spp frame never does), and dropped when
+                                     the uniforms, the mesh or the BSP change.  rt_empty_pixels_in_use reports it */
 
 /* ---- device / context (replaces src/gpu_handles.rs) -------------------- */
 
@@ -283,6 +297,23 @@ int rt_set_option(rt_ctx* ctx, int option, int64_t value);
  * probes (2 uint32, or NULL): the probes this context has started and their launches. */
 int rt_bsp_cull_in_use(rt_ctx* ctx, int* mode, float* probe_ms, uint32_t* probes);
 
+/* RT_OPT_EMPTY_PIXELS: the mask the most recent render used.  pixels_flagged (or NULL):
+ * the full-frame pixels flagged empty, 0 when that render used no mask (the option off,
+ * a mode or setting the option does not cover, too few iterations yet).  build_ms (or
+ * NULL): what the last mask build took on the device in milliseconds (0 until one ran). */
+int rt_empty_pixels_in_use(rt_ctx* ctx, uint64_t* pixels_flagged, float* build_ms);
+
+/* The same mask on the host, without a device: bit y * width + x of mask_words
+ * (ceil(width * height / 32) words) is set when pixel (x, y) of the uniforms' camera is
+ * empty for the mesh (nverts x float4 positions, ntris x (v0, v1, v2, material)).  The
+ * device mask of a context with this mesh and these uniforms is the same bits.
+ * *flagged (or NULL): the set bits.  A degenerate camera, a non-finite eye or
+ * subdivision_level > 1 flag nothing. */
+int rt_empty_mask_host(const float* pos_vec4, uint32_t nverts, const uint32_t* idx_vec4, uint32_t ntris,
+                       const rt_uniform* u, uint32_t* mask_words, uint64_t* flagged);
+/* The device mask of the most recent render into mask_words (host), all zero when it used
+ * none (synchronizes). */
+int rt_download_empty_mask(rt_ctx* ctx, uint32_t* mask_words, uint64_t nwords);
 /* Message describing the last failure on this context (or the last
  * context-less failure when ctx == NULL).  Never NULL. */
 const char* rt_last_error(const rt_ctx* ctx);
@@ -546,7 +577,10 @@ int rt_set_noise_buffer(rt_ctx* ctx, rt_noise_state* state_dev);
 /* The same kernel over caller-supplied DEVICE records (float4 each: rgb, w ignored) of
  * iterations first_iter .. first_iter+spp-1 for npix pixels: [pixel][iteration] when
  * pixel_major is non-zero, else [iteration][pixel] with stride npix.  npix == 0 or
- * spp == 0: no-op.  Asynchronous on the context stream. */
+ * spp == 0: no-op.  Asynchronous on the context stream.  It reads every record it is
+ * given: the renders' own scratch holds no records for the pixels RT_OPT_EMPTY_PIXELS
+ * flags (their fold and noise update take the constant), so a caller that feeds records
+ * of its own supplies them for every pixel. */
 int rt_noise_accumulate(rt_ctx* ctx, const float* samples_rgba_dev, uint32_t npix, uint32_t spp,
                         int pixel_major, uint32_t first_iter, rt_noise_state* state_dev);
 
@@ -654,6 +688,12 @@ int rt_last_counts(rt_ctx* ctx, rt_ray_counts* counts);
  * mesh (less the rays the W9 plane stopped).  Filled by the counting instantiation
  * only: 0 when RT_OPT_DETAIL_COUNTERS is off. */
 int rt_last_elided_shadows(rt_ctx* ctx, uint64_t* elided);
+
+/* Camera rays of the most recent render that RT_OPT_EMPTY_PIXELS did not cast: its
+ * flagged pixels x its iterations.  They stay counted in rt_ray_counts.primary and
+ * .samples (the rays the reference's shader casts), so primary - elided is what walked
+ * the mesh.  Host arithmetic: filled with or without RT_OPT_DETAIL_COUNTERS. */
+int rt_last_elided_primaries(rt_ctx* ctx, uint64_t* elided);
 
 /* Device-vs-host self check of the pinned f32 math (sqrt, division, the
  * rt_detmath.h transcendentals) over n inputs in [lo, hi]; returns the number
