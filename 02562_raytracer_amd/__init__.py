@@ -11,7 +11,7 @@ The package directory name starts with a digit; import it with
 from . import _ffi
 from ._ffi import MODES, TRAVERSALS, RtError, lib
 from .core import (BspTree, Bvh, Context, DeviceBuffer, Mesh, empty_mask_host, load_texture_rgba8, local_tiles,
-                   make_uniform)
+                   make_uniform, pixel_depth_host)
 from .render_state import ASSETS, RenderState
 from .camera import CameraController
 from .scenes import Camera, SceneDescriptor, find_scene, get_scenes

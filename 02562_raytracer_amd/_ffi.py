@@ -38,6 +38,7 @@ RT_OPT_UNIT_ORDER = 6
 RT_OPT_BSP_CULL = 9
 RT_OPT_ASYNC_FOLD = 10
 RT_OPT_EMPTY_PIXELS = 11   # 0 off, 1 on (default), 2 on and built at the first render
+RT_OPT_PIXEL_DEPTH = 12    # 0 off, 1 on (default): camera rays start on their pixel's certified depth range
 RT_BSP_CULL_OFF, RT_BSP_CULL_CERTIFIED, RT_BSP_CULL_FAST, RT_BSP_CULL_SILHOUETTE, RT_BSP_CULL_AUTO = range(5)
 BSP_TREELET_BYTES = 96   # rt_internal.h: the BSP walk's treelet (rt_download_bsp_treelets)
 RT_OPT_KERNEL_TIMING = 7
@@ -220,6 +221,8 @@ SIGNATURES = {
     "rt_empty_mask_host": (C.c_int, [f32p, C.c_uint32, u32p, C.c_uint32, C.POINTER(Uniform), u32p,
                                      C.POINTER(C.c_uint64)]),
     "rt_download_empty_mask": (C.c_int, [vp, u32p, C.c_uint64]),
+    "rt_pixel_depth_host": (C.c_int, [f32p, C.c_uint32, u32p, C.c_uint32, C.POINTER(Uniform), f32p, f32p]),
+    "rt_last_pixel_depth": (C.c_int, [vp, f32p, f32p, C.c_uint64, C.POINTER(C.c_int)]),
     "rt_selftest_math": (C.c_int, [vp, C.c_uint32, C.c_float, C.c_float, u32p]),
     "rt_mesh_load_obj": (C.c_int, [C.c_char_p, C.POINTER(vp)]),
     "rt_mesh_from_arrays": (C.c_int, [f32p, f32p, C.c_uint32, u32p, C.c_uint32, C.POINTER(Material), C.c_uint32,

@@ -534,6 +534,16 @@ class Context:
         self._chk(F.lib().rt_download_empty_mask(self._h, F.as_u32p(words), words.size))
         return _mask_bits(words, width, height)
 
+    def last_pixel_depth(self, width, height):
+        """(near, far, in use) of the pixel depth ranges the last render's camera rays
+        started on (rt_last_pixel_depth): two (height, width) float32 arrays; near 0 and
+        far +inf everywhere, and in use False, when it used none."""
+        near = np.empty(width * height, np.float32)
+        far = np.empty(width * height, np.float32)
+        used = C.c_int()
+        self._chk(F.lib().rt_last_pixel_depth(self._h, F.as_f32p(near), F.as_f32p(far), near.size, C.byref(used)))
+        return near.reshape(height, width), far.reshape(height, width), bool(used.value)
+
     def timer_start(self):
         self._chk(F.lib().rt_timer_start(self._h))
 
@@ -610,6 +620,22 @@ def empty_mask_host(mesh, uniform):
     F.check(F.lib().rt_empty_mask_host(F.as_f32p(V), V.shape[0], F.as_u32p(I), I.shape[0], C.byref(uniform),
                                        F.as_u32p(words), C.byref(n)))
     return _mask_bits(words, W, H)
+
+
+def pixel_depth_host(mesh, uniform):
+    """The per-pixel depth ranges of RT_OPT_PIXEL_DEPTH computed on the host, no device
+    (rt_pixel_depth_host): (near, far), two (height, width) float32 arrays that bound,
+    strictly, every distance a camera ray of the pixel can be accepted with; near +inf and
+    far 0 for a pixel empty_mask_host flags.  The device arrays are the same bits."""
+    V, _, I, _, _ = mesh.arrays()
+    V = np.ascontiguousarray(V, np.float32)
+    I = np.ascontiguousarray(I, np.uint32)
+    W, H = int(uniform.resolution[0]), int(uniform.resolution[1])
+    near = np.empty(W * H, np.float32)
+    far = np.empty(W * H, np.float32)
+    F.check(F.lib().rt_pixel_depth_host(F.as_f32p(V), V.shape[0], F.as_u32p(I), I.shape[0], C.byref(uniform),
+                                        F.as_f32p(near), F.as_f32p(far)))
+    return near.reshape(H, W), far.reshape(H, W)
 
 
 def load_texture_rgba8(path):

@@ -171,6 +171,10 @@ struct rt_ctx {
     float empty_build_ms = 0.0f;
     hipEvent_t empty_ev[2] = {nullptr, nullptr};
     DevBuf empty_mask, empty_hit, empty_cnt, empty_big;
+    // RT_OPT_PIXEL_DEPTH: the camera's per-pixel {near, far}, built with the mask and
+    // living and dying with it; depth_used: the most recent render's k_path read it
+    DevBuf empty_depth;
+    bool depth_opt = true, depth_used = false;
     DevBuf act_list, act_flags, act_offs, act_scan;
     uint32_t act_key[8] = {};
     uint32_t act_n = 0, act_flagged = 0;
@@ -420,6 +424,10 @@ int rt_set_option(rt_ctx* c, int option, int64_t value)
         if (value < 0 || value > 2)
             return fail(c, RT_E_INVALID, "empty pixels must be 0 (off), 1 (on) or 2 (on, built at the first render)");
         c->empty_opt = (uint32_t)value;
+        return RT_OK;
+    case RT_OPT_PIXEL_DEPTH:
+        if (value < 0 || value > 1) return fail(c, RT_E_INVALID, "pixel depth must be 0 (off) or 1 (on)");
+        c->depth_opt = value != 0;
         return RT_OK;
     case RT_OPT_SAMPLE_BUDGET_MB:
         if (value < 1 || value > (1 << 20)) return fail(c, RT_E_INVALID, "sample budget must be in [1,2^20] MiB");
@@ -1357,12 +1365,14 @@ static int ensure_empty(rt_ctx* c, const float cam14[14], uint32_t spp, bool* us
         if (area <= kEmptyBudgetPerPixel * npix) {
             HIPCHK(c, c->empty_hit.ensure(npix));
             HIPCHK(c, c->empty_mask.ensure((npix + 31) / 32 * 4));
+            HIPCHK(c, c->empty_depth.ensure(npix * sizeof(uint2)));
             for (hipEvent_t& e : c->empty_ev)
                 if (!e) HIPCHK(c, hipEventCreate(&e));
             HIPCHK(c, hipEventRecord(c->empty_ev[0], c->stream));
             if (rtk::launch_empty_mask(c->pos.as<float4>(), c->idx.as<uint4>(), c->nverts, c->ntris, cam14, W, H,
                                        c->mesh_scale, c->empty_big.as<uint32_t>(), std::min(nbig, c->ntris),
-                                       c->empty_hit.as<uint8_t>(), c->empty_mask.as<uint32_t>(), flagged_d, c->stream))
+                                       c->empty_hit.as<uint8_t>(), c->empty_mask.as<uint32_t>(), flagged_d,
+                                       c->empty_depth.as<uint2>(), c->stream))
                 return fail(c, RT_E_DEVICE, "empty-pixel mask: launch failed");
             HIPCHK(c, hipEventRecord(c->empty_ev[1], c->stream));
             uint32_t flagged = 0;
@@ -1536,7 +1546,7 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
     L.shade_threshold = default_threshold(c, mode, trav, S.bsp_cull_mode);
     L.counters = c->counters.as<unsigned long long>();
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, 32 * sizeof(unsigned long long), c->stream));
-    c->empty_used = false;
+    c->empty_used = c->depth_used = false;
     c->elided_primaries = 0;
     if (L.nwork == 0 || (L.spp == 0 && (path || direct_prog))) {
         if (counts) return rt_last_counts(c, counts);
@@ -1550,6 +1560,7 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
         // take the constant for the flagged pixels; with no active slot k_path is not
         // launched at all (a persistent kernel is never started on an empty queue)
         bool ep = false;
+        L.pix_depth = nullptr;   // (the jitter table's slot, which k_path never reads: rt_internal.h)
         if (empty_applies(c, mode, trav)) {
             if (int r = ensure_empty(c, L.cam, L.spp, &ep)) return r;
             if (ep)
@@ -1557,6 +1568,10 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
             if (ep) {
                 c->empty_used = true;
                 c->elided_primaries = (uint64_t)c->act_flagged * L.spp;
+                // RT_OPT_PIXEL_DEPTH: the active pixels' camera rays start on their certified range
+                // (a form of culling: RT_BSP_CULL_OFF keeps the reference's interval and node sequence)
+                c->depth_used = c->depth_opt && c->bsp_cull != RT_BSP_CULL_OFF;
+                if (c->depth_used) L.pix_depth = c->empty_depth.as<float2>();
             }
         }
         const bool nothing_active = ep && L.nactive == 0;
@@ -2104,6 +2119,27 @@ int rt_download_empty_mask(rt_ctx* c, uint32_t* mask_words, uint64_t nwords)
     HIPCHK(c, hipMemcpyAsync(mask_words, c->empty_mask.p, (size_t)std::min(have, nwords) * 4, hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
+int rt_last_pixel_depth(rt_ctx* c, float* near_out, float* far_out, uint64_t npix, int* in_use)
+{
+    if (!c || !near_out || !far_out) return RT_E_INVALID;
+    if (in_use) *in_use = c->depth_used ? 1 : 0;
+    for (uint64_t i = 0; i < npix; i++) {
+        near_out[i] = 0.0f;
+        far_out[i] = INFINITY;
+    }
+    if (!c->depth_used) return RT_OK;
+    if (int r = set_dev(c)) return r;
+    const uint64_t have = std::min<uint64_t>((uint64_t)c->u.resolution[0] * c->u.resolution[1], npix);
+    std::vector<float> pairs((size_t)have * 2);
+    HIPCHK(c, hipMemcpyAsync(pairs.data(), c->empty_depth.p, pairs.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint64_t i = 0; i < have; i++) {
+        near_out[i] = pairs[2 * i];
+        far_out[i] = pairs[2 * i + 1];
+    }
     return RT_OK;
 }
 

@@ -3,6 +3,8 @@
 // A pixel is EMPTY when no triangle of the mesh can be accepted by intersect_triangle
 // (w9e1.wgsl, f32) for any camera ray of that pixel, on any interval: the reference's
 // walk then returns no hit whatever path it takes (DESIGN.md section 4 "Empty pixels").
+// For the pairs it cannot exclude the same evaluation bounds the accepted distance
+// (pair_depth: RT_OPT_PIXEL_DEPTH, DESIGN.md section 4 "Pixel depth ranges").
 //
 // Everything here is f64 with +, -, *, /, fabs, min and max only (no sqrt, no
 // contraction: the build's -ffp-contract=off), so the host and the device compute the
@@ -229,8 +231,17 @@ RT_EMPTY_HD void tri_rect(const Cam& cam, const Tri& t, int32_t& x0, int32_t& x1
 // May some camera ray of pixel (x, y) accept the triangle?  false is a proof that none
 // can: the grown footprint's cone misses the triangle's box grown by the margin's upper
 // bound over the footprint, separated by one of the cone's four side planes.
-RT_EMPTY_HD bool may_hit(const Cam& cam, const Tri& t, uint32_t x, uint32_t y)
+//
+// depth (or null), when the answer is true: depth[0] < dist < depth[1] for every dist the
+// pair can be accepted with (RT_OPT_PIXEL_DEPTH, DESIGN.md section 4 "Pixel depth
+// ranges"; pair_depth below); the whole interval [0, +inf] where the pair is not bounded.
+RT_EMPTY_HD void pair_depth(const Cam& cam, const Tri& t, const double qc[3], const double r[3], double m, double depth[2]);
+RT_EMPTY_HD bool may_hit(const Cam& cam, const Tri& t, uint32_t x, uint32_t y, double* depth = nullptr)
 {
+    if (depth) {
+        depth[0] = 0.0;
+        depth[1] = __builtin_huge_val();
+    }
     if (t.kind != 1) return t.kind == 2;
     const double ux = ((double)x + 0.5) * cam.invW - 0.5, uy = 0.5 - ((double)y + 0.5) * cam.invH;
     const double s0 = ux - cam.pad, s1 = ux + cam.invH + cam.pad;
@@ -274,7 +285,96 @@ RT_EMPTY_HD bool may_hit(const Cam& cam, const Tri& t, uint32_t x, uint32_t y)
         for (int a = 0; a < 3; a++) far += sg * n[a] * t.c[a] + ab(n[a]) * (t.h[a] + m);
         if (far < 0.0) return false;   // the whole grown box lies outside this plane
     }
+    if (depth) pair_depth(cam, t, qc, r, m, depth);
     return true;
+}
+
+// lo <= sqrt(x) <= hi for a finite x >= 0, in +, -, *, / only (the header's discipline:
+// the same bits on the host and on the device).  Heron's iteration from above on x scaled
+// by a power of 4 into [1/4, 4): every iterate is >= sqrt (AM-GM) up to its own rounding,
+// which the 2^-48 covers, and x / hi is then a lower bound.  Six steps from (1 + z) / 2
+// converge to the last bits; fewer would still be bounds.
+RT_EMPTY_HD void sqrt_bounds(double x, double& lo, double& hi)
+{
+    lo = hi = 0.0;
+    if (!(x > 0.0)) return;
+    double z = x, s = 1.0;
+    for (int k = 0; k < 540 && z >= 4.0; k++) {
+        z *= 0.25;
+        s *= 2.0;
+    }
+    for (int k = 0; k < 540 && z < 0.25; k++) {
+        z *= 4.0;
+        s *= 0.5;
+    }
+    double y = 0.5 * (1.0 + z);
+    for (int k = 0; k < 6; k++) y = 0.5 * (y + z / y);
+    hi = y * s * (1.0 + 0x1p-48);
+    lo = x / hi * (1.0 - 0x1p-48);
+}
+
+// The distance range of one (triangle, pixel) pair that may_hit does not exclude.  Every
+// accepted hit point x = dist w (relative to the eye) lies in the triangle's box grown by
+// the pair's margin m, and w = q / |q|2 (1 +- 1e-6) per component with q in qc +- r.  So
+//   dist |w|2 = |x|2 lies between the eye's distance to the grown box and to its farthest
+//   corner, and |w|2 is within [DN, UP];
+//   on an axis where q does not straddle zero, dist = x_a / w_a with both ranges known.
+// The intersection of the four ranges, every step rounded outward, widened by 2^-19 (the
+// f32 rounding of the result and of dist itself sit far inside it): strict bounds.
+RT_EMPTY_HD void pair_depth(const Cam& cam, const Tri& t, const double qc[3], const double r[3], double m, double depth[2])
+{
+    const double up = 1.0 + 0x1p-40, dn = 1.0 - 0x1p-40;
+    double q2lo = 0.0, q2hi = 0.0, d2lo = 0.0, d2hi = 0.0, xl[3], xh[3];
+    for (int a = 0; a < 3; a++) {
+        const double ql = mx(ab(qc[a]) - r[a], 0.0), qh = ab(qc[a]) + r[a];
+        q2lo += ql * ql;
+        q2hi += qh * qh;
+        const double H = (t.h[a] + m + cam.scene * 0x1p-40) * up;   // (and the roundings of c)
+        xl[a] = t.c[a] - H;
+        xh[a] = t.c[a] + H;
+        const double dl = mx(ab(t.c[a]) - H, 0.0), dh = ab(t.c[a]) + H;
+        d2lo += dl * dl;
+        d2hi += dh * dh;
+    }
+    if (!fin(q2hi) || !fin(d2hi) || !(q2lo > 0.0)) return;
+    double nlo, nhi, blo, bhi, tmp;
+    sqrt_bounds(q2lo * dn, nlo, tmp);   // |q|2 within [nlo, nhi]
+    sqrt_bounds(q2hi * up, tmp, nhi);
+    sqrt_bounds(d2lo * dn, blo, tmp);   // |x|2 within [blo, bhi]
+    sqrt_bounds(d2hi * up, tmp, bhi);
+    if (!(nlo > 0.0) || !fin(nhi) || !fin(bhi)) return;
+    double lo = blo / UP * dn, hi = bhi / DN * up;
+    for (int a = 0; a < 3; a++) {
+        // the axis with its sign folded away: q_a in [ql, qh], x_a in [al, ah], ql > 0
+        double ql = qc[a] - r[a], qh = qc[a] + r[a], al = xl[a], ah = xh[a];
+        if (qh < 0.0) {
+            const double q0 = ql, a0 = al;
+            ql = -qh;
+            qh = -q0;
+            al = -ah;
+            ah = -a0;
+        }
+        if (!(ql > 0.0) || !(ah > 0.0)) continue;   // (ah <= 0: no dist > 0 reaches the box; any range is a bound)
+        const double wl = ql / nhi * DN * dn, wh = qh / nlo * UP * up;
+        if (!(wl > 0.0) || !fin(wh)) continue;
+        hi = mn(hi, ah / wl * up);
+        if (al > 0.0) lo = mx(lo, al / wh * dn);
+    }
+    lo *= 1.0 - 0x1p-19;
+    hi *= 1.0 + 0x1p-19;
+    if (!(lo >= 0x1p-100)) lo = 0.0;   // (no denormal f32: the device may flush it)
+    if (hi != hi) return;
+    if (!(hi >= 0x1p-100)) hi = 0x1p-100;
+    depth[0] = lo;
+    depth[1] = hi;   // (+inf when it overflows: still a bound)
+}
+
+// the f32 a pair's bounds are stored and folded as: near rounded to nearest inside its
+// 2^-19 of slack, far too; positive floats, which order as their unsigned bit patterns
+RT_EMPTY_HD void depth_f32(const double depth[2], float& nearf, float& farf)
+{
+    nearf = (float)depth[0];
+    farf = depth[1] < 3.0e38 ? (float)depth[1] : __builtin_huge_valf();
 }
 
 }  // namespace rtempty

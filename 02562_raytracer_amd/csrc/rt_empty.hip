@@ -7,6 +7,8 @@
 // and inside that rectangle the per-pixel predicate (may_hit) decides with the pixel's
 // own directions.  A pixel no triangle marks is empty.  Both steps are the shared f64
 // core of rt_empty.h, so rt_empty_mask_host computes the same bits without a device.
+// The same pass folds every marking pair's distance range into a {near, far} per pixel
+// (RT_OPT_PIXEL_DEPTH; rt_pixel_depth_host is its host form).
 #include <vector>
 
 #include "rt_device_common.h"
@@ -64,11 +66,33 @@ __global__ void __launch_bounds__(256) k_empty_area(const float4* pos, const uin
     if ((threadIdx.x & 63u) == 0 && a) atomicAdd(area, a);
 }
 
+// One pair of the mark kernels.  depth[y * W + x] = {near, far} as f32 bit patterns
+// (RT_OPT_PIXEL_DEPTH): the pair's range is folded in with an unsigned min and max, which
+// order positive floats as floats; {+inf, 0} (k_depth_init) is the pixel no pair marks.
+__device__ __forceinline__ void mark_pixel(const rtempty::Cam& cam, const rtempty::Tri& t, uint32_t x, uint32_t y,
+                                           uint8_t* hit, uint2* depth)
+{
+    double d[2];
+    if (!rtempty::may_hit(cam, t, x, y, d)) return;
+    const size_t i = (size_t)y * cam.W + x;
+    hit[i] = 1;
+    float nf, ff;
+    rtempty::depth_f32(d, nf, ff);
+    atomicMin(&depth[i].x, __float_as_uint(nf));
+    atomicMax(&depth[i].y, __float_as_uint(ff));
+}
+
+__global__ void __launch_bounds__(256) k_depth_init(uint2* depth, uint32_t npix)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < npix) depth[i] = make_uint2(0x7F800000u, 0u);
+}
+
 // one block per triangle: thread 0 sets the triangle up, the block walks its rectangle.
 // hit[y * W + x] = 1: some camera ray of the pixel may accept a triangle.  (Plain byte
 // stores of the same value from many blocks: the order does not matter.)
 __global__ void __launch_bounds__(256) k_empty_mark(const float4* pos, const uint4* idx, uint32_t nverts, uint32_t ntris,
-                                                    rtempty::Cam cam, uint8_t* hit)
+                                                    rtempty::Cam cam, uint8_t* hit, uint2* depth)
 {
     __shared__ TriRect sh;
     for (uint32_t k = blockIdx.x; k < ntris; k += gridDim.x) {
@@ -83,14 +107,15 @@ __global__ void __launch_bounds__(256) k_empty_mark(const float4* pos, const uin
         for (unsigned long long i = threadIdx.x; i < n; i += blockDim.x) {
             const uint32_t ry = (uint32_t)(i / rw), rx = (uint32_t)(i - (unsigned long long)ry * rw);
             const uint32_t x = (uint32_t)x0 + rx, y = (uint32_t)y0 + ry;   // < W, < H (tri_rect clamps)
-            if (x < cam.W && y < cam.H && rtempty::may_hit(cam, sh.t, x, y)) hit[(size_t)y * cam.W + x] = 1;
+            if (x < cam.W && y < cam.H) mark_pixel(cam, sh.t, x, y, hit, depth);
         }
     }
 }
 
 // the same for the triangles of the big list: blockIdx.x = list entry, blockIdx.y = its share
 __global__ void __launch_bounds__(256) k_empty_mark_big(const float4* pos, const uint4* idx, uint32_t nverts,
-                                                        const uint32_t* big, rtempty::Cam cam, uint8_t* hit)
+                                                        const uint32_t* big, rtempty::Cam cam, uint8_t* hit,
+                                                        uint2* depth)
 {
     __shared__ TriRect sh;
     if (threadIdx.x == 0) sh = tri_setup(cam, pos, idx, nverts, big[blockIdx.x]);
@@ -103,7 +128,7 @@ __global__ void __launch_bounds__(256) k_empty_mark_big(const float4* pos, const
          i += (unsigned long long)gridDim.y * blockDim.x) {
         const uint32_t ry = (uint32_t)(i / rw), rx = (uint32_t)(i - (unsigned long long)ry * rw);
         const uint32_t x = (uint32_t)x0 + rx, y = (uint32_t)y0 + ry;
-        if (x < cam.W && y < cam.H && rtempty::may_hit(cam, sh.t, x, y)) hit[(size_t)y * cam.W + x] = 1;
+        if (x < cam.W && y < cam.H) mark_pixel(cam, sh.t, x, y, hit, depth);
     }
 }
 
@@ -168,17 +193,19 @@ int launch_empty_area(const float4* pos, const uint4* idx, uint32_t nverts, uint
 
 int launch_empty_mask(const float4* pos, const uint4* idx, uint32_t nverts, uint32_t ntris, const float cam14[14],
                       uint32_t W, uint32_t H, float scale, const uint32_t* big, uint32_t nbig, uint8_t* hit,
-                      uint32_t* mask, uint32_t* flagged, hipStream_t stream)
+                      uint32_t* mask, uint32_t* flagged, uint2* depth, hipStream_t stream)
 {
     const uint32_t npix = W * H;
     if (hipMemsetAsync(hit, 0, npix, stream) != hipSuccess) return RT_E_DEVICE;
+    hipLaunchKernelGGL(k_depth_init, dim3((npix + 255u) / 256u), dim3(256), 0, stream, depth, npix);
     if (hipMemsetAsync(flagged, 0, 4, stream) != hipSuccess) return RT_E_DEVICE;
     const rtempty::Cam cam = cam_of(cam14, W, H, scale);
     if (ntris)
         hipLaunchKernelGGL(k_empty_mark, dim3(std::min<uint32_t>(ntris, 1u << 20)), dim3(256), 0, stream, pos, idx, nverts,
-                           ntris, cam, hit);
+                           ntris, cam, hit, depth);
     if (nbig)   // (nbig <= ntris < 2^31, the grid's x limit)
-        hipLaunchKernelGGL(k_empty_mark_big, dim3(nbig, kBigSplit), dim3(256), 0, stream, pos, idx, nverts, big, cam, hit);
+        hipLaunchKernelGGL(k_empty_mark_big, dim3(nbig, kBigSplit), dim3(256), 0, stream, pos, idx, nverts, big, cam, hit,
+                           depth);
     const uint32_t nwords = (npix + 31u) / 32u;
     hipLaunchKernelGGL(k_empty_pack, dim3((nwords + 255u) / 256u), dim3(256), 0, stream, hit, npix, mask, flagged);
     return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
@@ -205,7 +232,25 @@ int build_active_list(const DevLaunch& l, const uint32_t* empty_mask, uint32_t* 
 
 }  // namespace rtk
 
-// ---- the host entry point (rt.h): the same core on the host mesh, no device
+// ---- the host entry points (rt.h): the same core on the host mesh, no device
+// the camera of the uniforms as the context forms it (the scale: the finite coordinates'
+// largest magnitude); false: a degenerate camera or a non-finite eye, no mask
+static bool host_cam(const float* pos_vec4, uint32_t nverts, const rt_uniform& u, rtempty::Cam& cam)
+{
+    float scale = 0.0f;
+    for (size_t v = 0; v < nverts; v++)
+        for (int a = 0; a < 3; a++) {
+            const float x = pos_vec4[4 * v + a];
+            if (x - x == 0.0f) scale = std::max(scale, x < 0 ? -x : x);
+        }
+    float cam14[14];
+    rtk::camera_basis(u, cam14);
+    cam = rtempty::make_cam(cam14, u.resolution[0], u.resolution[1], (double)scale);
+    bool eye_ok = cam.ok != 0;
+    for (int a = 0; a < 3; a++) eye_ok = eye_ok && rtempty::fin(cam.o[a]);
+    return eye_ok;
+}
+
 extern "C" int rt_empty_mask_host(const float* pos_vec4, uint32_t nverts, const uint32_t* idx_vec4, uint32_t ntris,
                                   const rt_uniform* u, uint32_t* mask_words, uint64_t* flagged)
 {
@@ -215,17 +260,8 @@ extern "C" int rt_empty_mask_host(const float* pos_vec4, uint32_t nverts, const 
     const size_t npix = (size_t)W * H, nwords = (npix + 31) / 32;
     for (size_t w = 0; w < nwords; w++) mask_words[w] = 0;
     if (flagged) *flagged = 0;
-    float scale = 0.0f;
-    for (size_t v = 0; v < nverts; v++)
-        for (int a = 0; a < 3; a++) {
-            const float x = pos_vec4[4 * v + a];
-            if (x - x == 0.0f) scale = std::max(scale, x < 0 ? -x : x);
-        }
-    float cam14[14];
-    rtk::camera_basis(*u, cam14);
-    const rtempty::Cam cam = rtempty::make_cam(cam14, W, H, (double)scale);
-    bool eye_ok = cam.ok != 0;
-    for (int a = 0; a < 3; a++) eye_ok = eye_ok && rtempty::fin(cam.o[a]);
+    rtempty::Cam cam;
+    const bool eye_ok = host_cam(pos_vec4, nverts, *u, cam);
     if (!eye_ok || u->subdivision_level > 1u) return RT_OK;   // no mask: nothing flagged
     std::vector<uint8_t> hit(npix, 0);
     const float4* pos = reinterpret_cast<const float4*>(pos_vec4);
@@ -243,5 +279,44 @@ extern "C" int rt_empty_mask_host(const float* pos_vec4, uint32_t nverts, const 
             n++;
         }
     if (flagged) *flagged = n;
+    return RT_OK;
+}
+
+// RT_OPT_PIXEL_DEPTH on the host: every pair's range folded as the mark kernels fold it
+extern "C" int rt_pixel_depth_host(const float* pos_vec4, uint32_t nverts, const uint32_t* idx_vec4, uint32_t ntris,
+                                   const rt_uniform* u, float* near_out, float* far_out)
+{
+    if (!pos_vec4 || !idx_vec4 || !u || !near_out || !far_out) return RT_E_INVALID;
+    const uint32_t W = u->resolution[0], H = u->resolution[1];
+    if (W == 0 || H == 0 || W >= 65536u || H >= 65536u) return RT_E_INVALID;
+    const size_t npix = (size_t)W * H;
+    rtempty::Cam cam;
+    const bool eye_ok = host_cam(pos_vec4, nverts, *u, cam);
+    if (!eye_ok || u->subdivision_level > 1u) {   // no mask: nothing flagged, nothing bounded
+        for (size_t i = 0; i < npix; i++) {
+            near_out[i] = 0.0f;
+            far_out[i] = __builtin_huge_valf();
+        }
+        return RT_OK;
+    }
+    for (size_t i = 0; i < npix; i++) {
+        near_out[i] = __builtin_huge_valf();
+        far_out[i] = 0.0f;
+    }
+    const float4* pos = reinterpret_cast<const float4*>(pos_vec4);
+    const uint4* idx = reinterpret_cast<const uint4*>(idx_vec4);
+    for (uint32_t k = 0; k < ntris; k++) {
+        const rtk::TriRect r = rtk::tri_setup(cam, pos, idx, nverts, k);
+        for (int32_t y = r.y0; y <= r.y1 && r.x0 <= r.x1; y++)
+            for (int32_t x = r.x0; x <= r.x1; x++) {
+                double d[2];
+                if (!rtempty::may_hit(cam, r.t, (uint32_t)x, (uint32_t)y, d)) continue;
+                float nf, ff;
+                rtempty::depth_f32(d, nf, ff);
+                const size_t i = (size_t)y * W + x;
+                near_out[i] = std::min(near_out[i], nf);   // (never NaN, never negative)
+                far_out[i] = std::max(far_out[i], ff);
+            }
+    }
     return RT_OK;
 }

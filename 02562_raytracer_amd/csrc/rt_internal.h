@@ -77,7 +77,16 @@ struct DevScene {
 struct DevLaunch {
     rt_uniform u;
     float cam[14];                // camera basis e, v, b1, b2, d, aspect (get_camera_ray, w7e3.wgsl:211-228)
-    const float* jitter;          // subdiv^2 float2 (device), may be null when subdiv == 1
+    union {
+        // subdiv^2 float2 (device), may be null when subdiv == 1.  The kernels that take their
+        // samples from the table read it (k_primary, k_direct, the flat modes); k_path draws its
+        // own jitter and never does, so the path renders lend it the slot:
+        const float* jitter;
+        // RT_OPT_PIXEL_DEPTH (the path renders: set or nulled by every one of them): per
+        // full-frame pixel y * width + x the certified {near, far} of its camera rays' accepted
+        // hits, or null (rt_empty.hip); W9E1's BSP walk starts a camera ray on that interval
+        const float2* pix_depth;
+    };
     float env[3];
     const uint32_t* env_tex;      // RGBA8 equirectangular hdri0, or null for the constant env
     uint32_t env_w, env_h;
@@ -286,10 +295,11 @@ int launch_empty_area(const float4* pos, const uint4* idx, uint32_t nverts, uint
                       uint32_t W, uint32_t H, float scale, unsigned long long* area, uint32_t* big, uint32_t* nbig,
                       hipStream_t stream);
 // hit: W x H bytes of scratch; mask: ceil(W H / 32) words, bit y * W + x set = empty;
-// *flagged (device u32, zeroed here) = the set bits
+// *flagged (device u32, zeroed here) = the set bits; depth: W x H {near, far} f32 bit
+// patterns (RT_OPT_PIXEL_DEPTH), {+inf, 0} for a pixel no triangle marks
 int launch_empty_mask(const float4* pos, const uint4* idx, uint32_t nverts, uint32_t ntris, const float cam14[14],
                       uint32_t W, uint32_t H, float scale, const uint32_t* big, uint32_t nbig, uint8_t* hit,
-                      uint32_t* mask, uint32_t* flagged, hipStream_t stream);
+                      uint32_t* mask, uint32_t* flagged, uint2* depth, hipStream_t stream);
 // the active list of l's pixel slots under the mask: flags and offs hold l.nwork * 64
 // words each, scan: scan_scratch_words(l.nwork * 64); active: l.nwork * 64 words;
 // *nactive (host) is read back, which synchronises the stream

@@ -1436,7 +1436,20 @@ k_path(DevScene S, DevLaunch L)
         prim = 0xFFFFFFFFu;
         shadow = false;
         inv = trav_inv<TRAV>(rd);
-        trav_start<TRAV>(tr, stk, ETA, ray_tmax<MODE>(ro, rd, ETA));
+        // RT_OPT_PIXEL_DEPTH: every distance a camera ray of this pixel can be accepted with
+        // lies strictly inside the pixel's (near, far) (rt_empty.h pair_depth), so the walk on
+        // that interval visits a subsequence of the reference walk's leaves and returns its
+        // hit.  One load, the same address for the lanes a pixel-major refill hands a pixel;
+        // the capture and the counters keep the reference's ray.
+        float t0 = ETA, t1 = ray_tmax<MODE>(ro, rd, ETA);
+        if constexpr (EMPTYPX) {
+            if (L.pix_depth) {
+                const float2 nf = L.pix_depth[py * u.resolution[0] + px];
+                t0 = fmaxf(t0, nf.x);
+                t1 = fminf(t1, nf.y);
+            }
+        }
+        trav_start<TRAV>(tr, stk, t0, t1);
         capture_ray<COUNT>(L, ro, rd, ETA, ray_tmax<MODE>(ro, rd, ETA), false);
         st = ST_TRACE;
         ao = false;

@@ -266,6 +266,15 @@ typedef struct rt_ray_counts {
                                      unchanged camera, the call's own included, reach 96 (a 256-spp call builds it
                                      at once, a camera that moves every 1-spp frame never does), and dropped when
                                      the uniforms, the mesh or the BSP change.  rt_empty_pixels_in_use reports it */
+#define RT_OPT_PIXEL_DEPTH    12  /* 1 (default) / 0: whenever a render uses the mask of RT_OPT_EMPTY_PIXELS, the camera
+                                     rays of its pixels start their BSP walk on the pixel's certified depth range
+                                     instead of [1e-4, tmax]: with the mask, and by the same margin, the build folds
+                                     for every pixel a near and a far such that every distance intersect_triangle can
+                                     accept for any camera ray of the pixel lies strictly between them.  The walk on
+                                     that interval visits a subsequence of the reference walk's leaves and returns its
+                                     hit (DESIGN.md section 4 "Pixel depth ranges"): accum, ids, the noise state and
+                                     rt_ray_counts are the same bits as with 0.  Bounce rays are untouched, and with
+                                     RT_BSP_CULL_OFF the walk keeps the reference's interval */
 
 /* ---- device / context (replaces src/gpu_handles.rs) -------------------- */
 
@@ -314,6 +323,17 @@ int rt_empty_mask_host(const float* pos_vec4, uint32_t nverts, const uint32_t* i
 /* The device mask of the most recent render into mask_words (host), all zero when it used
  * none (synchronizes). */
 int rt_download_empty_mask(rt_ctx* ctx, uint32_t* mask_words, uint64_t nwords);
+/* RT_OPT_PIXEL_DEPTH on the host, without a device (the sibling of rt_empty_mask_host, same
+ * inputs): near_out / far_out [y * width + x] bound every distance that intersect_triangle
+ * can accept for a camera ray of pixel (x, y), strictly.  A pixel rt_empty_mask_host flags
+ * has near = +inf and far = 0; a pixel a non-finite triangle marks, and every pixel where
+ * that entry point flags nothing for want of a mask, has near = 0 and far = +inf.  The
+ * device arrays of a context with this mesh and these uniforms are the same bits. */
+int rt_pixel_depth_host(const float* pos_vec4, uint32_t nverts, const uint32_t* idx_vec4, uint32_t ntris,
+                        const rt_uniform* u, float* near_out, float* far_out);
+/* The device ranges the most recent render's camera rays started on, npix = width * height
+ * floats each (synchronizes); *in_use (or NULL) = 0 and near = 0, far = +inf when it used none. */
+int rt_last_pixel_depth(rt_ctx* ctx, float* near_out, float* far_out, uint64_t npix, int* in_use);
 /* Message describing the last failure on this context (or the last
  * context-less failure when ctx == NULL).  Never NULL. */
 const char* rt_last_error(const rt_ctx* ctx);

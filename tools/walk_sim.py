@@ -1,7 +1,12 @@
 """Trip-count model of k_path's BSP walk under walk variants (tools/walk_sim.c).
 Rays: camera rays of a workload (random pixels, jittered), the W9E1 shadow ray
 of every hit (any-hit, direction (0, 1, 0), [1e-4, 999999 - 1e-4]) and a
-cosine bounce about the face normal.  usage: python tools/walk_sim.py [config] [rays]"""
+cosine bounce about the face normal.  usage: python tools/walk_sim.py [config] [rays]
+
+WALK_PIXDEPTH (RT_OPT_PIXEL_DEPTH's price): the rays of pixels the host empty-pixel mask
+flags are dropped, as the kernel drops them; 1: each camera ray's interval is its pixel's
+host depth range (pixel_depth_host) clipped to [1e-4, 5000]; 0: the same rays on the full
+interval, the figure to compare against.  WALK_HITTING=1 keeps the hitting camera rays."""
 import ctypes
 import os
 import subprocess
@@ -43,6 +48,11 @@ def main():
     u = O.make_uniform(*cfg.camera, cfg.width, cfg.height)
     rng = np.random.default_rng(1)
     rays, flags = [], []
+    pixdepth = os.environ.get("WALK_PIXDEPTH")
+    gaps, width = [], []
+    if pixdepth is not None:
+        rt = import_module("02562_raytracer_amd")
+        dnear, dfar = rt.pixel_depth_host(mesh, rt.make_uniform(*cfg.camera, cfg.width, cfg.height))
     t0 = time.time()
     # WALK_COHERENT=k: k consecutive samples of each pixel (the kernel's pixel-major units)
     coh = int(os.environ.get("WALK_COHERENT", "1"))
@@ -50,9 +60,22 @@ def main():
         if r_ % coh == 0:
             x, y = int(rng.integers(cfg.width)), int(rng.integers(cfg.height))
         o, d = O.camera_ray(u, x, y, float(rng.random()) / cfg.height, float(rng.random()) / cfg.height)
-        rays.append([*o, *d, 1e-4, 5000.0])
-        flags.append(0)
         hit, tri, dist = O.trace_one(sc, "BSP", o, d, 1e-4, 5000.0)
+        lo, hi = np.float32(1e-4), np.float32(5000.0)
+        if pixdepth is not None:
+            if not dnear[y, x] < dfar[y, x]:   # flagged empty: the kernel casts no ray
+                assert not hit
+                continue
+            if os.environ.get("WALK_HITTING") and not hit:
+                continue
+            width.append(float(dfar[y, x]) - float(dnear[y, x]))
+            if hit:
+                assert dnear[y, x] < dist < dfar[y, x], (x, y, dnear[y, x], dist, dfar[y, x])
+                gaps.append(float(dist) - float(dnear[y, x]))
+            if pixdepth == "1":
+                lo, hi = max(lo, dnear[y, x]), min(hi, dfar[y, x])
+        rays.append([*o, *d, lo, hi])
+        flags.append(0)
         if hit:
             p = (o + d * np.float32(dist)).astype(np.float32)
             rays.append([*p, 0.0, 1.0, 0.0, 1e-4, np.float32(999999.0) - np.float32(1e-4)])
@@ -297,6 +320,12 @@ def main():
         L.walk_sim_spec_stats(P(sp.ctypes.data))
         print("speculative cull per ray: flagged %.4f, spec-only culls %.4f, spec-only clip decisions %.4f, "
               "proven culls %.3f, re-walk trips %.3f, re-walk tests %.3f" % tuple(v / len(R) for v in sp[:6]))
+    if pixdepth is not None:
+        q = [0.01, 0.1, 0.25, 0.5, 0.75, 0.9, 0.99]
+        print(f"pixel depth {pixdepth}: {len(width)} camera rays of unflagged pixels kept, {len(gaps)} of them hit (full interval)")
+        print("  far - near over those rays' pixels, quantiles", q, [float(f"{v:.3g}") for v in np.quantile(width, q)])
+        if gaps:
+            print("  first-hit dist - near, quantiles", q, [float(f"{v:.3g}") for v in np.quantile(gaps, q)])
     print(f"config {cfgn}: {len(R)} rays ({sum(flags)} any-hit), {time.time() - t0:.1f} s")
     for v in range(5 if boxes is not None else 3):
         s = {k: round(out[v, i] / len(R), 3) for i, k in enumerate(NAMES)}
