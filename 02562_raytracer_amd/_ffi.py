@@ -160,6 +160,20 @@ class BvhView(C.Structure):
     _fields_ = [("nodes", C.POINTER(GpuNode)), ("tri_ids", u32p), ("nnodes", C.c_uint32), ("nids", C.c_uint32)]
 
 
+class AdaptiveSummary(C.Structure):   # include/rt.h rt_adaptive_summary
+    _fields_ = [("pixels", C.c_uint64), ("live_next", C.c_uint64), ("above", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("total_samples", C.c_uint64), ("max_rel_err", C.c_float), ("min_count", C.c_uint32),
+                ("max_count", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def asdict(self):
+        d = {n: int(getattr(self, n)) for n, _ in self._fields_ if n not in ("max_rel_err", "reserved")}
+        d["max_rel_err"] = float(self.max_rel_err)
+        return d
+
+
+RT_ADAPT_PIXEL, RT_ADAPT_TILE = 0, 1
+ADAPT_VOTES = {"pixel": RT_ADAPT_PIXEL, "tile": RT_ADAPT_TILE}
+
 # name -> (restype, argtypes); mirrors include/rt.h one to one
 SIGNATURES = {
     "rt_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -205,6 +219,13 @@ SIGNATURES = {
     "rt_noise_map": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_float, vp]),
     "rt_noise_summarize": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
                                      C.POINTER(NoiseSummary)]),
+    "rt_set_adaptive": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_uint32, C.c_int]),
+    "rt_adaptive_accumulate": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, vp, vp, vp, vp,
+                                         vp]),
+    "rt_adaptive_map": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_float, vp]),
+    "rt_adaptive_summarize": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
+                                        C.c_uint32, C.c_int, C.POINTER(AdaptiveSummary)]),
+    "rt_adaptive_in_use": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "rt_unpack_tiles": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "rt_comm_unique_id": (C.c_int, [vp]),
     "rt_comm_init": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),

@@ -453,6 +453,43 @@ class Context:
                                              C.byref(s)))
         return s.asdict()
 
+    # ---- adaptive sampling of the path modes (include/rt.h "adaptive sampling")
+    def set_adaptive(self, count_ptr=None, target=0.0, floor=1e-3, min_samples=16, vote="tile"):
+        """rt_set_adaptive: the device buffer of per-slot sample counts (uint32, indexed as
+        accum) and the rule's parameters; None turns it off."""
+        self._chk(F.lib().rt_set_adaptive(self._h, C.c_void_p(count_ptr) if count_ptr else None, float(target),
+                                          float(floor), int(min_samples), F.ADAPT_VOTES.get(vote, vote)))
+
+    def adaptive_accumulate(self, samples_ptr, npix, spp, pixel_major, first_iter, last_pass, live_ptr, accum_ptr,
+                            ids_ptr, state_ptr, count_ptr):
+        """rt_adaptive_accumulate: the fused fold of device records into the live pixels'
+        accumulation, id, noise state and count (device pointers; live: one byte per pixel)."""
+        self._chk(F.lib().rt_adaptive_accumulate(self._h, C.c_void_p(samples_ptr), npix, spp, int(bool(pixel_major)),
+                                                 first_iter, int(bool(last_pass)), C.c_void_p(live_ptr),
+                                                 C.c_void_p(accum_ptr), C.c_void_p(ids_ptr) if ids_ptr else None,
+                                                 C.c_void_p(state_ptr), C.c_void_p(count_ptr)))
+
+    def adaptive_map(self, state_ptr, count_ptr, npix, floor, rel_ptr):
+        """rt_adaptive_map: the relative standard error per slot with n = the slot's count."""
+        self._chk(F.lib().rt_adaptive_map(self._h, C.c_void_p(state_ptr), C.c_void_p(count_ptr), npix, float(floor),
+                                          C.c_void_p(rel_ptr)))
+
+    def adaptive_summary(self, state_ptr, count_ptr, width, height, iteration, target, floor=1e-3, min_samples=16,
+                         vote="tile"):
+        """rt_adaptive_summarize: {pixels, live_next, above, nonfinite, total_samples, min_count,
+        max_count, max_rel_err} of a row-major width x height frame; synchronizes."""
+        s = F.AdaptiveSummary()
+        self._chk(F.lib().rt_adaptive_summarize(self._h, C.c_void_p(state_ptr), C.c_void_p(count_ptr), width, height,
+                                                iteration, float(target), float(floor), int(min_samples),
+                                                F.ADAPT_VOTES.get(vote, vote), C.byref(s)))
+        return s.asdict()
+
+    def adaptive_in_use(self):
+        """rt_adaptive_in_use: {live, dealt, list} of the most recent path-mode render."""
+        live, dealt, took = C.c_uint64(0), C.c_uint64(0), C.c_int(0)
+        self._chk(F.lib().rt_adaptive_in_use(self._h, C.byref(live), C.byref(dealt), C.byref(took)))
+        return {"live": int(live.value), "dealt": int(dealt.value), "list": bool(took.value)}
+
     # ---- the tile gather over RCCL (include/rt.h "multi-GPU")
     @staticmethod
     def comm_unique_id():

@@ -159,6 +159,14 @@ struct rt_ctx {
     // rt_set_noise_buffer: the path modes' renders update it after every fold (device, caller-owned)
     rt_noise_state* noise = nullptr;
     DevBuf noise_sum;   // rt_noise_summarize's 24-B result
+    // rt_set_adaptive: the per-slot sample counts (device, caller-owned; null: off) and the
+    // rule's parameters; the live map, the list of one call and its build's scratch; what
+    // rt_adaptive_in_use reports of the most recent render
+    uint32_t* adapt_count = nullptr;
+    rtk::AdaptParams adapt = {0.0f, 1e-3f, 16u, RT_ADAPT_TILE};
+    DevBuf ad_live, ad_list, ad_flags, ad_offs, ad_scan, ad_stats;
+    bool adapt_used = false, adapt_list = false;
+    uint64_t adapt_live = 0, adapt_dealt = 0;
     // RT_OPT_EMPTY_PIXELS (ensure_empty; rt_empty.hip): the mask of empty_cam -- the camera
     // terms and the resolution the iterations are counted for -- once empty_iters reaches
     // kEmptyBuildIters; empty_tried: built or given up (over budget) for this camera.  The
@@ -1416,7 +1424,7 @@ static int ensure_active(rt_ctx* c, rtk::DevLaunch& L)
         const size_t nslots = (size_t)L.nwork * 64;
         HIPCHK(c, c->act_list.ensure(nslots * 4));
         HIPCHK(c, c->act_flags.ensure(nslots * 4));
-        HIPCHK(c, c->act_offs.ensure(nslots * 4));
+        HIPCHK(c, c->act_offs.ensure((nslots + 1) * 4));   // (the scan stores the total at [nslots])
         HIPCHK(c, c->act_scan.ensure(rtk::scan_scratch_words((uint32_t)nslots) * 4));
         uint32_t n = 0;
         if (rtk::build_active_list(L, c->empty_mask.as<uint32_t>(), c->act_flags.as<uint32_t>(), c->act_offs.as<uint32_t>(),
@@ -1548,6 +1556,14 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
     HIPCHK(c, hipMemsetAsync(c->counters.p, 0, 32 * sizeof(unsigned long long), c->stream));
     c->empty_used = c->depth_used = false;
     c->elided_primaries = 0;
+    c->adapt_used = c->adapt_list = false;
+    c->adapt_live = c->adapt_dealt = 0;
+    // rt_set_adaptive: the path modes only; the live set is read back on the context stream
+    const bool adaptive = path && c->adapt_count;
+    if (adaptive && !c->noise)
+        return fail(c, RT_E_NOT_READY, "rt_render: the adaptive count buffer needs a noise buffer (rt_set_noise_buffer)");
+    if (adaptive && c->async_fold)
+        return fail(c, RT_E_UNSUPPORTED, "rt_render: adaptive sampling does not run with RT_OPT_ASYNC_FOLD");
     if (L.nwork == 0 || (L.spp == 0 && (path || direct_prog))) {
         if (counts) return rt_last_counts(c, counts);
         return RT_OK;
@@ -1574,8 +1590,38 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
                 if (c->depth_used) L.pix_depth = c->empty_depth.as<float2>();
             }
         }
-        const bool nothing_active = ep && L.nactive == 0;
         const uint32_t* emask = ep ? c->empty_mask.as<uint32_t>() : nullptr;
+        // rt_set_adaptive: this call's live slots, decided here once from the state and the
+        // counts (every pass below runs with them); k_path's list becomes the live slots
+        // that are not flagged, where its instantiation takes one
+        bool nothing_live = false;
+        if (adaptive) {
+            const size_t nslots = (size_t)L.nwork * 64;
+            HIPCHK(c, c->ad_live.ensure(std::max<size_t>(L.stride, 1)));
+            HIPCHK(c, c->ad_list.ensure(nslots * 4));
+            HIPCHK(c, c->ad_flags.ensure(nslots * 4));
+            HIPCHK(c, c->ad_offs.ensure((nslots + 1) * 4));   // (the scan stores the total at [nslots])
+            HIPCHK(c, c->ad_scan.ensure(rtk::scan_scratch_words((uint32_t)nslots) * 4));
+            HIPCHK(c, c->ad_stats.ensure(16 * sizeof(unsigned long long)));
+            uint64_t n[3] = {0, 0, 0};
+            if (rtk::build_adaptive_list(L, emask, c->noise, c->adapt_count, c->adapt, c->ad_live.as<uint8_t>(),
+                                         c->ad_flags.as<uint32_t>(), c->ad_offs.as<uint32_t>(), c->ad_scan.as<uint32_t>(),
+                                         c->ad_list.as<uint32_t>(), c->ad_stats.as<unsigned long long>(), n, c->stream))
+                return fail(c, RT_E_DEVICE, "adaptive live list: launch failed");
+            c->adapt_used = true;
+            c->adapt_live = n[1];
+            nothing_live = n[1] == 0;
+            c->adapt_list = rtk::path_takes_list(S, mode, trav);
+            if (c->adapt_list) {
+                L.active = c->ad_list.as<uint32_t>();
+                L.nactive = (uint32_t)n[0];
+                c->adapt_dealt = n[0];
+            } else {
+                c->adapt_dealt = nothing_live ? 0 : L.stride;
+            }
+            c->elided_primaries = ep ? n[2] * L.spp : 0;
+        }
+        const bool nothing_active = adaptive ? (c->adapt_list ? L.nactive == 0 : nothing_live) : ep && L.nactive == 0;
         const uint64_t per_it = (uint64_t)L.stride * sizeof(float4);
         const uint64_t budget = c->sample_budget_mb << 20;
         uint32_t pass_spp = (uint32_t)std::min<uint64_t>(L.spp, std::max<uint64_t>(1, budget / per_it));
@@ -1635,6 +1681,13 @@ static int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaun
             HIPCHK(c, hipMemsetAsync(c->work.p, 0, 4096, c->stream));
             if (!nothing_active)
                 if (int r = probe_launch(c, S, L, mode, trav, slot)) return r;
+            if (adaptive) {   // k_fold and k_noise fused, for the live slots alone
+                if (!nothing_live &&
+                    rtk::launch_adaptive_fold(L, emask, c->ad_live.as<uint8_t>(), c->noise, c->adapt_count,
+                                              done + L.spp >= total, c->stream))
+                    return fail(c, RT_E_DEVICE, std::string("adaptive fold launch failed: ") + hipGetErrorString(hipGetLastError()));
+                continue;
+            }
             const int r = rtk::launch_fold(L, emask, c->stream);
             if (r) return fail(c, r, std::string("fold launch failed: ") + hipGetErrorString(hipGetLastError()));
             if (c->noise && rtk::launch_noise(L, emask, c->noise, c->stream))
@@ -1829,6 +1882,139 @@ int rt_noise_summarize(rt_ctx* c, const rt_noise_state* state, uint32_t npix, ui
 // The 255 thresholds of 8-bit sRGB codes: code k+1 starts where
 // 255 * oetf(v) reaches k + 0.5 (oetf inverted in double, rounded up to the
 // first float whose code is k + 1).
+// ---- adaptive sampling (rt.h "adaptive sampling"; rt_adaptive.hip) -------------
+static int adaptive_args(rt_ctx* c, const char* who, float target, float floor, uint32_t min_samples, int vote)
+{
+    if (min_samples < 2) return fail(c, RT_E_INVALID, std::string(who) + ": min_samples must be >= 2");
+    if (!(target >= 0.0f)) return fail(c, RT_E_INVALID, std::string(who) + ": target must be >= 0 and not NaN");
+    if (!(floor > 0.0f)) return fail(c, RT_E_INVALID, std::string(who) + ": floor must be > 0");
+    if (vote != RT_ADAPT_PIXEL && vote != RT_ADAPT_TILE)
+        return fail(c, RT_E_INVALID, std::string(who) + ": vote must be RT_ADAPT_PIXEL or RT_ADAPT_TILE");
+    return RT_OK;
+}
+
+int rt_set_adaptive(rt_ctx* c, uint32_t* count_dev, float target, float floor, uint32_t min_samples, int vote)
+{
+    if (!c) return fail(nullptr, RT_E_INVALID, "rt_set_adaptive: null context");
+    if (!count_dev) {
+        c->adapt_count = nullptr;
+        return RT_OK;
+    }
+    if ((uintptr_t)count_dev % 4) return fail(c, RT_E_INVALID, "rt_set_adaptive: the counts must be 4-byte aligned");
+    if (int r = adaptive_args(c, "rt_set_adaptive", target, floor, min_samples, vote)) return r;
+    c->adapt_count = count_dev;
+    c->adapt = rtk::AdaptParams{target, floor, min_samples, (uint32_t)vote};
+    return RT_OK;
+}
+
+// a row-major region of w x h pixels as a launch's geometry
+static rtk::DevLaunch region_launch(uint32_t w, uint32_t h)
+{
+    rtk::DevLaunch L;
+    memset(&L, 0, sizeof L);
+    L.w = w;
+    L.h = h;
+    L.nranks = 1;
+    L.tiles_x = (w + 7) / 8;
+    L.tiles_y = (h + 7) / 8;
+    L.nwork = L.tiles_x * L.tiles_y;
+    L.u.resolution[0] = w;
+    L.u.resolution[1] = h;
+    return L;
+}
+
+int rt_adaptive_accumulate(rt_ctx* c, const float* samples, uint32_t npix, uint32_t spp, int pixel_major,
+                           uint32_t first_iter, int last_pass, const uint8_t* live, float* accum, uint32_t* ids,
+                           rt_noise_state* state, uint32_t* count)
+{
+    if (!c) return fail(nullptr, RT_E_INVALID, "rt_adaptive_accumulate: null context");
+    if (npix == 0 || spp == 0) return RT_OK;
+    if (!samples || !live || !accum || !state || !count)
+        return fail(c, RT_E_INVALID, "rt_adaptive_accumulate: null buffer");
+    if ((uintptr_t)samples % 16 || (uintptr_t)accum % 16 || (uintptr_t)state % 8 || (uintptr_t)count % 4 ||
+        (uintptr_t)ids % 4)
+        return fail(c, RT_E_INVALID, "rt_adaptive_accumulate: the records and the accumulation must be 16-byte, the "
+                                     "state 8-byte, the counts and ids 4-byte aligned");
+    if ((uint64_t)first_iter + spp > 0xFFFFFFFFull)
+        return fail(c, RT_E_INVALID, "rt_adaptive_accumulate: first_iter + spp overflows");
+    if (int r = set_dev(c)) return r;
+    // the fold's view of the records: a region of npix x 1 pixels, one pass
+    rtk::DevLaunch L = region_launch(npix, 1);
+    L.first_iter = first_iter;
+    L.spp = spp;
+    L.chunk = 1;
+    L.nchunks = spp;
+    L.unit_order = pixel_major ? 1u : 0u;
+    L.stride = npix;
+    L.samples = reinterpret_cast<float4*>(const_cast<float*>(samples));   // (read only)
+    L.accum = reinterpret_cast<float4*>(accum);
+    L.ids = ids;
+    if (rtk::launch_adaptive_fold(L, nullptr, live, state, count, last_pass != 0, c->stream))
+        return fail(c, RT_E_DEVICE, std::string("rt_adaptive_accumulate: launch failed: ") +
+                                        hipGetErrorString(hipGetLastError()));
+    return RT_OK;
+}
+
+int rt_adaptive_map(rt_ctx* c, const rt_noise_state* state, const uint32_t* count, uint32_t npix, float floor, float* rel)
+{
+    if (!c) return fail(nullptr, RT_E_INVALID, "rt_adaptive_map: null context");
+    if (!(floor > 0.0f)) return fail(c, RT_E_INVALID, "rt_adaptive_map: floor must be > 0");
+    if (npix == 0) return RT_OK;
+    if (!state || !count || !rel) return fail(c, RT_E_INVALID, "rt_adaptive_map: null buffer");
+    if ((uintptr_t)state % 8 || (uintptr_t)count % 4 || (uintptr_t)rel % 4)
+        return fail(c, RT_E_INVALID, "rt_adaptive_map: the state must be 8-byte, the counts and the map 4-byte aligned");
+    if (int r = set_dev(c)) return r;
+    if (rtk::launch_adaptive_map(state, count, npix, floor, rel, c->stream))
+        return fail(c, RT_E_DEVICE, "rt_adaptive_map: launch failed");
+    return RT_OK;
+}
+
+int rt_adaptive_summarize(rt_ctx* c, const rt_noise_state* state, const uint32_t* count, uint32_t width, uint32_t height,
+                          uint32_t iteration, float target, float floor, uint32_t min_samples, int vote,
+                          rt_adaptive_summary* out)
+{
+    if (!c) return fail(nullptr, RT_E_INVALID, "rt_adaptive_summarize: null context");
+    if (!out) return fail(c, RT_E_INVALID, "rt_adaptive_summarize: null summary");
+    if (int r = adaptive_args(c, "rt_adaptive_summarize", target, floor, min_samples, vote)) return r;
+    const uint64_t npix = (uint64_t)width * height;
+    if (npix >= (1ull << 31)) return fail(c, RT_E_INVALID, "rt_adaptive_summarize: the frame is too large");
+    memset(out, 0, sizeof *out);
+    out->pixels = npix;
+    if (npix == 0) return RT_OK;
+    if (!state || !count) return fail(c, RT_E_INVALID, "rt_adaptive_summarize: null buffer");
+    if ((uintptr_t)state % 8 || (uintptr_t)count % 4)
+        return fail(c, RT_E_INVALID, "rt_adaptive_summarize: the state must be 8-byte and the counts 4-byte aligned");
+    if (int r = set_dev(c)) return r;
+    rtk::DevLaunch L = region_launch(width, height);
+    L.first_iter = iteration;
+    const rtk::AdaptParams P{target, floor, min_samples, (uint32_t)vote};
+    HIPCHK(c, c->ad_stats.ensure(16 * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->ad_stats.p, 0, 16 * sizeof(unsigned long long), c->stream));
+    if (rtk::launch_adaptive_summary(L, state, count, P, c->ad_stats.as<unsigned long long>(), c->stream))
+        return fail(c, RT_E_DEVICE, "rt_adaptive_summarize: launch failed");
+    unsigned long long h[9] = {};
+    HIPCHK(c, hipMemcpyAsync(h, c->ad_stats.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out->live_next = h[0];
+    out->above = h[2];
+    out->nonfinite = h[3];
+    out->total_samples = h[4];
+    const uint32_t bits = (uint32_t)h[5];
+    memcpy(&out->max_rel_err, &bits, 4);
+    out->min_count = ~(uint32_t)h[6];
+    out->max_count = (uint32_t)h[7];
+    return RT_OK;
+}
+
+int rt_adaptive_in_use(rt_ctx* c, uint64_t* live_slots, uint64_t* dealt_slots, int* took_list)
+{
+    if (!c) return RT_E_INVALID;
+    if (live_slots) *live_slots = c->adapt_used ? c->adapt_live : 0;
+    if (dealt_slots) *dealt_slots = c->adapt_used ? c->adapt_dealt : 0;
+    if (took_list) *took_list = c->adapt_used && c->adapt_list ? 1 : 0;
+    return RT_OK;
+}
+
 static void srgb_code_thresholds(float* t)
 {
     for (int k = 0; k < 255; k++) {
@@ -2074,8 +2260,11 @@ int rt_last_counts(rt_ctx* c, rt_ray_counts* counts)
     uint64_t* dst = reinterpret_cast<uint64_t*>(counts);
     for (size_t i = 0; i < sizeof(rt_ray_counts) / sizeof(uint64_t); i++) dst[i] = h[i];
     // the camera rays RT_OPT_EMPTY_PIXELS did not cast are rays the reference's shader casts
-    counts->samples += c->elided_primaries;
-    counts->primary += c->elided_primaries;
+    // (rt_set_adaptive: the rays actually traced)
+    if (!c->adapt_used) {
+        counts->samples += c->elided_primaries;
+        counts->primary += c->elided_primaries;
+    }
     c->last = *counts;
     return RT_OK;
 }

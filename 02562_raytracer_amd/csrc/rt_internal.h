@@ -118,7 +118,9 @@ struct DevLaunch {
         uint32_t* bvh_deep;       // BVH walk: stack entries beyond the LDS share, (50 - K) x grid lanes
         // BSP walk of W9E1 (RT_OPT_EMPTY_PIXELS, rt_empty.hip): the launch's pixel slots that
         // are valid and not flagged empty, ascending, nactive of them; null: k_path deals
-        // every slot of the launch
+        // every slot of the launch.  With rt_set_adaptive (rt_adaptive.hip) the list holds the
+        // live slots that are not flagged, for every BSP instantiation that reads one
+        // (rt_kernels.hip path_takes_list)
         const uint32_t* active;
     };
     // ray capture (rt_set_ray_capture; the counting instantiation only): every ray
@@ -228,6 +230,34 @@ int launch_noise_map(const rt_noise_state* state, uint32_t npix, uint32_t n, flo
 int launch_noise_summary(const rt_noise_state* state, uint32_t npix, uint32_t n, float threshold, float floor,
                          unsigned long long* out, hipStream_t stream);
 
+// Adaptive sampling (rt_adaptive.hip; rt.h "adaptive sampling").
+struct AdaptParams {
+    float target, floor;
+    uint32_t min_samples, vote;   // RT_ADAPT_PIXEL / RT_ADAPT_TILE
+};
+// does the k_path instantiation of (mode, trav) for this scene deal its work units from
+// DevLaunch::active?  (rt_kernels.hip, beside launch_path)
+bool path_takes_list(const DevScene& s, rt_mode mode, rt_traverse trav);
+// The live slots of a call that starts at l.first_iter, decided from state and count:
+// live: one byte per output slot (as accum is indexed; zeroed here, 1 = live); list: the
+// pixel slots that are live and not flagged by empty_mask (or null), ascending.  flags, offs
+// and list hold l.nwork * 64 words each, scan: scan_scratch_words(l.nwork * 64), stats: 16
+// u64.  out (host; the stream is synchronised): {list entries, live slots, live slots that
+// are flagged empty}.  offs holds one word more than flags: the scan stores the total there
+int build_adaptive_list(const DevLaunch& l, const uint32_t* empty_mask, const rt_noise_state* state,
+                        const uint32_t* count, const AdaptParams& p, uint8_t* live, uint32_t* flags, uint32_t* offs,
+                        uint32_t* scan, uint32_t* list, unsigned long long* stats, uint64_t out[3], hipStream_t stream);
+// k_fold + k_noise of one pass fused, for the live slots alone; last_pass: count = l.first_iter + l.spp
+int launch_adaptive_fold(const DevLaunch& l, const uint32_t* empty_mask, const uint8_t* live, rt_noise_state* state,
+                         uint32_t* count, bool last_pass, hipStream_t stream);
+// rel[i] with n = count[i] (0x7FC00000: count < 2 or a non-finite state)
+int launch_adaptive_map(const rt_noise_state* state, const uint32_t* count, uint32_t npix, float floor, float* rel,
+                        hipStream_t stream);
+// stats (device, 16 u64, zeroed before the launch; k_adaptive_live's layout) of l's region, with
+// l.first_iter the iteration whose live set is counted
+int launch_adaptive_summary(const DevLaunch& l, const rt_noise_state* state, const uint32_t* count,
+                            const AdaptParams& p, unsigned long long* stats, hipStream_t stream);
+
 // display frame: RGBA32F accum -> 8-bit sRGB (thr: 255 device floats, srgb_code_thresholds)
 int launch_frame(const float4* accum, uint32_t npix, const float* thr, uchar4* out, hipStream_t stream);
 // the same without the pow, for the modes whose shader returns its colour as it is
@@ -278,6 +308,7 @@ int launch_bsp_repack(const uint32_t* tree, const float* planes, uint32_t nnodes
                       const float4* pos, const uint4* idx, const uint32_t* ids, uint32_t nids, float margin,
                       void* box_scratch, uint2* tm, hipStream_t stream);
 // device primitives shared by the builders (rt_build.hip)
+// (out holds n + 1 words: the total goes to out[n])
 int scan_exclusive_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* scratch, hipStream_t s);
 size_t scan_scratch_words(uint32_t n);
 int radix_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, uint32_t passes,
@@ -300,8 +331,8 @@ int launch_empty_area(const float4* pos, const uint4* idx, uint32_t nverts, uint
 int launch_empty_mask(const float4* pos, const uint4* idx, uint32_t nverts, uint32_t ntris, const float cam14[14],
                       uint32_t W, uint32_t H, float scale, const uint32_t* big, uint32_t nbig, uint8_t* hit,
                       uint32_t* mask, uint32_t* flagged, uint2* depth, hipStream_t stream);
-// the active list of l's pixel slots under the mask: flags and offs hold l.nwork * 64
-// words each, scan: scan_scratch_words(l.nwork * 64); active: l.nwork * 64 words;
+// the active list of l's pixel slots under the mask: flags holds l.nwork * 64 words and offs
+// one more (scan_exclusive_u32 stores the total at out[n]), scan: scan_scratch_words(l.nwork * 64); active: l.nwork * 64 words;
 // *nactive (host) is read back, which synchronises the stream
 int build_active_list(const DevLaunch& l, const uint32_t* empty_mask, uint32_t* flags, uint32_t* offs, uint32_t* scan, uint32_t* active,
                       uint32_t* nactive, hipStream_t stream);

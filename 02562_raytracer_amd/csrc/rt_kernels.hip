@@ -1331,6 +1331,8 @@ __device__ __forceinline__ void capture_ray(const DevLaunch& L, const f3 o, cons
     }
 }
 
+// (k_path alone) CM_LIST: formula 1, and the refill deals its work units from DevLaunch::active
+constexpr int CM_LIST = 3;
 template <int MODE, int TRAV, bool COUNT, int CM = 1>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
     TRAV == RT_TRAVERSE_BVH ? RT_BVH_WAVES_PER_EU : MODE == RT_MODE_W7E3 ? RT_W7E3_WAVES_PER_EU : RT_PATH_WAVES_PER_EU,
@@ -1391,6 +1393,17 @@ k_path(DevScene S, DevLaunch L)
     // RT_OPT_EMPTY_PIXELS: W9E1's BSP walk deals no work unit for a pixel that no camera
     // ray can leave with a hit (the refill's active list; rt_empty.hip)
     constexpr bool EMPTYPX = REDRAW && TRAV == RT_TRAVERSE_BSP;
+    // The refill's active list itself (L.active / L.nactive: RT_OPT_EMPTY_PIXELS' unflagged
+    // slots, and the live slots of rt_set_adaptive, rt_adaptive.hip).  W9E1's BSP
+    // instantiations hold it; for the other modes' BSP walk it is an instantiation of its
+    // own, CM_LIST (the generic margin formula and the list), launched only when a render
+    // hands k_path a list -- compiled into the instantiation every render runs, it cost
+    // W7E3's bench frame 0.14 % (profiles/r11/ab_default.txt).  W7E3's fast-margin
+    // instantiation has none (the list takes it past its spill budget,
+    // tests/test_isa_guard.py), nor has the BVH walk, which holds bvh_deep in that slot:
+    // path_takes_list below tells the host.
+    constexpr bool ACTLIST = EMPTYPX || (TRAV == RT_TRAVERSE_BSP && CM == CM_LIST);
+    constexpr int WCM = CM == CM_LIST ? 1 : CM;   // the walk's margin formula
     const float ETA = W9 ? 0.0001f : 0.01f;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t T = L.shade_threshold;
@@ -1533,7 +1546,7 @@ k_path(DevScene S, DevLaunch L)
             }
             const bool go = st == ST_TRACE;
             if (go) {
-                if (trav_step<TRAV, COUNT, W9E3, CM>(S, stk, dp, ro, rd, inv, shadow, tr, cnt, chk)) st = ST_SHADE;
+                if (trav_step<TRAV, COUNT, W9E3, WCM>(S, stk, dp, ro, rd, inv, shadow, tr, cnt, chk)) st = ST_SHADE;
             }
             // further steps before the next check: the check (two ballots, a
             // popcount, the compares) is SALU work, and the SALU is a per-CU
@@ -1541,7 +1554,7 @@ k_path(DevScene S, DevLaunch L)
 #pragma unroll
             for (int k = 1; k < (COUNT ? 1 : TRAV == RT_TRAVERSE_BVH ? RT_BVH_TRIPS_PER_CHECK : RT_TRIPS_PER_CHECK); ++k) {
                 if (st == ST_TRACE) {
-                    if (trav_step<TRAV, COUNT, W9E3, CM>(S, stk, dp, ro, rd, inv, shadow, tr, cnt, chk)) st = ST_SHADE;
+                    if (trav_step<TRAV, COUNT, W9E3, WCM>(S, stk, dp, ro, rd, inv, shadow, tr, cnt, chk)) st = ST_SHADE;
                 }
             }
         }
@@ -1568,7 +1581,7 @@ k_path(DevScene S, DevLaunch L)
         const uint32_t it_end = L.first_iter + L.spp;
         // pixel slots: all of the launch's, or (RT_OPT_EMPTY_PIXELS, W9E1's BSP walk) the
         // active list's -- the slots whose pixel is not flagged empty
-        const uint32_t pslots = (EMPTYPX && L.active) ? L.nactive : L.nwork * 64u;
+        const uint32_t pslots = (ACTLIST && L.active) ? L.nactive : L.nwork * 64u;
         const uint32_t nslots = pslots * L.nchunks;       // work units (host keeps this < 2^31)
         const f3 env = V(L.env[0], L.env[1], L.env[2]);
         // ---- shading phase
@@ -1894,7 +1907,7 @@ k_path(DevScene S, DevLaunch L)
                     uint32_t ch, ps;
                     uint32_t psl = sopaque(L.nwork) * 64u;
                     const uint32_t nch = sopaque(L.nchunks);
-                    if constexpr (EMPTYPX) {
+                    if constexpr (ACTLIST) {
                         if (L.active) psl = sopaque(L.nactive);
                     }
                     if (L.unit_order == 0u) {
@@ -1905,7 +1918,7 @@ k_path(DevScene S, DevLaunch L)
                         ch = slot - ps * nch;
                     }
                     // the ps-th active slot's pixel (ps < nactive: slot < nslots)
-                    if constexpr (EMPTYPX) {
+                    if constexpr (ACTLIST) {
                         if (L.active) ps = L.active[ps];
                     }
                     const Pix p = map_pixel(L, ps >> 6, ps & 63u);
@@ -2680,7 +2693,22 @@ static void launch_path(const DevScene& s, const DevLaunch& l, int grid, size_t 
             return;
         }
     }
+    // a render that hands the other modes' BSP walk a list (rt_set_adaptive) runs the
+    // instantiation that reads it; W9E1's own instantiations do (k_path's ACTLIST)
+    if constexpr (MODE != RT_MODE_W9E1 && MODE != MODE_W9E1_TRANSPARENT && TRAV == RT_TRAVERSE_BSP) {
+        if (l.active) {
+            hipLaunchKernelGGL((k_path<MODE, TRAV, COUNT, CM_LIST>), dim3(grid), dim3(256), lds, st, s, l);
+            return;
+        }
+    }
     hipLaunchKernelGGL((k_path<MODE, TRAV, COUNT>), dim3(grid), dim3(256), lds, st, s, l);
+}
+// does the k_path instantiation launch_path picks for (mode, trav) and this scene deal its
+// work units from l.active (k_path's ACTLIST)?
+bool path_takes_list(const DevScene& s, rt_mode mode, rt_traverse trav)
+{
+    if (trav != RT_TRAVERSE_BSP) return false;
+    return !(mode == RT_MODE_W7E3 && s.cull_k1 == 0.0f);
 }
 int launch_render(const DevScene& s, const DevLaunch& l, rt_mode mode, rt_traverse trav, bool detail, int num_cus,
                   int waves_per_cu, hipStream_t stream)

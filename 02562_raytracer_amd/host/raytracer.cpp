@@ -363,11 +363,15 @@ void RenderState::release()
     if (ids_) rt_device_free(gpu_.ctx(), ids_);
     if (tile_accum_) rt_device_free(gpu_.ctx(), tile_accum_);
     if (tile_ids_) rt_device_free(gpu_.ctx(), tile_ids_);
+    if (counts_) {
+        rt_set_adaptive(gpu_.ctx(), nullptr, 0.0f, 0.0f, 0, 0);
+        rt_device_free(gpu_.ctx(), counts_);
+    }
     if (noise_) {
         rt_set_noise_buffer(gpu_.ctx(), nullptr);
         rt_device_free(gpu_.ctx(), noise_);
     }
-    accum_ = ids_ = tile_accum_ = tile_ids_ = noise_ = nullptr;
+    accum_ = ids_ = tile_accum_ = tile_ids_ = noise_ = counts_ = nullptr;
 }
 
 static bool writes_records(rt_mode m)   // the k_path modes (rt.h "noise estimate")
@@ -437,9 +441,72 @@ uint32_t RenderState::render_until(float target, uint32_t max_samples, uint32_t 
     return iteration_;
 }
 
+static const char* const kAdaptiveUntiled =
+    " is for an untiled state: a tiled render (set_tiling, any rank count) keeps its counts packed per tile";
+
+void RenderState::enable_adaptive(float target, float floor, uint32_t min_samples, int vote)
+{
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("enable_adaptive") + kAdaptiveUntiled);
+    if (!writes_records(mode_))
+        throw Error(RT_E_UNSUPPORTED, "enable_adaptive: the mode writes no per-iteration records");
+    if (iteration_) throw Error(RT_E_INVALID, "enable_adaptive: the counts start at iteration 0");
+    if (min_samples < 2 || !(target >= 0.0f) || !(floor > 0.0f) || (vote != RT_ADAPT_PIXEL && vote != RT_ADAPT_TILE))
+        throw Error(RT_E_INVALID, "enable_adaptive: min_samples >= 2, target >= 0, floor > 0, vote pixel or tile");
+    if (!noise_) enable_noise();
+    rt_ctx* c = gpu_.ctx();
+    if (!counts_) {
+        const size_t npx = (size_t)width_ * height_;
+        gpu_.check(rt_device_alloc(c, npx * 4, &counts_), "sample count buffer");
+        gpu_.check(rt_memset_device(c, counts_, 0, npx * 4), "clear sample counts");
+    }
+    ad_target_ = target;
+    ad_floor_ = floor;
+    ad_min_ = min_samples;
+    ad_vote_ = vote;
+    gpu_.check(rt_set_adaptive(c, static_cast<uint32_t*>(counts_), target, floor, min_samples, vote), "set adaptive");
+}
+
+std::vector<uint32_t> RenderState::sample_counts() const
+{
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("sample_counts") + kAdaptiveUntiled);
+    if (!counts_) throw Error(RT_E_NOT_READY, "sample_counts: enable_adaptive() first");
+    std::vector<uint32_t> out((size_t)width_ * height_);
+    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), out.data(), counts_, out.size() * 4), "sample_counts");
+    return out;
+}
+
+rt_adaptive_summary RenderState::adaptive_summary() const
+{
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("adaptive_summary") + kAdaptiveUntiled);
+    if (!counts_) throw Error(RT_E_NOT_READY, "adaptive_summary: enable_adaptive() first");
+    rt_adaptive_summary s;
+    gpu_.check(rt_adaptive_summarize(gpu_.ctx(), static_cast<const rt_noise_state*>(noise_),
+                                     static_cast<const uint32_t*>(counts_), width_, height_, iteration_, ad_target_,
+                                     ad_floor_, ad_min_, ad_vote_, &s),
+               "adaptive_summary");
+    return s;
+}
+
+uint32_t RenderState::render_adaptive(uint32_t max_samples, uint32_t batch, rt_adaptive_summary* summary)
+{
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("render_adaptive") + kAdaptiveUntiled);
+    if (!counts_) throw Error(RT_E_NOT_READY, "render_adaptive: enable_adaptive() first");
+    if (!progressive_) throw Error(RT_E_INVALID, "render_adaptive needs progressive rendering");
+    if (batch == 0) throw Error(RT_E_INVALID, "render_adaptive: batch must be at least 1");
+    rt_adaptive_summary s{};
+    while (iteration_ < max_samples) {
+        render(std::min(batch, max_samples - iteration_));
+        s = adaptive_summary();
+        if (s.live_next == 0) break;
+    }
+    if (summary) *summary = s;
+    return iteration_;
+}
+
 void RenderState::set_tiling(uint32_t nranks, uint32_t rank, const uint8_t comm_id[RT_COMM_ID_BYTES])
 {
     if (tiled_) throw Error(RT_E_INVALID, "set_tiling: already tiled");
+    if (counts_) throw Error(RT_E_UNSUPPORTED, "set_tiling: adaptive sampling is enabled (it is for an untiled state)");
     // the noise buffer is width x height states, row-major; tile renders would write it packed per tile
     if (noise_) throw Error(RT_E_UNSUPPORTED, "set_tiling: the noise estimate is enabled (it is for an untiled state)");
     gpu_.check(rt_comm_init(gpu_.ctx(), nranks, rank, comm_id), "communicator");
@@ -522,7 +589,7 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
     }
     gpu_.check(rt_set_environment(c, opts_.environment.data()), "environment");
     gpu_.check(rt_set_environment_map(c, nullptr, 0, 0), "environment map");
-    const bool had_noise = noise_ != nullptr;
+    const bool had_noise = noise_ != nullptr, had_adaptive = counts_ != nullptr;
     release();
     const size_t npx = (size_t)width_ * height_;
     gpu_.check(rt_device_alloc(c, npx * 16, &accum_), "accumulation buffer");
@@ -531,6 +598,7 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
     alloc_tiles();
     iteration_ = 0;
     if (had_noise && writes_records(mode_)) enable_noise();   // the buffer follows the scene
+    if (had_adaptive && writes_records(mode_)) enable_adaptive(ad_target_, ad_floor_, ad_min_, ad_vote_);
     update();
 }
 

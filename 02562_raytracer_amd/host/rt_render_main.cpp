@@ -17,6 +17,17 @@
 //                                        pixels, above, nonfinite, max_rel_err}, and --out
 //                                        writes PREFIX.noise.f32, the H*W map; an untiled
 //                                        render only: refused with --comm-file / --nranks)
+//             [--adaptive-target T [--adaptive-min N] [--adaptive-vote pixel|tile] [--noise-batch B]]
+//                                        (a path-mode scene: adaptive sampling, render_adaptive --
+//                                        B (16) iterations at a time for the pixels (or 8x8 tiles,
+//                                        the default vote) that have fewer than N (16) samples or a
+//                                        relative standard error above T, until none is left or
+//                                        --samples / --spp (1024) iterations are done; the JSON
+//                                        line gains "adaptive": {iterations, pixels, live_next,
+//                                        above, nonfinite, total_samples, min_count, max_count,
+//                                        max_rel_err}, and --out writes PREFIX.count.u32, the H*W
+//                                        sample counts; refused with --comm-file / --nranks and
+//                                        with --noise-target)
 //   rt_render ... --nranks N --rank R --comm-file PATH [--comm-token T] [--device D]
 //                                        (one process per GPU: rank R renders its
 //                                        interleaved tiles, rank 0 gathers the frame
@@ -237,6 +248,17 @@ int main(int argc, char** argv)
         // (--nranks 1 too), and its states would be packed per tile, not the H x W map
         if (arg("--noise-target") && (nranks > 1 || arg("--comm-file")))
             throw Error(RT_E_UNSUPPORTED, "--noise-target does not go with --comm-file / --nranks (a tiled render)");
+        const bool adaptive = arg("--adaptive-target") || arg("--adaptive-min") || arg("--adaptive-vote");
+        if (adaptive && (nranks > 1 || arg("--comm-file")))
+            throw Error(RT_E_UNSUPPORTED,
+                        "--adaptive-target / --adaptive-min / --adaptive-vote do not go with --comm-file / --nranks (a tiled render)");
+        if (adaptive && !arg("--adaptive-target")) throw Error(RT_E_INVALID, "--adaptive-min / --adaptive-vote need --adaptive-target T");
+        if (adaptive && arg("--noise-target")) throw Error(RT_E_INVALID, "--adaptive-target does not go with --noise-target");
+        int vote = RT_ADAPT_TILE;
+        if (const std::string* v = arg("--adaptive-vote")) {
+            if (*v == "pixel") vote = RT_ADAPT_PIXEL;
+            else if (*v != "tile") throw Error(RT_E_INVALID, "--adaptive-vote pixel|tile");
+        }
         GpuHandles gpu(arg("--device") ? std::atoi(arg("--device")->c_str()) : (int)rank);
         RenderState rs(gpu, find_scene(*name), opt);
         if (const std::string* cf = arg("--comm-file")) {
@@ -308,6 +330,28 @@ int main(int argc, char** argv)
                           "\"max_rel_err\":%s}",
                           its, (unsigned long long)ns.pixels, (unsigned long long)ns.above,
                           (unsigned long long)ns.nonfinite, hexf(ns.max_rel_err).c_str());
+            noise_json = b;
+        } else if (const std::string* t = arg("--adaptive-target")) {   // adaptive sampling (render_adaptive)
+            const uint32_t cap = arg("--samples") ? (uint32_t)std::atoi(arg("--samples")->c_str())
+                                 : arg("--spp")   ? (uint32_t)std::atoi(arg("--spp")->c_str())
+                                                  : 1024u;
+            const uint32_t batch = arg("--noise-batch") ? (uint32_t)std::atoi(arg("--noise-batch")->c_str()) : 16u;
+            const uint32_t amin = arg("--adaptive-min") ? (uint32_t)std::atoi(arg("--adaptive-min")->c_str()) : 16u;
+            rs.enable_adaptive((float)std::atof(t->c_str()), 1e-3f, amin, vote);
+            rt_adaptive_summary as;
+            const uint32_t its = rs.render_adaptive(cap, batch, &as);
+            frames = (its + batch - 1) / batch;
+            if (const std::string* out = arg("--out")) {
+                const auto cn = rs.sample_counts();
+                write_file(*out + ".count.u32", cn.data(), cn.size() * 4);
+            }
+            char b[384];
+            std::snprintf(b, sizeof b,
+                          ",\"adaptive\":{\"iterations\":%u,\"pixels\":%llu,\"live_next\":%llu,\"above\":%llu,"
+                          "\"nonfinite\":%llu,\"total_samples\":%llu,\"min_count\":%u,\"max_count\":%u,\"max_rel_err\":%s}",
+                          its, (unsigned long long)as.pixels, (unsigned long long)as.live_next,
+                          (unsigned long long)as.above, (unsigned long long)as.nonfinite,
+                          (unsigned long long)as.total_samples, as.min_count, as.max_count, hexf(as.max_rel_err).c_str());
             noise_json = b;
         } else if (const std::string* s = arg("--samples")) {   // the progressive loop, SetSamples
             rs.set_samples((uint32_t)std::atoi(s->c_str()), true);

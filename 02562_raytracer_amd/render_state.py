@@ -48,6 +48,8 @@ class RenderState:
         self.subdivision_level = 1   # Uniform.subdivision_level (uniform.rs:122-129)
         self.camera_controller = CameraController()
         self.noise = None   # enable_noise(): the device buffer of rt_noise_state
+        self.counts = None  # enable_adaptive(): the device buffer of per-pixel sample counts
+        self.adaptive = None   # its parameters: target, floor, min_samples, vote
         self.setup_rendering(scene)
 
     def _background(self, scene):
@@ -116,11 +118,16 @@ class RenderState:
         self.accum.zero()
         self.ids = self.ctx.alloc(npx * 4)
         self.iteration = 0
+        adaptive = self.adaptive
+        if adaptive is not None:
+            self.disable_adaptive()
         if self.noise is not None:
             # the noise buffer follows the scene: a new one for a path mode, none otherwise
             self.disable_noise()
             if self.mode in F.NOISE_MODES:
                 self.enable_noise()
+        if adaptive is not None and self.mode in F.NOISE_MODES:
+            self.enable_adaptive(**adaptive)   # and so do the sample counts
         self.update()
 
     def _load_model(self, model):
@@ -219,6 +226,8 @@ class RenderState:
         self.ctx.set_noise_buffer(self.noise.ptr)
 
     def disable_noise(self):
+        if self.counts is not None:
+            self.disable_adaptive()   # (a count buffer without a noise buffer renders nothing)
         self.ctx.set_noise_buffer(None)
         if self.noise is not None:
             self.noise.free()   # (rt_device_free waits for the renders that wrote it)
@@ -265,6 +274,73 @@ class RenderState:
                 summary = self.noise_summary(target, floor)
                 if summary["above"] <= allow * summary["pixels"]:
                     break
+        return self.iteration, summary
+
+    # ---- adaptive sampling (include/rt.h "adaptive sampling"; single process, no tiles)
+    def enable_adaptive(self, target, floor=1e-3, min_samples=16, vote="tile"):
+        """Render only the pixels that have not converged: a pixel (vote "pixel") or an 8x8
+        tile (vote "tile", the default) stops taking samples once it has min_samples
+        iterations and its relative standard error is at most target (rt_set_adaptive).
+        Enables the noise estimate if needed; starts at iteration 0; reallocated by
+        load_scene."""
+        if vote not in F.ADAPT_VOTES:
+            raise ValueError(f"enable_adaptive: vote must be one of {', '.join(F.ADAPT_VOTES)}")
+        if int(min_samples) < 2:
+            raise ValueError("enable_adaptive: min_samples must be at least 2")
+        if not float(target) >= 0.0:
+            raise ValueError("enable_adaptive: target must be >= 0")
+        if not float(floor) > 0.0:
+            raise ValueError("enable_adaptive: floor must be > 0")
+        if self.iteration:
+            raise ValueError("enable_adaptive: the counts start at iteration 0 (reset_iteration() first)")
+        if self.noise is None:
+            self.enable_noise()
+        if self.counts is None:
+            self.counts = self.ctx.alloc(self.width * self.height * 4)
+            self.counts.zero()
+        self.adaptive = {"target": float(target), "floor": float(floor), "min_samples": int(min_samples), "vote": vote}
+        self.ctx.set_adaptive(self.counts.ptr, **self.adaptive)
+
+    def disable_adaptive(self):
+        self.ctx.set_adaptive(None)
+        if self.counts is not None:
+            self.counts.free()
+            self.counts = None
+        self.adaptive = None
+
+    def _adaptive_or_raise(self):
+        if self.counts is None:
+            raise ValueError("adaptive sampling is off: enable_adaptive() before the first iteration")
+        return self.counts.ptr
+
+    def sample_counts(self):
+        """The iterations folded into every pixel: uint32 [H, W]."""
+        self._adaptive_or_raise()
+        return self.counts.to_numpy(np.uint32, (self.height, self.width))
+
+    def adaptive_summary(self):
+        """{pixels, live_next, above, nonfinite, total_samples, min_count, max_count,
+        max_rel_err} of the frame (rt_adaptive_summarize): every pixel's error with its own
+        count; live_next = the pixels the next render would sample."""
+        counts = self._adaptive_or_raise()
+        return self.ctx.adaptive_summary(self._noise_or_raise(), counts, self.width, self.height, self.iteration,
+                                         **self.adaptive)
+
+    def render_adaptive(self, max_samples, batch=16):
+        """Render `batch` iterations at a time (the last batch clipped to max_samples) until
+        no pixel is live any more or max_samples iterations are done.  Returns (iterations,
+        summary); the summary is None when nothing was rendered."""
+        self._adaptive_or_raise()
+        if not self.progressive:
+            raise ValueError("render_adaptive needs progressive rendering (set_samples(.., True))")
+        if batch < 1:
+            raise ValueError("render_adaptive: batch must be at least 1")
+        summary = None
+        while self.iteration < max_samples:
+            self.render(min(int(batch), int(max_samples) - self.iteration))
+            summary = self.adaptive_summary()
+            if summary["live_next"] == 0:
+                break
         return self.iteration, summary
 
     def frame(self):

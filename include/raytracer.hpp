@@ -207,6 +207,20 @@ public:
     uint32_t render_until(float target, uint32_t max_samples, uint32_t batch = 16, double allow = 0.0,
                           float floor = 1e-3f, rt_noise_summary* summary = nullptr);
 
+    /* Adaptive sampling (rt.h "adaptive sampling"): from iteration 0 on, every render traces
+     * and folds only the pixels that have not converged -- a pixel (RT_ADAPT_PIXEL) or its 8x8
+     * tile (RT_ADAPT_TILE) stops once it has min_samples iterations and its relative standard
+     * error is at most target (rt_set_adaptive).  Enables the noise estimate if needed; the
+     * count buffer is reallocated by load_scene.  As for the noise estimate: every adaptive
+     * call throws on a tiled state, and set_tiling throws once this is enabled. */
+    void enable_adaptive(float target, float floor = 1e-3f, uint32_t min_samples = 16, int vote = RT_ADAPT_TILE);
+    std::vector<uint32_t> sample_counts() const;   /* the iterations folded into every pixel, H x W */
+    rt_adaptive_summary adaptive_summary() const;
+    /* Render `batch` iterations at a time (the last batch clipped to max_samples) until no pixel
+     * is live any more or max_samples iterations are done.  Returns the iteration count;
+     * *summary (if given) receives the last summary (zeroed when nothing was rendered). */
+    uint32_t render_adaptive(uint32_t max_samples, uint32_t batch = 16, rt_adaptive_summary* summary = nullptr);
+
     std::vector<float> frame() const;        /* linear RGBA32F accumulation, H x W x 4 */
     std::vector<uint32_t> hit_ids() const;   /* primary-hit triangle ids, H x W */
     /* the sRGB surface frame, H x W x 4 (rt_frame_rgba8_mode: W1E2 and W1E3 without the pow) */
@@ -244,6 +258,10 @@ private:
     void* tile_accum_ = nullptr;       // this rank's packed tiles (rt_render_tiles)
     void* tile_ids_ = nullptr;
     void* noise_ = nullptr;            // enable_noise: width x height rt_noise_state
+    void* counts_ = nullptr;           // enable_adaptive: width x height uint32 sample counts
+    float ad_target_ = 0.0f, ad_floor_ = 1e-3f;
+    uint32_t ad_min_ = 16;
+    int ad_vote_ = RT_ADAPT_TILE;
 };
 
 }  // namespace raytracer

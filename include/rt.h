@@ -615,6 +615,105 @@ int rt_noise_map(rt_ctx* ctx, const rt_noise_state* state_dev, uint32_t npix, ui
 int rt_noise_summarize(rt_ctx* ctx, const rt_noise_state* state_dev, uint32_t npix, uint32_t n,
                        float threshold, float floor, rt_noise_summary* out);
 
+/* ---- adaptive sampling of the path modes (DESIGN.md section 4 "Adaptive sampling") ----
+ * With a per-slot sample-count buffer set, a path-mode render traces and folds only the
+ * output slots that are still LIVE; a frozen slot keeps its accumulation, primary id,
+ * noise state and count untouched.  No reference counterpart.
+ * State per output slot, indexed exactly as accum_rgba32f: the rt_noise_state of the noise
+ * buffer (which must be set) and a uint32 count, the iterations folded into the slot.
+ * The live set is decided ONCE per rt_render / rt_render_tiles call, at its start, from
+ * the state and the counts the previous calls left -- never per pass, so it does not
+ * depend on RT_OPT_SAMPLE_BUDGET_MB, the chunk size, the unit order or a probe launch.
+ * For a call (first_iter, spp):
+ *   first_iter == 0: every valid slot is live; its state and count restart.
+ *   first_iter > 0:  a valid slot WANTS MORE iff all of
+ *       count == first_iter        it took part in every call so far (a slot that fell
+ *                                  behind is frozen for good);
+ *       its state is finite        (Welford keeps a NaN: no further sample repairs it; the
+ *                                  slot stays reported as non-finite);
+ *       first_iter < min_samples, or rel > target, rel being the relative standard error
+ *                                  pinned above with n = first_iter and this floor, and the
+ *                                  same strict > as rt_noise_summarize's "above".
+ *   vote RT_ADAPT_PIXEL: a slot is live iff it wants more.
+ *   vote RT_ADAPT_TILE:  a valid slot is live iff its count == first_iter and any slot of
+ *       its 8x8 tile wants more.  The tile is the launch's pixel slots 64 t .. 64 t + 63 (one
+ *       wave of the kernels: in region mode the 8x8 tiles of the region from its corner, in
+ *       tileset mode the packed tile).  A frozen tile stays frozen.  This guards against
+ *       the bias of stopping per pixel: a pixel whose first min_samples samples happened to
+ *       agree (a dark pixel that a rare bright path reaches) shows no variance yet and
+ *       would be frozen too dark; its neighbours, which see the same light, keep it alive.
+ *   After the call every live slot has count = first_iter + spp.
+ * Invariant: after any sequence of adaptive calls each valid slot p holds, bit for bit, the
+ * accumulation, primary id and noise state a uniform render of count[p] iterations gives it
+ * (the sample seed is tea16(pixel, iteration) and the average is sequential per pixel).
+ * Work: the BSP walk's k_path deals work units for the live slots only (the ascending list
+ * of live slots that are not flagged by RT_OPT_EMPTY_PIXELS); with no such slot it is not
+ * launched.  Two cases take no list -- the BVH walk, and W7E3 on the BSP walk under
+ * RT_BSP_CULL_FAST or RT_BSP_CULL_OFF (its fast-margin kernel sits on its register budget):
+ * there k_path traces every slot as without the buffer and the fold skips the slots that
+ * are not live.  The frame is the same; no time is saved (rt_adaptive_in_use tells).
+ * With the buffer set, rt_last_counts reports the rays actually traced (nothing is added
+ * for the pixels RT_OPT_EMPTY_PIXELS flags) and rt_last_elided_primaries counts the flagged
+ * pixels that are live only. */
+#define RT_ADAPT_PIXEL 0
+#define RT_ADAPT_TILE 1
+
+typedef struct rt_adaptive_summary {
+    uint64_t pixels;         /* width * height */
+    uint64_t live_next;      /* the slots that would be live in a call with first_iter = iteration */
+    uint64_t above;          /* finite slots with count >= 2 and rel (n = count) > target */
+    uint64_t nonfinite;      /* slots with a non-finite state or count < 2 */
+    uint64_t total_samples;  /* the sum of the counts */
+    float max_rel_err;       /* the largest rel of the finite slots (0 when there is none) */
+    uint32_t min_count, max_count;
+    uint32_t reserved;       /* 0 */
+} rt_adaptive_summary;
+
+/* count_dev: DEVICE, indexed as accum_rgba32f (rt_render_tiles' packed layout included:
+ * padding slots are neither read nor written), 4-byte aligned; NULL: off (the default; a
+ * render then issues exactly the launches it issues without this call).  RT_E_INVALID for
+ * min_samples < 2, a target that is negative or NaN, a floor that is not > 0, a vote that is
+ * neither RT_ADAPT_PIXEL nor RT_ADAPT_TILE, or a misaligned pointer (the parameters are
+ * not checked when count_dev is NULL).  A path-mode render with the buffer set and no noise
+ * buffer returns RT_E_NOT_READY, and together with RT_OPT_ASYNC_FOLD RT_E_UNSUPPORTED (the
+ * live set is read back on the context stream).  Such a render synchronizes the context
+ * stream once, at its start.  Every other mode ignores the buffer. */
+int rt_set_adaptive(rt_ctx* ctx, uint32_t* count_dev, float target, float floor, uint32_t min_samples, int vote);
+
+/* The fused fold over caller-supplied DEVICE records (rt_noise_accumulate's layouts and
+ * alignment; accum_dev 16-byte, state_dev 8-byte, count_dev 4-byte aligned): for every
+ * pixel i < npix with live_dev[i] != 0 (one byte per pixel), the progressive average of
+ * rt_render into accum_dev[i], the primary id (the record's w bits) of the last iteration
+ * into ids_dev[i] (or NULL), the noise update into state_dev[i] and, when last_pass is
+ * non-zero, count_dev[i] = first_iter + spp.  first_iter == 0 starts from zero, else the
+ * stored accumulation and state continue.  Every other pixel keeps what the four buffers
+ * held.  npix == 0 or spp == 0: no-op.  Asynchronous on the context stream. */
+int rt_adaptive_accumulate(rt_ctx* ctx, const float* samples_rgba_dev, uint32_t npix, uint32_t spp, int pixel_major,
+                           uint32_t first_iter, int last_pass, const uint8_t* live_dev, float* accum_dev,
+                           uint32_t* ids_dev, rt_noise_state* state_dev, uint32_t* count_dev);
+
+/* rel_dev[i] (DEVICE, npix floats) = rel of state_dev[i] with n = count_dev[i]; the quiet NaN
+ * 0x7FC00000 for a non-finite state or a count < 2.  Asynchronous on the context stream. */
+int rt_adaptive_map(rt_ctx* ctx, const rt_noise_state* state_dev, const uint32_t* count_dev, uint32_t npix,
+                    float floor, float* rel_dev);
+
+/* The summary of a row-major width x height frame (a full-region rt_render's buffers) into
+ * *out (host; synchronizes): every rel with n = the slot's own count; live_next by the rule
+ * above for a call that starts at `iteration`, with the 8x8 tiles of the frame.
+ * Deterministic: integer sums and integer maxima of bit patterns.  Arguments as
+ * rt_set_adaptive's. */
+int rt_adaptive_summarize(rt_ctx* ctx, const rt_noise_state* state_dev, const uint32_t* count_dev, uint32_t width,
+                          uint32_t height, uint32_t iteration, float target, float floor, uint32_t min_samples,
+                          int vote, rt_adaptive_summary* out);
+
+/* The most recent path-mode render with the count buffer set: *live_slots (or NULL) the
+ * slots that were live, *dealt_slots (or NULL) the slots k_path dealt work units for (the
+ * live ones that RT_OPT_EMPTY_PIXELS does not flag when it took the list; every slot of the
+ * launch in the two fallback cases; 0 when it was not launched), *took_list (or NULL) 1
+ * when k_path ran from the list (or was not launched because the list was empty), 0 in a
+ * fallback case.  All 0 when the most recent render did not use the buffer. */
+int rt_adaptive_in_use(rt_ctx* ctx, uint64_t* live_slots, uint64_t* dealt_slots, int* took_list);
+
 /* ---- multi-GPU: the tile gather over RCCL -----------------
  * One process per GPU, each with its own context: every rank renders its
  * interleaved tiles (rt_render_tiles with rt_tileset {rank, nranks}), then
@@ -696,7 +795,8 @@ typedef struct rt_ray_hit {
 int rt_trace_rays(rt_ctx* ctx, rt_traverse trav, const float* rays, const uint32_t* flags, uint32_t n,
                   rt_ray_hit* hits);
 
-/* Counters of the most recent launch (synchronizes). */
+/* Counters of the most recent launch (synchronizes).  With rt_set_adaptive's buffer set: the
+ * rays actually traced. */
 int rt_last_counts(rt_ctx* ctx, rt_ray_counts* counts);
 
 /* Shadow rays of the most recent launch that the path kernel resolved at shading
@@ -712,7 +812,9 @@ int rt_last_elided_shadows(rt_ctx* ctx, uint64_t* elided);
 /* Camera rays of the most recent render that RT_OPT_EMPTY_PIXELS did not cast: its
  * flagged pixels x its iterations.  They stay counted in rt_ray_counts.primary and
  * .samples (the rays the reference's shader casts), so primary - elided is what walked
- * the mesh.  Host arithmetic: filled with or without RT_OPT_DETAIL_COUNTERS. */
+ * the mesh.  Host arithmetic: filled with or without RT_OPT_DETAIL_COUNTERS.  With
+ * rt_set_adaptive's buffer set: the flagged pixels that are live x the iterations, and they
+ * are not added to rt_ray_counts. */
 int rt_last_elided_primaries(rt_ctx* ctx, uint64_t* elided);
 
 /* Device-vs-host self check of the pinned f32 math (sqrt, division, the
