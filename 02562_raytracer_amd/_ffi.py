@@ -39,6 +39,8 @@ RT_OPT_BSP_CULL = 9
 RT_OPT_ASYNC_FOLD = 10
 RT_OPT_EMPTY_PIXELS = 11   # 0 off, 1 on (default), 2 on and built at the first render
 RT_OPT_PIXEL_DEPTH = 12    # 0 off, 1 on (default): camera rays start on their pixel's certified depth range
+RT_OPT_DENOISE_LDS_STEP = 13   # the largest step whose denoise level stages its tile in LDS: 0, 1, 2, 4 or 8
+RT_OPT_DENOISE_LATTICE_STEP = 14   # the smallest step that runs the lattice form: 0 (never, default), 2, 4, 8 or 16
 RT_BSP_CULL_OFF, RT_BSP_CULL_CERTIFIED, RT_BSP_CULL_FAST, RT_BSP_CULL_SILHOUETTE, RT_BSP_CULL_AUTO = range(5)
 BSP_TREELET_BYTES = 96   # rt_internal.h: the BSP walk's treelet (rt_download_bsp_treelets)
 RT_OPT_KERNEL_TIMING = 7
@@ -226,6 +228,13 @@ SIGNATURES = {
     "rt_adaptive_summarize": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
                                         C.c_uint32, C.c_int, C.POINTER(AdaptiveSummary)]),
     "rt_adaptive_in_use": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "rt_denoise_guide": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp]),
+    "rt_denoise_variance": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, vp]),
+    "rt_denoise_filter": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_float, C.c_float, vp,
+                                    vp]),
+    "rt_denoise": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
+                             vp]),
+    "rt_denoise_level_times": (C.c_int, [vp, f32p, u32p]),
     "rt_unpack_tiles": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "rt_comm_unique_id": (C.c_int, [vp]),
     "rt_comm_init": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),

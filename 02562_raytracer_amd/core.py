@@ -490,6 +490,41 @@ class Context:
         self._chk(F.lib().rt_adaptive_in_use(self._h, C.byref(live), C.byref(dealt), C.byref(took)))
         return {"live": int(live.value), "dealt": int(dealt.value), "list": bool(took.value)}
 
+    # ---- the denoise filter (include/rt.h "denoise"; device pointers, asynchronous)
+    def denoise_guide(self, width, height, ids_ptr, nz_ptr, dz_ptr):
+        """rt_denoise_guide: {N, z} (float4) and {dzx, dzy} (float2) per pixel from the primary ids,
+        the uploaded mesh and the current uniforms."""
+        self._chk(F.lib().rt_denoise_guide(self._h, width, height, C.c_void_p(ids_ptr), C.c_void_p(nz_ptr),
+                                           C.c_void_p(dz_ptr)))
+
+    def denoise_variance(self, state_ptr, count_ptr, npix, n, var_ptr):
+        """rt_denoise_variance: the variance of the mean luminance per slot, with the slot's own
+        count (count_ptr) or n iterations (count_ptr None)."""
+        self._chk(F.lib().rt_denoise_variance(self._h, C.c_void_p(state_ptr), C.c_void_p(count_ptr) if count_ptr else None,
+                                              npix, n, C.c_void_p(var_ptr)))
+
+    def denoise_filter(self, width, height, color_ptr, var_ptr, nz_ptr, dz_ptr, out_color_ptr, out_var_ptr=None,
+                       levels=5, sigma_l=4.0, sigma_z=1.0):
+        """rt_denoise_filter: `levels` a-trous levels over colour and variance with the guide."""
+        self._chk(F.lib().rt_denoise_filter(self._h, width, height, C.c_void_p(color_ptr), C.c_void_p(var_ptr),
+                                            C.c_void_p(nz_ptr), C.c_void_p(dz_ptr), int(levels), float(sigma_l),
+                                            float(sigma_z), C.c_void_p(out_color_ptr),
+                                            C.c_void_p(out_var_ptr) if out_var_ptr else None))
+
+    def denoise(self, width, height, accum_ptr, ids_ptr, state_ptr, count_ptr, n, out_ptr, levels=5, sigma_l=4.0,
+                sigma_z=1.0):
+        """rt_denoise: guide, variance and filter of a rendered frame on the context's scratch."""
+        self._chk(F.lib().rt_denoise(self._h, width, height, C.c_void_p(accum_ptr), C.c_void_p(ids_ptr),
+                                     C.c_void_p(state_ptr), C.c_void_p(count_ptr) if count_ptr else None, int(n),
+                                     int(levels), float(sigma_l), float(sigma_z), C.c_void_p(out_ptr)))
+
+    def denoise_level_times(self):
+        """rt_denoise_level_times: ([ms per level], [form per level: 0 direct, 1 LDS tile, 2 lattice])
+        of the most recent filter (RT_OPT_KERNEL_TIMING); synchronizes."""
+        ms, form = (C.c_float * 5)(), (C.c_uint32 * 5)()
+        self._chk(F.lib().rt_denoise_level_times(self._h, ms, form))
+        return [float(x) for x in ms], [int(x) for x in form]
+
     # ---- the tile gather over RCCL (include/rt.h "multi-GPU")
     @staticmethod
     def comm_unique_id():

@@ -1,5 +1,5 @@
 // rt_internal.h -- launch interface between the C ABI layer (rt_api.cpp) and
-// the gfx950 kernels (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip, rt_noise.hip),
+// the gfx950 kernels (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip, rt_noise.hip, rt_denoise.hip),
 // and what the launchers of the flat modes share: their grid and the expansion of a
 // run-time (mode, detail) into template constants.  Not part of the public ABI.
 #pragma once
@@ -257,6 +257,30 @@ int launch_adaptive_map(const rt_noise_state* state, const uint32_t* count, uint
 // l.first_iter the iteration whose live set is counted
 int launch_adaptive_summary(const DevLaunch& l, const rt_noise_state* state, const uint32_t* count,
                             const AdaptParams& p, unsigned long long* stats, hipStream_t stream);
+
+// The a-trous filter (rt_denoise.hip; rt.h "denoise").  DenoiseCam: camera_basis's terms and
+// the frame the pixel-centre rays are for.
+struct DenoiseCam {
+    float cam[14];
+    uint32_t w, h;
+};
+// nz: w x h float4 {N, z}, dz: w x h float2 {dzx, dzy}, from the primary ids and the mesh
+int launch_denoise_guide(const DenoiseCam& g, const float4* pos, const uint4* tri_idx, uint32_t ntris,
+                         const uint32_t* ids, float* nz, float* dz, hipStream_t stream);
+// var[i] = the variance of state[i]'s mean after count[i] (or, count null, n) iterations; 0x7FC00000: unfilterable
+int launch_denoise_variance(const rt_noise_state* state, const uint32_t* count, uint32_t npix, uint32_t n, float* var,
+                            hipStream_t stream);
+// cv[i] = {color[i].rgb, var[i]}
+int launch_denoise_pack(const float* color, const float* var, uint32_t npix, float* cv, hipStream_t stream);
+// One level at `step` from cv ({rgb, v}) into out_cv, or on the last level (out_cv null) into
+// out_color ({rgb, 1}) and out_var (or null).  form: every tap from global memory; the block's
+// tile and its halo staged in LDS (step <= DENOISE_LDS_MAX_STEP); or a block per 16 x 16 lattice
+// of stride step, a 20 x 20 tile at every step.  All three give the same bits
+enum { DENOISE_FORM_DIRECT = 0, DENOISE_FORM_LDS = 1, DENOISE_FORM_LATTICE = 2 };
+constexpr uint32_t DENOISE_LDS_MAX_STEP = 8;   // (16 + 4 s)^2 x 32 B: 73 KiB at 8, 204 KiB at 16
+int launch_denoise_level(const float* cv, const float* nz, const float* dz, uint32_t w, uint32_t h, uint32_t step,
+                         float sigma_l, float sigma_z, int form, float* out_cv, float* out_color, float* out_var,
+                         hipStream_t stream);
 
 // display frame: RGBA32F accum -> 8-bit sRGB (thr: 255 device floats, srgb_code_thresholds)
 int launch_frame(const float4* accum, uint32_t npix, const float* thr, uchar4* out, hipStream_t stream);

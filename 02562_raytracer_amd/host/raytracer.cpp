@@ -713,6 +713,53 @@ std::vector<uint8_t> RenderState::frame_rgba8() const
     return out;
 }
 
+// the denoised frame on the device (the caller frees it)
+void* RenderState::denoise_device(uint32_t levels, float sigma_l, float sigma_z) const
+{
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, "denoise is for an untiled state: the filter needs every pixel's neighbours, and a tiled render (set_tiling, any rank count) keeps its buffers packed per tile");
+    if (!writes_records(mode_)) throw Error(RT_E_UNSUPPORTED, "denoise: the mode keeps no noise state");
+    if (!noise_) throw Error(RT_E_NOT_READY, "denoise: enable_noise() first");
+    if (iteration_ < 2) throw Error(RT_E_INVALID, "denoise: the variance needs at least 2 rendered iterations");
+    if (levels < 1 || levels > 5 || !(sigma_l > 0.0f) || !(sigma_z > 0.0f))
+        throw Error(RT_E_INVALID, "denoise: levels in 1..5, sigmas > 0");
+    const size_t npx = (size_t)width_ * height_;
+    void* d = nullptr;
+    gpu_.check(rt_device_alloc(gpu_.ctx(), npx * 16, &d), "denoise buffer");
+    const int rc = rt_denoise(gpu_.ctx(), width_, height_, static_cast<const float*>(accum_),
+                              static_cast<const uint32_t*>(ids_), static_cast<const rt_noise_state*>(noise_),
+                              static_cast<const uint32_t*>(counts_), iteration_, levels, sigma_l, sigma_z,
+                              static_cast<float*>(d));
+    if (rc != RT_OK) rt_device_free(gpu_.ctx(), d);
+    gpu_.check(rc, "denoise");
+    return d;
+}
+
+std::vector<float> RenderState::denoise(uint32_t levels, float sigma_l, float sigma_z) const
+{
+    void* d = denoise_device(levels, sigma_l, sigma_z);
+    std::vector<float> out((size_t)width_ * height_ * 4);
+    const int rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), d, out.size() * 4);
+    rt_device_free(gpu_.ctx(), d);
+    gpu_.check(rc, "denoise");
+    return out;
+}
+
+std::vector<uint8_t> RenderState::denoised_rgba8(uint32_t levels, float sigma_l, float sigma_z) const
+{
+    void* d = denoise_device(levels, sigma_l, sigma_z);
+    const size_t npx = (size_t)width_ * height_;
+    void* img = nullptr;
+    int rc = rt_device_alloc(gpu_.ctx(), npx * 4, &img);
+    std::vector<uint8_t> out(npx * 4);
+    if (rc == RT_OK)
+        rc = rt_frame_rgba8_mode(gpu_.ctx(), mode_, static_cast<const float*>(d), (uint32_t)npx, static_cast<uint8_t*>(img));
+    if (rc == RT_OK) rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), img, out.size());
+    rt_device_free(gpu_.ctx(), img);
+    rt_device_free(gpu_.ctx(), d);
+    gpu_.check(rc, "denoised_rgba8");
+    return out;
+}
+
 rt_ray_counts RenderState::last_counts() const
 {
     rt_ray_counts c;

@@ -28,6 +28,14 @@
 //                                        max_rel_err}, and --out writes PREFIX.count.u32, the H*W
 //                                        sample counts; refused with --comm-file / --nranks and
 //                                        with --noise-target)
+//             [--denoise [--denoise-levels L] [--denoise-sigma-l S] [--denoise-sigma-z Z]]
+//                                        (a path-mode scene with at least 2 iterations: the frame
+//                                        through the variance-guided a-trous filter, rt_denoise --
+//                                        L (5) levels, luminance and depth tolerances S (4) and Z (1);
+//                                        enables the noise estimate if no other flag did; --out
+//                                        also writes PREFIX.denoised.f32 (H*W*4 float32) and
+//                                        PREFIX.denoised.rgba8 (its sRGB frame); refused with
+//                                        --comm-file / --nranks)
 //   rt_render ... --nranks N --rank R --comm-file PATH [--comm-token T] [--device D]
 //                                        (one process per GPU: rank R renders its
 //                                        interleaved tiles, rank 0 gathers the frame
@@ -254,6 +262,23 @@ int main(int argc, char** argv)
                         "--adaptive-target / --adaptive-min / --adaptive-vote do not go with --comm-file / --nranks (a tiled render)");
         if (adaptive && !arg("--adaptive-target")) throw Error(RT_E_INVALID, "--adaptive-min / --adaptive-vote need --adaptive-target T");
         if (adaptive && arg("--noise-target")) throw Error(RT_E_INVALID, "--adaptive-target does not go with --noise-target");
+        // the denoise filter needs every pixel's neighbours and a noise state: an untiled render of a path mode
+        const bool denoise = flag("--denoise");
+        if (!denoise && (arg("--denoise-levels") || arg("--denoise-sigma-l") || arg("--denoise-sigma-z")))
+            throw Error(RT_E_INVALID, "--denoise-levels / --denoise-sigma-l / --denoise-sigma-z need --denoise");
+        if (denoise && (nranks > 1 || arg("--comm-file")))
+            throw Error(RT_E_UNSUPPORTED, "--denoise does not go with --comm-file / --nranks (a tiled render)");
+        const uint32_t dn_levels = arg("--denoise-levels") ? (uint32_t)std::atoi(arg("--denoise-levels")->c_str()) : 5u;
+        const float dn_sigma_l = arg("--denoise-sigma-l") ? (float)std::atof(arg("--denoise-sigma-l")->c_str()) : 4.0f;
+        const float dn_sigma_z = arg("--denoise-sigma-z") ? (float)std::atof(arg("--denoise-sigma-z")->c_str()) : 1.0f;
+        if (denoise) {
+            if (dn_levels < 1 || dn_levels > 5 || !(dn_sigma_l > 0.0f) || !(dn_sigma_z > 0.0f))
+                throw Error(RT_E_INVALID, "--denoise-levels in 1..5, --denoise-sigma-l and --denoise-sigma-z > 0");
+            const std::optional<rt_mode> m = find_scene(*name).mode();
+            const bool path = m && (*m == RT_MODE_W7E3 || *m == RT_MODE_W9E1 || *m == RT_MODE_W8E1 || *m == RT_MODE_W8E2 ||
+                                    *m == RT_MODE_W8E3 || *m == RT_MODE_W9E2 || *m == RT_MODE_W9E3);
+            if (!path) throw Error(RT_E_UNSUPPORTED, "--denoise: the scene's mode keeps no noise state (a path mode only)");
+        }
         int vote = RT_ADAPT_TILE;
         if (const std::string* v = arg("--adaptive-vote")) {
             if (*v == "pixel") vote = RT_ADAPT_PIXEL;
@@ -307,6 +332,8 @@ int main(int argc, char** argv)
         } else {
             rs.update();
         }
+        // --denoise: the noise estimate from iteration 0 on, unless --noise-target / --adaptive-target enable it
+        if (denoise && !arg("--noise-target") && !arg("--adaptive-target")) rs.enable_noise();
         uint32_t frames = 0;
         std::string noise_json;
         if (const std::string* t = arg("--noise-target")) {   // render until converged (render_until)
@@ -370,6 +397,12 @@ int main(int argc, char** argv)
             write_file(*out + ".accum.f32", f.data(), f.size() * 4);
             write_file(*out + ".ids.u32", ids.data(), ids.size() * 4);
             write_file(*out + ".rgba8", rgba.data(), rgba.size());
+            if (denoise) {
+                const auto df = rs.denoise(dn_levels, dn_sigma_l, dn_sigma_z);
+                const auto drgba = rs.denoised_rgba8(dn_levels, dn_sigma_l, dn_sigma_z);
+                write_file(*out + ".denoised.f32", df.data(), df.size() * 4);
+                write_file(*out + ".denoised.rgba8", drgba.data(), drgba.size());
+            }
         }
         std::printf("{\"scene\":%s,\"mode\":%s,\"width\":%u,\"height\":%u,\"iteration\":%u,\"frames\":%u,"
                     "\"last_launch\":{\"samples\":%llu,\"primary\":%llu,\"shadow\":%llu,\"bounce\":%llu},\"camera\":%s%s}\n",

@@ -343,6 +343,53 @@ class RenderState:
                 break
         return self.iteration, summary
 
+    # ---- the denoise filter (include/rt.h "denoise"; single process, no tiles)
+    def _denoise_check(self, levels, sigma_l, sigma_z):
+        """(no device: the checks come before any allocation)"""
+        if self.mode not in F.NOISE_MODES:
+            raise ValueError(f"{self.mode} keeps no noise state: the denoise filter follows {', '.join(F.NOISE_MODES)}")
+        self._noise_or_raise()
+        if self.iteration < 2:
+            raise ValueError("denoise: the variance needs at least 2 rendered iterations")
+        if not 1 <= int(levels) <= 5:
+            raise ValueError("denoise: levels must be in 1..5")
+        if not (float(sigma_l) > 0.0 and float(sigma_z) > 0.0):
+            raise ValueError("denoise: the sigmas must be > 0")
+
+    def _denoise_into(self, out, levels, sigma_l, sigma_z):
+        state = self._noise_or_raise()
+        counts = self.counts.ptr if self.counts is not None else None
+        self.ctx.denoise(self.width, self.height, self.accum.ptr, self.ids.ptr, state, counts, self.iteration, out.ptr,
+                         levels=levels, sigma_l=sigma_l, sigma_z=sigma_z)
+
+    def denoise(self, levels=5, sigma_l=4.0, sigma_z=1.0):
+        """The frame through the variance-guided a-trous filter (rt_denoise): float32 [H, W, 4],
+        alpha 1.  Needs enable_noise() from iteration 0 and at least 2 iterations; with adaptive
+        sampling every pixel's variance uses its own sample count.  The accumulation, the ids and
+        the noise state are not changed."""
+        self._denoise_check(levels, sigma_l, sigma_z)
+        out = self.ctx.alloc(self.width * self.height * 16)
+        try:
+            self._denoise_into(out, levels, sigma_l, sigma_z)
+            return out.to_numpy(np.float32, (self.height, self.width, 4))
+        finally:
+            out.free()
+
+    def denoised_rgba8(self, levels=5, sigma_l=4.0, sigma_z=1.0):
+        """The denoised frame as the sRGB surface would hold it: uint8 [H, W, 4]
+        (rt_frame_rgba8_mode of denoise())."""
+        self._denoise_check(levels, sigma_l, sigma_z)
+        npx = self.width * self.height
+        out = self.ctx.alloc(npx * 16)
+        img = self.ctx.alloc(npx * 4)
+        try:
+            self._denoise_into(out, levels, sigma_l, sigma_z)
+            self.ctx.frame_rgba8(out.ptr, npx, img.ptr, mode=self.mode)
+            return img.to_numpy(np.uint8, (self.height, self.width, 4))
+        finally:
+            out.free()
+            img.free()
+
     def frame(self):
         """Linear accumulation [H, W, 4] float32 (the RenderDestination texture)."""
         return self.accum.to_numpy(np.float32, (self.height, self.width, 4))

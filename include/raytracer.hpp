@@ -221,6 +221,15 @@ public:
      * *summary (if given) receives the last summary (zeroed when nothing was rendered). */
     uint32_t render_adaptive(uint32_t max_samples, uint32_t batch = 16, rt_adaptive_summary* summary = nullptr);
 
+    /* The frame through the variance-guided a-trous filter (rt.h "denoise", rt_denoise): linear
+     * RGBA32F, H x W x 4, alpha 1.  Needs enable_noise() and iteration() >= 2; under adaptive
+     * sampling every pixel's variance uses its own sample count.  The accumulation, the ids and
+     * the noise state are not changed.  Throws for a mode without a noise state and on a tiled
+     * state (the filter needs every pixel's neighbours). */
+    std::vector<float> denoise(uint32_t levels = 5, float sigma_l = 4.0f, float sigma_z = 1.0f) const;
+    /* ... as the sRGB surface would hold it, H x W x 4 (rt_frame_rgba8_mode of denoise()) */
+    std::vector<uint8_t> denoised_rgba8(uint32_t levels = 5, float sigma_l = 4.0f, float sigma_z = 1.0f) const;
+
     std::vector<float> frame() const;        /* linear RGBA32F accumulation, H x W x 4 */
     std::vector<uint32_t> hit_ids() const;   /* primary-hit triangle ids, H x W */
     /* the sRGB surface frame, H x W x 4 (rt_frame_rgba8_mode: W1E2 and W1E3 without the pow) */
@@ -237,6 +246,7 @@ public:
 private:
     void setup_rendering(const SceneDescriptor& scene);   /* :161-265 */
     void release();
+    void* denoise_device(uint32_t levels, float sigma_l, float sigma_z) const;
 
     GpuHandles& gpu_;
     RenderOptions opts_;

@@ -275,6 +275,12 @@ typedef struct rt_ray_counts {
                                      hit (DESIGN.md section 4 "Pixel depth ranges"): accum, ids, the noise state and
                                      rt_ray_counts are the same bits as with 0.  Bounce rays are untouched, and with
                                      RT_BSP_CULL_OFF the walk keeps the reference's interval */
+#define RT_OPT_DENOISE_LDS_STEP 13 /* the largest step 2^i at which a level of the denoise filter stages its tile and
+                                     halo in LDS; larger steps load every tap from global memory.  0 (never), 1, 2,
+                                     4 or 8 (default 4: DESIGN.md section 4 "Denoise"); every form gives the same bits */
+#define RT_OPT_DENOISE_LATTICE_STEP 14 /* the smallest step from which a level runs the lattice form instead (a block per
+                                     16 x 16 lattice of stride 2^i, a 20 x 20 LDS tile at every step): 0 (never, the
+                                     default: it measured slower), 2, 4, 8 or 16; it takes precedence over the above */
 
 /* ---- device / context (replaces src/gpu_handles.rs) -------------------- */
 
@@ -713,6 +719,100 @@ int rt_adaptive_summarize(rt_ctx* ctx, const rt_noise_state* state_dev, const ui
  * when k_path ran from the list (or was not launched because the list was empty), 0 in a
  * fallback case.  All 0 when the most recent render did not use the buffer. */
 int rt_adaptive_in_use(rt_ctx* ctx, uint64_t* live_slots, uint64_t* dealt_slots, int* took_list);
+
+/* ---- denoise: a variance-guided a-trous filter (DESIGN.md section 4 "Denoise") ----
+ * An edge-avoiding a-trous wavelet filter (the spatial half of SVGF) over a row-major
+ * width x height frame, guided by the variance the noise estimate keeps and by the geometry
+ * under each pixel.  No reference counterpart; off unless called.  Pinned f32 arithmetic (no
+ * contraction, correctly rounded / and sqrt), every line below one operation, sums left to
+ * right; max(a, 0) is (a > 0 ? a : 0), which also sends a NaN to 0; |a| clears the sign bit;
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.
+ *
+ * Variance (rt_denoise_variance).  With cnt = count[p] (or the call's n without counts) and
+ * nf = (float)cnt:
+ *     v = (m2 < 0 ? 0 : m2) / (nf * (nf - 1.0f))          the variance of the mean luminance
+ * and v = the quiet NaN 0x7FC00000 when cnt < 2 or a field of the state is not finite.
+ *
+ * Filterable.  At every level a pixel is FILTERABLE iff its three colour components and its v
+ * are finite and v is not negative; else it is unfilterable.  As a centre an unfilterable pixel
+ * is copied through, colour and v unchanged, at every level; as a tap it has weight 0.
+ *
+ * Guide (rt_denoise_guide).  The camera is the uniforms' (get_camera_ray, w7e3.wgsl:211-228):
+ *     v = normalize(look_at - pos); b1 = normalize(cross(v, up)); b2 = cross(b1, v)
+ *     ux = ((float)x + 0.5f) / (float)width - 0.5f;  uy = 0.5f - ((float)y + 0.5f) / (float)height
+ *     w(x, y) = normalize(((b1 * (ux + 0.0f)) * aspect + b2 * (uy + 0.0f)) + v * camera_constant)
+ * the pixel-centre ray (e, w), e = camera_pos; normalize(a) = a / sqrtf(dot(a, a)).  For the
+ * triangle id = ids[p] with vertices v0, v1, v2:
+ *     e0 = v1 - v0; e1 = v2 - v0; g = normalize(cross(e0, e1)); if (dot(g, w) > 0) g = -g
+ *     den = dot(w, g); num = dot(v0 - e, g); z = num / den
+ *     dzx = num / dot(w(x+1, y), g) - z;  dzy = num / dot(w(x, y+1), g) - z
+ * (the neighbour's ray is computed as written even when it lies outside the frame); a dzx or
+ * dzy that is not finite becomes 0.  The pixel is BACKGROUND when id is 0xFFFFFFFF or >= ntris,
+ * den == 0, or z is not finite or <= 0: then N = 0, z = -1, dz = 0.  Else N = g.
+ * rt_denoise_filter takes any guide: a pixel is background iff !(z > 0).
+ *
+ * One level i = 0 .. levels-1 (1 <= levels <= 5) has step s = 2^i, reads the previous level's
+ * colour c and variance v (level 0: the inputs) and the same guide, and for a filterable p:
+ *   1. sk = sv = 0; for dy = -1..1, dx = -1..1 (dy outer), q = p + (dx, dy) inside the frame
+ *      and filterable:  k = ((float)(2-|dy|) * (float)(2-|dx|)) / 16.0f;  sk = sk + k;
+ *      sv = sv + k * v_q.   sd = sqrtf(sv / sk)              (the centre counts: sk >= 1/4)
+ *   2. h = {1/16, 1/4, 3/8, 1/4, 1/16}; the 25 taps q = p + s*(dx, dy), dy outer, dx inner, both
+ *      -2..2.  A tap outside the frame, unfilterable, or of the other class (background against
+ *      surface) has weight 0 and adds nothing.  The centre tap has w = h[2] * h[2].  Every other:
+ *          d  = dot(N_p, N_q);  wn = max(d, 0), squared seven times (^128)
+ *          gr = dzx_p * (float)(s*dx) + dzy_p * (float)(s*dy)
+ *          xz = |z_p - z_q| / (sigma_z * |gr| + 1e-3f * |z_p|)
+ *          (a background pair: wn = 1, xz = 0)
+ *          l  = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z     (the noise estimate's luminance)
+ *          xl = |l_p - l_q| / (sigma_l * sd + 1e-6f)
+ *          t  = max(1.0f - (xz + xl) * 0.125f, 0), squared three times: E(x) = t^8
+ *          w  = ((h[dy+2] * h[dx+2]) * wn) * E
+ *      E follows exp(-x) (it is (1 - x/8)^8), has compact support (0 from x = 8 on) and needs
+ *      no transcendental.  No weight is NaN: both denominators are positive for a filterable
+ *      pair (sigma_l * sd >= 0 plus 1e-6f; for a surface pixel z_p > 0, so 1e-3f * |z_p| > 0
+ *      unless it underflows -- and then a NaN or infinite x still gives t = 0 by the max).
+ *      Per tap, in order:  sw = sw + w;  sc = sc + w * c_q (per component);  sv = sv + (w*w) * v_q
+ *   3. c' = sc / sw;  v' = sv / (sw * sw).  The last level's output alpha is 1.
+ * Values whose sums overflow keep their class (infinite or NaN), not a NaN's payload.
+ * Defaults of the hosts: levels = 5, sigma_l = 4, sigma_z = 1.
+ *
+ * All four calls are asynchronous on the context stream, take DEVICE pointers, and return
+ * RT_E_INVALID for a null buffer (out_var_dev and count_dev may be NULL), levels outside 1..5,
+ * a sigma that is not > 0, n < 2 without counts, a pointer that is not aligned (16 B for the
+ * float4 buffers, 8 B for states and dz, 4 B otherwise), an output that overlaps an input or
+ * another output, or width * height >= 2^31.  A zero-sized frame is a no-op (RT_OK). */
+
+/* nz_dev: width*height float4 {N.xyz, z}; dz_dev: width*height float2 {dzx, dzy}; from ids_dev
+ * (width*height u32, rt_render's primary_hit_ids), the uploaded mesh and the current uniforms,
+ * whose resolution must be width x height (RT_E_INVALID otherwise).  RT_E_NOT_READY without a
+ * mesh or uniforms. */
+int rt_denoise_guide(rt_ctx* ctx, uint32_t width, uint32_t height, const uint32_t* ids_dev, float* nz_dev,
+                     float* dz_dev);
+
+/* var_dev[i] (npix floats) = v of state_dev[i] with count_dev[i] (or, count_dev NULL, n) iterations. */
+int rt_denoise_variance(rt_ctx* ctx, const rt_noise_state* state_dev, const uint32_t* count_dev, uint32_t npix,
+                        uint32_t n, float* var_dev);
+
+/* `levels` levels over color_dev (float4: rgb, w ignored) and var_dev into out_color_dev (float4,
+ * alpha 1) and out_var_dev (or NULL).  The levels ping-pong between two buffers of the context
+ * (allocated at the first call, freed with the context). */
+int rt_denoise_filter(rt_ctx* ctx, uint32_t width, uint32_t height, const float* color_dev, const float* var_dev,
+                      const float* nz_dev, const float* dz_dev, uint32_t levels, float sigma_l, float sigma_z,
+                      float* out_color_dev, float* out_var_dev);
+
+/* The three calls above on the context's scratch: the frame rt_render left in accum_dev, ids_dev
+ * and state_dev (the noise buffer) after n iterations -- or count_dev[i] iterations per pixel
+ * under adaptive sampling -- filtered into out_rgba_dev.  The inputs are not written.  The
+ * primary id is the LAST iteration's: the camera ray's jitter stays inside the pixel, so the
+ * id picks one of the surfaces the pixel sees. */
+int rt_denoise(rt_ctx* ctx, uint32_t width, uint32_t height, const float* accum_dev, const uint32_t* ids_dev,
+               const rt_noise_state* state_dev, const uint32_t* count_dev, uint32_t n, uint32_t levels,
+               float sigma_l, float sigma_z, float* out_rgba_dev);
+
+/* With RT_OPT_KERNEL_TIMING: the device time of each level of the most recent rt_denoise_filter
+ * or rt_denoise in milliseconds (level_ms: 5 floats, 0 past its levels) and the form the level
+ * ran (lds_form: 5 uint32, or NULL: 0 every tap from global memory, 1 the LDS tile, 2 the lattice).  Synchronizes.  All 0 when the option was off. */
+int rt_denoise_level_times(rt_ctx* ctx, float* level_ms, uint32_t* lds_form);
 
 /* ---- multi-GPU: the tile gather over RCCL -----------------
  * One process per GPU, each with its own context: every rank renders its
