@@ -1,4 +1,4 @@
-// rt_internal.h -- launch interface between the C ABI layer (rt_api.cpp) and
+// rt_internal.h -- launch interface between the C ABI layer (rt_ctx.h) and
 // the gfx950 kernels (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip, rt_noise.hip, rt_denoise.hip),
 // and what the launchers of the flat modes share: their grid and the expansion of a
 // run-time (mode, detail) into template constants.  Not part of the public ABI.
@@ -23,7 +23,7 @@ struct DevScene {
     const rt_material* mats;
     const uint32_t* lights;
     uint32_t nverts, ntris, nmats, nlights;
-    // BSP: one allocation [96-B treelets | 48-B records] (rt_api.cpp rt_upload_bsp):
+    // BSP: one allocation [96-B treelets | 48-B records] (rt_scene.cpp install_bsp):
     // treelet of 1-based node M at 96*M holds M's content box (min.xyz, max.xyz: the
     // triangles its subtree references), nodes M, 2M, 2M+1, 4M..4M+3 (8 B each:
     // interior {axis, plane bits}, leaf {3 | (48*count) << 2, first record's byte
@@ -37,7 +37,7 @@ struct DevScene {
     uint32_t bsp_depth;           // MAX_LEVEL
     float aabb[6];                // root BboxGpu min.xyz, max.xyz
     // BVH: one allocation [32-B node records | 48-B triangle records in bvh_triangles
-    // order] (rt_api.cpp rt_upload_bvh; links and leaf ranges as byte offsets)
+    // order] (rt_scene.cpp rt_upload_bvh; links and leaf ranges as byte offsets)
     const uint8_t* bvh_base;
     uint32_t bvh_bytes;
     uint32_t bvh_rec_off;

@@ -1,4 +1,4 @@
-"""RT_BSP_CULL_AUTO (rt_api.cpp probe_take / probe_launch / probe_finish; DESIGN.md
+"""RT_BSP_CULL_AUTO (rt_render.cpp probe_take / probe_launch / probe_finish; DESIGN.md
 section 4 "The auto probe"): the W9E1 BSP renders time the certified and the
 silhouette kernels on four of their own launches (certified, silhouette,
 certified, silhouette; each >= 2^20 samples) and run the faster once the probe's
