@@ -7,7 +7,7 @@
 // (tests/test_isa_guard.py).
 //
 // The arithmetic is pinned (f32, no contraction, correctly rounded / and sqrt; the
-// Makefile's NUMFLAGS) and restates k_fold's average (rt_kernels.hip) and k_noise's update
+// Makefile's NUMFLAGS) and restates k_fold's average (rt_stream_kernels.h) and k_noise's update
 // and relative error (rt_noise.hip) operation for operation: a slot that took part in n
 // iterations holds the bits a uniform n-iteration render gives it.  tests/adaptive_ref.py
 // restates the rule in numpy.
@@ -23,16 +23,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 namespace {
 
-__device__ __forceinline__ bool finitef(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
-// rt_noise.hip noise_rel: the relative standard error of a finite state, denom = nf * (nf - 1)
-__device__ __forceinline__ float noise_rel(float mean, float m2, float denom, float floor)
-{
-    const float var = (m2 < 0.0f ? 0.0f : m2) / denom;
-    const float a = rt_absf(mean);
-    return rt_det_sqrtf(var) / (a < floor ? floor : a);
-}
-
+// (finitef and noise_rel: rt_device_common.h, shared with rt_noise.hip)
 // rt.h: does a valid slot with this state and count want more at a call's first_iter > 0?
 __device__ __forceinline__ bool wants_more(const v2f s, uint32_t cnt, uint32_t first, const AdaptParams& P)
 {
@@ -229,12 +220,6 @@ __global__ void __launch_bounds__(256) k_adaptive_map(const rt_noise_state* __re
         rel[o] = n >= 2u && finitef(s.x) && finitef(s.y) ? __float_as_uint(noise_rel(s.x, s.y, nf * (nf - 1.0f), floor))
                                                          : 0x7FC00000u;
     }
-}
-
-uint32_t stream_blocks(uint64_t n, uint64_t cap)
-{
-    const uint64_t b = (n + 255) / 256;
-    return (uint32_t)(b > cap ? cap : b ? b : 1);
 }
 
 }  // namespace

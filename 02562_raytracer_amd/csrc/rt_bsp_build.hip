@@ -445,7 +445,7 @@ namespace rtk {
 // Content box of every node's subtree: the union of the bounding boxes of the
 // triangles its leaves reference (2 x float4 per node: min, max; empty: +inf /
 // -inf).  The BSP walk skips a subtree whose box the ray interval misses
-// (rt_kernels.hip bsp_walk, DESIGN.md section 4 "Subtree culling").
+// (rt_walk_bsp.h bsp_walk, DESIGN.md section 4 "Subtree culling").
 // Certification data of every node's subtree (2 x float4 per node), for the
 // certified margin of bsp_box_miss (DESIGN.md section 4 "Certified culling"):
 //   {E2, nlo.xyz}, {0, nhi.xyz}: E2 = the largest max(|e0|inf, |e1|inf)^2 over
@@ -589,7 +589,7 @@ __global__ void __launch_bounds__(256) k_bsp_repack(const uint32_t* tree, const 
 
 // The 48-B triangle records in treeIds order, and beside them each slot's
 // {triangle id, material} (tm: what shading resolves a BSP hit to, one load
-// instead of treeIds -> tri_idx; rt_kernels.hip resolve)
+// instead of treeIds -> tri_idx; rt_walk.h resolve)
 __global__ void __launch_bounds__(256) k_tri_records2(const float4* pos, const uint4* idx, const uint32_t* ids,
                                                       uint32_t nids, float4* recs, uint2* tm)
 {
@@ -606,7 +606,7 @@ __global__ void __launch_bounds__(256) k_tri_records2(const float4* pos, const u
     }
 }
 
-// The camera term of the certified margin (rt_kernels.hip bsp_box_miss,
+// The camera term of the certified margin (rt_walk_bsp.h bsp_box_miss,
 // DESIGN.md section 4 "Certified culling"): for the eye E of the camera rays,
 // H = min over a subtree's triangles of |(v0 - E) . n*| / E_T^2, a lower bound,
 // rounded down (the f64 dot product's error subtracted, a 2^-19 relative slack
@@ -777,7 +777,7 @@ int launch_bsp_camera(const uint32_t* tree, uint32_t nnodes, const float4* pos, 
     return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
 }
 
-// Whether the walk's plane divisions need their range check (rt_kernels.hip bsp_decide):
+// Whether the walk's plane divisions need their range check (rt_walk_bsp.h bsp_decide):
 // rt_div_by_recip is exact for x = plane - o with x == 0 or 2^-100 <= |x| <= 2^100
 // (include/rt_detmath.h).  That holds for every ray origin coordinate o that is 0 or
 // in [2^-76, 2^99] in magnitude (k_path checks those per ray) when every interior

@@ -346,31 +346,27 @@ __global__ void __launch_bounds__(256) k_denoise_level_lattice(LevelArgs A)
 }
 
 // ------------------------------------------------------------------ launchers
-static uint32_t dn_blocks(uint64_t n, uint64_t cap)
-{
-    const uint64_t b = (n + 255) / 256;
-    return (uint32_t)(b > cap ? cap : b ? b : 1);
-}
 static int dn_ok() { return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE; }
 
 int launch_denoise_guide(const DenoiseCam& g, const float4* pos, const uint4* tri_idx, uint32_t ntris,
                          const uint32_t* ids, float* nz, float* dz, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_denoise_guide, dim3(dn_blocks((uint64_t)g.w * g.h, 4096)), dim3(256), 0, stream, g, pos, tri_idx,
-                       ntris, ids, reinterpret_cast<v4f*>(nz), reinterpret_cast<v2f*>(dz));
+    hipLaunchKernelGGL(k_denoise_guide, dim3(stream_blocks((uint64_t)g.w * g.h, 4096)), dim3(256), 0, stream, g, pos,
+                       tri_idx, ntris, ids, reinterpret_cast<v4f*>(nz), reinterpret_cast<v2f*>(dz));
     return dn_ok();
 }
 
 int launch_denoise_variance(const rt_noise_state* state, const uint32_t* count, uint32_t npix, uint32_t n, float* var,
                             hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_denoise_variance, dim3(dn_blocks(npix, 4096)), dim3(256), 0, stream, state, count, npix, n, var);
+    hipLaunchKernelGGL(k_denoise_variance, dim3(stream_blocks(npix, 4096)), dim3(256), 0, stream, state, count, npix, n,
+                       var);
     return dn_ok();
 }
 
 int launch_denoise_pack(const float* color, const float* var, uint32_t npix, float* cv, hipStream_t stream)
 {
-    hipLaunchKernelGGL(k_denoise_pack, dim3(dn_blocks(npix, 4096)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(k_denoise_pack, dim3(stream_blocks(npix, 4096)), dim3(256), 0, stream,
                        reinterpret_cast<const v4f*>(color), var, npix, reinterpret_cast<v4f*>(cv));
     return dn_ok();
 }

@@ -1,5 +1,6 @@
 // rt_device_common.h -- device helpers shared by the kernel translation units
-// (rt_kernels.hip, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip, rt_noise.hip): the f32 vector
+// (rt_kernels.hip and its headers, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip, rt_noise.hip,
+// rt_adaptive.hip): the f32 vector
 // math of the WGSL builtins, the per-launch counters and the wave sum, the camera ray
 // of get_camera_ray and the work mapping of one 8x8 tile per wave.  Not part of the
 // public ABI.
@@ -197,6 +198,19 @@ __device__ __forceinline__ rec4 path_record(bool flagged, const rec4 cst, const 
 {
     if (flagged) return cst;
     return STREAM ? __builtin_nontemporal_load(p) : *p;
+}
+
+// ------------------------------------------------------------------ noise estimate
+// (k_noise_map / k_noise_summary, rt_noise.hip; the live rule and the count-aware map, rt_adaptive.hip)
+__device__ __forceinline__ bool finitef(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+
+// the relative standard error of the mean of a finite state after n >= 2 iterations
+// (denom = nf * (nf - 1)); never NaN: m2 is clamped, denom and the floor are positive
+__device__ __forceinline__ float noise_rel(float mean, float m2, float denom, float floor)
+{
+    const float var = (m2 < 0.0f ? 0.0f : m2) / denom;
+    const float a = rt_absf(mean);
+    return rt_det_sqrtf(var) / (a < floor ? floor : a);
 }
 
 __device__ __forceinline__ void pixel_uv(const rt_uniform& u, uint32_t x, uint32_t y, float& ux, float& uy)

@@ -151,7 +151,7 @@ RT_EMPTY_HD Tri make_tri(const Cam& cam, const float v0[3], const float v1[3], c
     return t;
 }
 
-// the certified margin (rt_kernels.hip bsp_box_miss's formula, whose constants carry
+// the certified margin (rt_walk_bsp.h bsp_box_miss's formula, whose constants carry
 // slack over the proof's 34u and 10u) for |w|1 <= w1 and |denom| / E^2 >= den
 RT_EMPTY_HD double margin(const Cam& cam, const Tri& t, double w1, double den)
 {

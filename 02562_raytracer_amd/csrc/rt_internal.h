@@ -45,7 +45,7 @@ struct DevScene {
     uint32_t bvh_nnodes;
     // RT_OPT_BSP_CULL: the BSP walk skips a subtree whose content box, grown by a
     // margin, the ray misses by more than this fraction of |tn| + |tf| (2^-18; +inf
-    // turns culling off without a branch on a uniform flag, rt_kernels.hip bsp_box_miss)
+    // turns culling off without a branch on a uniform flag, rt_walk_bsp.h bsp_box_miss)
     float bsp_cull_gap;
     // the margin, as data for both culling modes (bsp_box_miss):
     //   m = D1 * (cull_k1 * w1 / max(F, 2 Dlb - 20u w1) + cull_k3) + max(|o|inf * cull_ko, bsp_margin)
@@ -62,7 +62,7 @@ struct DevScene {
     // (kept last: a field added mid-struct once moved the trip loop into spills)
     float bsp_cull_emax;
     // per BSP record slot: {triangle id, material} (treeIds[k], tri_idx[treeIds[k]].w),
-    // so shading resolves a hit with one load (rt_kernels.hip resolve)
+    // so shading resolves a hit with one load (rt_walk.h resolve)
     const uint2* bsp_tm;
     // RT_BSP_CULL_SILHOUETTE: per 1-based node M, the camera term's two excluded
     // triangles' normals and the rest's term, 16 B at [M] (rt_bsp_build.hip k_treelet_hcam)
@@ -140,6 +140,13 @@ inline int flat_grid(int num_cus, int waves_per_cu, uint32_t nwork)
     const int wpc = waves_per_cu > 0 ? waves_per_cu : 16;
     const long long cap = std::max(1LL, (long long)num_cus * wpc / 4);
     return (int)std::min<long long>(cap, ((long long)nwork + 3) / 4);
+}
+// Grid of the streaming kernels (a thread per element, grid-stride): the 256-thread blocks
+// n elements fill, at least one and at most cap
+inline uint32_t stream_blocks(uint64_t n, uint64_t cap)
+{
+    const uint64_t b = (n + 255) / 256;
+    return (uint32_t)(b > cap ? cap : b ? b : 1);
 }
 // Run-time values as template constants: f(std::bool_constant<b>), and
 // f(Int<mode>, std::bool_constant<detail>) for a mode in FIRST..LAST (false: outside).

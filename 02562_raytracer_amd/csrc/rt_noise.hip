@@ -29,7 +29,7 @@ __device__ __forceinline__ void noise1(float& mean, float& m2, const v4f x, uint
 }
 
 // ------------------------------------------------------------------ state update
-// After k_fold, over the same records and with the same addressing (rt_kernels.hip
+// After k_fold, over the same records and with the same addressing (rt_stream_kernels.h
 // k_fold): one thread per output slot.  [pixel][iteration] records are the thread's own
 // contiguous run, loaded eight (128 B, one line) at a time; [iteration][pixel] records
 // are 1 KiB contiguous per wave and iteration.  The records are not read again after
@@ -73,17 +73,7 @@ __global__ void __launch_bounds__(256) k_noise(DevLaunch L, const uint32_t* empt
 }
 
 // ------------------------------------------------------------------ map and summary
-__device__ __forceinline__ bool finitef(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
-// the relative standard error of the mean of a finite state after n >= 2 iterations
-// (denom = nf * (nf - 1)); never NaN: m2 is clamped, denom and the floor are positive
-__device__ __forceinline__ float noise_rel(float mean, float m2, float denom, float floor)
-{
-    const float var = (m2 < 0.0f ? 0.0f : m2) / denom;
-    const float a = rt_absf(mean);
-    return rt_det_sqrtf(var) / (a < floor ? floor : a);
-}
-
+// (finitef and noise_rel: rt_device_common.h, shared with rt_adaptive.hip)
 __global__ void __launch_bounds__(256) k_noise_map(const rt_noise_state* __restrict__ state, uint32_t npix, float nf,
                                                    float floor, uint32_t* __restrict__ rel)
 {
@@ -132,12 +122,6 @@ __global__ void __launch_bounds__(256) k_noise_summary(const rt_noise_state* __r
 }
 
 // ------------------------------------------------------------------ launchers
-static uint32_t stream_blocks(uint64_t n, uint64_t cap)
-{
-    const uint64_t b = (n + 255) / 256;
-    return (uint32_t)(b > cap ? cap : b ? b : 1);
-}
-
 int launch_noise(const DevLaunch& l, const uint32_t* empty_mask, rt_noise_state* state, hipStream_t stream)
 {
     // k_fold's grid (launch_fold): the two kernels stream the same records

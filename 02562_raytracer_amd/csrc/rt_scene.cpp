@@ -49,7 +49,7 @@ void build_recs(const std::vector<float>& pos, const std::vector<uint32_t>& idx,
 // bsp.ref_tree / bsp.ref_planes / bsp.ids, mesh in pos / idx): content boxes,
 // 96-B treelets and the 48-B records (rt_bsp_build.hip launch_bsp_repack), and
 // the scale of the content boxes' margins: the largest coordinate magnitude of
-// the BSP's root box (bsp_box_miss in rt_kernels.hip adds the ray origin's).
+// the BSP's root box (bsp_box_miss in rt_walk_bsp.h adds the ray origin's).
 int repack_bsp(rt_ctx* c, uint32_t nnodes, uint32_t nids, size_t rec_off, size_t total, const float aabb[8])
 {
     SceneState& s = c->scene;
@@ -196,7 +196,7 @@ rtk::DevScene dev_scene(const rt_ctx* c)
     S.bvh_rec_off = s.bvh.rec_off;
     S.bvh_ids = s.bvh.ids.as<uint32_t>();
     S.bvh_nnodes = s.bvh.nnodes;
-    // the culling margin as data (rt_internal.h DevScene, rt_kernels.hip bsp_box_miss)
+    // the culling margin as data (rt_internal.h DevScene, rt_walk_bsp.h bsp_box_miss)
     S.bsp_cull_gap = c->bsp_cull != RT_BSP_CULL_OFF ? 0x1p-18f : INFINITY;
     S.bsp_cull_emax = c->bsp_cull != RT_BSP_CULL_OFF ? FLT_MAX : INFINITY;
     // off: the fast formula's constants (k1 = 0 picks k_path's fast-margin

@@ -2,7 +2,7 @@
 // w3e4.wgsl): a triangle, a sphere of radius 0.3 and the plane y = 0 as constants, a
 // point light at (0, 1.2, 0), the objects' base colours and the background.  The one
 // device copy: rt_worksheet1.hip (W1E4..W1E6) and rt_analytic.hip (W2E1..W3E4) render
-// the scene, rt_kernels.hip uses the sphere test for the W8 balls.
+// the scene, rt_shade.h uses the sphere test for the W8 balls.
 //
 // Each test answers whether the object is hit inside [tmin, tmax] and at which
 // distance; what an accept means is the caller's: the worksheet-1 shaders lower tmax

@@ -45,7 +45,7 @@ struct TriPre {
 };
 // false: the shader's test certainly rejects.  The degenerate test is the W5
 // shaders' abs(denom) < 1e-6.  The rest is the approximate-reciprocal rejection
-// of rt_kernels.hip tri_math<FAST>, whose argument carries over (1e-6 <= |denom|
+// of rt_trace_common.h tri_math<FAST>, whose argument carries over (1e-6 <= |denom|
 // <= 2^60 makes r = v_rcp_f32(denom) a normal number within 1 ulp of 1 / denom):
 // each rejection implies that the predicate on the exact quotients rejects; a
 // survivor is decided by sweep_exact on the exact quotients alone.

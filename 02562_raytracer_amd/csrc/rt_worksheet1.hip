@@ -172,10 +172,7 @@ __global__ void __launch_bounds__(256) k_frame_linear(const float4* accum, uint3
 
 int launch_frame_linear(const float4* accum, uint32_t npix, const float* thr, uchar4* out, hipStream_t stream)
 {
-    uint64_t blocks = ((uint64_t)npix + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(k_frame_linear, dim3((uint32_t)blocks), dim3(256), 0, stream, accum, npix, thr, out);
+    hipLaunchKernelGGL(k_frame_linear, dim3(stream_blocks(npix, 8192)), dim3(256), 0, stream, accum, npix, thr, out);
     return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
 }
 

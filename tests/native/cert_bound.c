@@ -1,5 +1,5 @@
 /* cert_bound.c -- empirical check of the certified culling margin (test code;
- * DESIGN.md section 4 "Certified culling", rt_kernels.hip bsp_box_miss).
+ * DESIGN.md section 4 "Certified culling", rt_walk_bsp.h bsp_box_miss).
  *
  * The claim: when intersect_triangle (w7e3.wgsl:286-332, f32, no contraction,
  * correctly rounded division) accepts a ray (o, w) at distance t, the point
@@ -16,7 +16,7 @@
  * evaluated in long double.
  * Build: gcc -O2 -ffp-contract=off -o cert_bound cert_bound.c -lm
  * usage: cert_bound <trials> <seed> [camera 0/1]   prints: accepts max_ratio floor_accepts
- * With camera 1 the margin also takes the camera bound (rt_kernels.hip bsp_box_miss)
+ * With camera 1 the margin also takes the camera bound (rt_walk_bsp.h bsp_box_miss)
  * with each ray's origin as the eye -- every trial is then a camera ray. */
 #include <math.h>
 #include <stdint.h>

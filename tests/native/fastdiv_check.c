@@ -46,7 +46,7 @@ int main(int argc, char** argv)
         }
         if (rnd32() & 1u) d = -d;
         /* x = +-0 (a plane through the ray origin's coordinate), which the walk's
-         * unchecked divisions (rt_kernels.hip bsp_decide without chk) also take: the
+         * unchecked divisions (rt_walk_bsp.h bsp_decide without chk) also take: the
          * result must be a zero; its sign is x / d's for x = +0 and may differ for
          * x = -0 (counted apart), which the walk does not see -- it only compares t */
         for (int zs = 0; zs < 2; zs++) {

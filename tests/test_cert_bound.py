@@ -1,4 +1,4 @@
-"""The certified culling margin (rt_kernels.hip bsp_box_miss, DESIGN.md section 4
+"""The certified culling margin (rt_walk_bsp.h bsp_box_miss, DESIGN.md section 4
 "Certified culling") against adversarial rays on the CPU: tests/native/cert_bound.c
 runs the reference's f32 triangle test (w7e3.wgsl:286-332) on random triangles
 (sizes 1e-4 .. 3, slivers included) and rays aimed near them from up to 10x the

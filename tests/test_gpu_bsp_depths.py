@@ -3,7 +3,7 @@ test uploads mesh.bsp_tree() at its default depth): D = 1, 2, 3, 4, 5, 7 on
 scatter(3000) and D = 19, 21, 22, 24 on `deep` (tests/build_cases.py), whose
 tree has leaves at depth D for each of them.  What depends on the depth:
 
-  * the launchers size the LDS trail by bsp_depth (rt_kernels.hip: bsp_depth x
+  * the launchers size the LDS trail by bsp_depth (rt_kernels.hip walk_lds_bytes: bsp_depth x
     256 x 4 bytes); an interior node at depth D - 1, the deepest there is,
     pushes into slot D - 1, the last one.  The rays of the "plane" group pass
     through a point of the split plane of such a node inside its cell, and a

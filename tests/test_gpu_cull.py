@@ -1,4 +1,4 @@
-"""Subtree culling of the BSP walk (RT_OPT_BSP_CULL, rt_kernels.hip bsp_box_miss;
+"""Subtree culling of the BSP walk (RT_OPT_BSP_CULL, rt_walk_bsp.h bsp_box_miss;
 DESIGN.md section 4 "Subtree culling") changes only the work, never the result:
 frames rendered with certified culling (exact by proof), with the
 silhouette bound and the timed choice between the two (RT_BSP_CULL_SILHOUETTE,

@@ -1,4 +1,4 @@
-"""The VERT form of the leaf test (rt_kernels.hip tri_math<..., VERT>): for a ray of
+"""The VERT form of the leaf test (rt_trace_common.h tri_math<..., VERT>): for a ray of
 direction exactly (0, 1, 0) -- every W9E1 shadow ray, light_init, w9e1.wgsl:67-73 --
 the reference's intersect_triangle (w7e3.wgsl:286-332, f32, no contraction) computes
 cross(ov, w) = (-ov.z, +-0, ov.x) and dot(w, n) = n.y exactly, so a and b reduce to one

@@ -1,9 +1,8 @@
 """Per-kernel comparison of the render kernels' gfx950 assembly between a git revision
 and the working tree: the check that a refactor left the compiled kernels alone.
 
-Cross-compiles rt_kernels.hip, rt_sweep.hip, rt_analytic.hip and rt_worksheet1.hip of
-both trees with the Makefile's flags plus --cuda-device-only -S, and compares every
-kernel symbol's body (up to .Lfunc_end) and its .amdhsa_kernel block.  Before comparing,
+Cross-compiles every .hip file of the library in both trees, each with the flags its
+Makefile rule gives it plus --cuda-device-only -S, and compares every kernel symbol's body (up to .Lfunc_end) and its .amdhsa_kernel block.  Before comparing,
 `;` comments are stripped, whitespace is collapsed and the function number leaves the
 basic-block labels (.LBB12_3 -> BB_3): removing or reordering a function renumbers those
 labels and shifts the comment columns, and nothing else.  usage:
@@ -19,15 +18,20 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "02562_raytracer_amd"
-FILES = ["rt_kernels.hip", "rt_sweep.hip", "rt_analytic.hip", "rt_worksheet1.hip"]
+# the Makefile's OBJS built from .hip files; those of NO_SLP get -fno-slp-vectorize there
+FILES = ["rt_kernels.hip", "rt_sweep.hip", "rt_analytic.hip", "rt_worksheet1.hip", "rt_noise.hip", "rt_adaptive.hip",
+         "rt_denoise.hip", "rt_empty.hip", "rt_build.hip", "rt_bsp_build.hip"]
+NO_SLP = {"rt_kernels.hip", "rt_sweep.hip", "rt_analytic.hip", "rt_worksheet1.hip", "rt_noise.hip", "rt_adaptive.hip",
+          "rt_denoise.hip"}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
-         "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-bitwise-instead-of-logical", "-fno-slp-vectorize",
+         "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-bitwise-instead-of-logical",
          "-x", "hip", "--cuda-device-only", "-S"]
 
 
 def device_asm(root, name, out):
-    subprocess.run([HIPCC, *FLAGS, os.path.join(root, PKG, "csrc", name), "-o", out], check=True, timeout=1800)
+    slp = ["-fno-slp-vectorize"] if name in NO_SLP else []
+    subprocess.run([HIPCC, *FLAGS, *slp, os.path.join(root, PKG, "csrc", name), "-o", out], check=True, timeout=1800)
     return open(out).read()
 
 
