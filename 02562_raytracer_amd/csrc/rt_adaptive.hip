@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "rt_device_common.h"
+#include "rt_prims.h"
 
 namespace rtk {
 
@@ -38,7 +39,7 @@ __device__ __forceinline__ bool wants_more(const v2f s, uint32_t cnt, uint32_t f
 // One wave per 8x8 tile of the launch at a time (pixel slot s = 64 * tile + lane), so the
 // tile vote is one ballot.  live (or null): per OUTPUT slot, as accum is
 // indexed, 1 = live; padding slots are not written.  flags (or null): per pixel slot, 1 =
-// live and not flagged empty -- what the scan and the scatter below turn into k_path's
+// live and not flagged empty -- what compact_flagged (rt_prims.hip) turns into k_path's
 // list.  stats (u64 words, zeroed before the launch): [0] live slots, [1] live slots
 // flagged empty; SUMMARY adds [2] above, [3] non-finite, [4] total samples, [5] the bits
 // of the largest finite rel, [6] ~(smallest count), [7] largest count, [8] valid slots
@@ -124,14 +125,6 @@ __global__ void __launch_bounds__(256) k_adaptive_live(DevLaunch L, const uint32
             atomicAdd(stats + 8, (unsigned long long)nvalid);
         }
     }
-}
-
-// rt_empty.hip k_slot_scatter: the set flags' slots, ascending (offs: their exclusive scan)
-__global__ void __launch_bounds__(256) k_adaptive_scatter(const uint32_t* flags, const uint32_t* offs, uint32_t nslots,
-                                                          uint32_t* list)
-{
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < nslots && flags[s]) list[offs[s]] = s;   // offs[s] < the number of set flags <= nslots
 }
 
 // ------------------------------------------------------------------ the fused fold
@@ -238,16 +231,12 @@ int build_adaptive_list(const DevLaunch& l, const uint32_t* empty_mask, const rt
     hipLaunchKernelGGL(k_adaptive_live<false>, dim3(stream_blocks(nslots, 512)), dim3(256), 0, stream, l, empty_mask, state,
                        count, p, live, flags, stats);
     if (hipGetLastError() != hipSuccess) return RT_E_DEVICE;
-    if (int r = scan_exclusive_u32(flags, offs, nslots, scan, stream)) return r;
-    hipLaunchKernelGGL(k_adaptive_scatter, dim3((nslots + 255u) / 256u), dim3(256), 0, stream, flags, offs, nslots, list);
-    if (hipGetLastError() != hipSuccess) return RT_E_DEVICE;
-    uint32_t last[2] = {0, 0};
+    uint32_t nlist = 0;
     unsigned long long st[2] = {0, 0};
-    if (hipMemcpyAsync(&last[0], offs + (nslots - 1), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return RT_E_DEVICE;
-    if (hipMemcpyAsync(&last[1], flags + (nslots - 1), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return RT_E_DEVICE;
+    if (int r = compact_flagged(flags, offs, nslots, scan, list, &nlist, stream)) return r;
     if (hipMemcpyAsync(st, stats, sizeof st, hipMemcpyDeviceToHost, stream) != hipSuccess) return RT_E_DEVICE;
     if (hipStreamSynchronize(stream) != hipSuccess) return RT_E_DEVICE;
-    out[0] = (uint64_t)last[0] + last[1];
+    out[0] = nlist;
     out[1] = st[0];
     out[2] = st[1];
     return 0;

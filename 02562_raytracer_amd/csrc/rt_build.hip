@@ -6,8 +6,8 @@
 // Phases (the reference's BvhConstructionTime split, bvh_util.rs):
 //   morton_codes  k_boxes (triangle boxes + per-block centroid bounds),
 //                 k_bound, k_morton (10 bits/axis, Rust `as u32` saturation)
-//   radix_sort    4 LSD passes of 8 bits over the 30-bit codes: k_rs_hist,
-//                 k_rs_scan, k_rs_scatter (stable: equal codes stay in
+//   radix_sort    4 LSD passes of 8 bits over the 30-bit codes (rt_prims.hip
+//                 radix_sort_pairs; stable: equal codes stay in
 //                 primitive-index order, the host builder's tie order)
 //   treelet_init  k_treelet_count / k_treelet_list: treelets = runs of equal
 //                 top-12 code bits (mask 0x3FFC0000), in code order
@@ -21,9 +21,9 @@
 //                 level), the DFS offsets of the roots and the upper nodes' records
 //   flattening    k_top_down per level (DFS index of every node: left child
 //                 = parent+1, right = parent+1+size(left)), k_write_nodes, the
-//                 upper nodes, the GpuNode::new(root box) filler of the
-//                 over-allocated array, and the traversal repack (node records
-//                 with byte offsets + 48-B triangle records)
+//                 upper nodes and the GpuNode::new(root box) filler of the
+//                 over-allocated array
+// The traversal layout of the result is rt_layout.hip's (launch_bvh_repack).
 // Numerics: min/max folds with the reference's operand order, -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -37,12 +37,12 @@
 #include "../../include/rt_detmath.h"
 #include "host_types.h"
 #include "rt_internal.h"
+#include "rt_prims.h"
 
 namespace rtb {
 
 constexpr int kLevels = 19;          // emit_lbvh bits 17 .. -1
 constexpr uint32_t kTreeletMask = 0x3FFC0000u;
-constexpr int kTile = 2048;          // radix sort keys per block (256 threads x 8)
 
 struct BNode {                       // build node (pool)
     float mn[3], mx[3];
@@ -82,12 +82,8 @@ __global__ void __launch_bounds__(256) k_boxes(const float4* pos, const uint4* i
     __shared__ float red[6][256];
     float bmn[3] = {1.0e37f, 1.0e37f, 1.0e37f}, bmx[3] = {-1.0e37f, -1.0e37f, -1.0e37f};
     for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < nt; t += gridDim.x * 256u) {
-        const uint4 ix = idx[t];
-        const float4 a = pos[ix.x], b = pos[ix.y], c = pos[ix.z];
-        const float mn[3] = {rt_minf(a.x, rt_minf(b.x, c.x)), rt_minf(a.y, rt_minf(b.y, c.y)),
-                             rt_minf(a.z, rt_minf(b.z, c.z))};
-        const float mx[3] = {rt_maxf(a.x, rt_maxf(b.x, c.x)), rt_maxf(a.y, rt_maxf(b.y, c.y)),
-                             rt_maxf(a.z, rt_maxf(b.z, c.z))};
+        float mn[3], mx[3];
+        rtk::tri_box(pos, idx[t], mn, mx);
         boxes[2u * t] = make_float4(mn[0], mn[1], mn[2], 0.0f);
         boxes[2u * t + 1u] = make_float4(mx[0], mx[1], mx[2], 0.0f);
         for (int i = 0; i < 3; i++) {
@@ -96,19 +92,7 @@ __global__ void __launch_bounds__(256) k_boxes(const float4* pos, const uint4* i
             bmx[i] = rt_maxf(bmx[i], cc);
         }
     }
-    for (int i = 0; i < 3; i++) {
-        red[i][threadIdx.x] = bmn[i];
-        red[3 + i][threadIdx.x] = bmx[i];
-    }
-    __syncthreads();
-    for (uint32_t s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s)
-            for (int i = 0; i < 3; i++) {
-                red[i][threadIdx.x] = rt_minf(red[i][threadIdx.x], red[i][threadIdx.x + s]);
-                red[3 + i][threadIdx.x] = rt_maxf(red[3 + i][threadIdx.x], red[3 + i][threadIdx.x + s]);
-            }
-        __syncthreads();
-    }
+    rtk::block_minmax6(red, bmn, bmx);
     if (threadIdx.x < 6) partial[blockIdx.x * 6u + threadIdx.x] = red[threadIdx.x][0];
 }
 
@@ -121,16 +105,7 @@ __global__ void __launch_bounds__(256) k_bound(const float* partial, uint32_t np
             v[i] = rt_minf(v[i], partial[p * 6u + i]);
             v[3 + i] = rt_maxf(v[3 + i], partial[p * 6u + 3 + i]);
         }
-    for (int i = 0; i < 6; i++) red[i][threadIdx.x] = v[i];
-    __syncthreads();
-    for (uint32_t s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s)
-            for (int i = 0; i < 3; i++) {
-                red[i][threadIdx.x] = rt_minf(red[i][threadIdx.x], red[i][threadIdx.x + s]);
-                red[3 + i][threadIdx.x] = rt_maxf(red[3 + i][threadIdx.x], red[3 + i][threadIdx.x + s]);
-            }
-        __syncthreads();
-    }
+    rtk::block_minmax6(red, v, v + 3);
     if (threadIdx.x < 6) bound[threadIdx.x] = red[threadIdx.x][0];
 }
 
@@ -169,96 +144,6 @@ __global__ void __launch_bounds__(256) k_morton(const float4* boxes, const float
     }
 }
 
-// ------------------------------------------------------------ radix sort
-// Stable LSD radix sort of (code, index) pairs, 8-bit digits.  Per pass:
-// per-tile digit histograms (digit-major), one exclusive scan, and a stable
-// scatter: each tile ranks its keys in order, 256 at a time, with wave64
-// match masks (8 ballots) and a per-digit running count across the 4 waves.
-__global__ void __launch_bounds__(256) k_rs_hist(const uint32_t* keys, uint32_t n, uint32_t shift, uint32_t ntiles,
-                                                 uint32_t* hist)
-{
-    __shared__ uint32_t cnt[256];
-    cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * (uint32_t)kTile;
-    for (uint32_t i = threadIdx.x; i < (uint32_t)kTile; i += 256u) {
-        const uint32_t k = base + i;
-        if (k < n) atomicAdd(&cnt[(keys[k] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[threadIdx.x * ntiles + blockIdx.x] = cnt[threadIdx.x];
-}
-
-// exclusive scan of m words in place, one block of 1024 threads
-__global__ void __launch_bounds__(1024) k_rs_scan(uint32_t* a, uint32_t m)
-{
-    __shared__ uint32_t part[1024];
-    const uint32_t per = (m + 1023u) / 1024u;
-    const uint32_t lo = threadIdx.x * per, hi = min(m, lo + per);
-    uint32_t s = 0;
-    for (uint32_t i = lo; i < hi; i++) s += a[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024u; off <<= 1) {   // Hillis-Steele inclusive scan
-        const uint32_t v = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - s;
-    for (uint32_t i = lo; i < hi; i++) {
-        const uint32_t v = a[i];
-        a[i] = run;
-        run += v;
-    }
-}
-
-__global__ void __launch_bounds__(256) k_rs_scatter(const uint32_t* kin, const uint32_t* vin, uint32_t n,
-                                                    uint32_t shift, uint32_t ntiles, const uint32_t* offs,
-                                                    uint32_t* kout, uint32_t* vout)
-{
-    __shared__ uint32_t gbase[256], running[256], wcnt[4][256], wbase[4][256];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    gbase[threadIdx.x] = offs[threadIdx.x * ntiles + blockIdx.x];
-    running[threadIdx.x] = 0;
-    for (int w = 0; w < 4; w++) wcnt[w][threadIdx.x] = 0;
-    __syncthreads();
-    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64u - lane));
-    for (uint32_t r = 0; r < (uint32_t)kTile / 256u; r++) {
-        const uint32_t k = blockIdx.x * (uint32_t)kTile + r * 256u + threadIdx.x;
-        const bool valid = k < n;
-        const uint32_t key = valid ? kin[k] : 0u, val = valid ? vin[k] : 0u;
-        const uint32_t d = (key >> shift) & 255u;
-        uint64_t peers = __ballot(valid);
-#pragma unroll
-        for (int b = 0; b < 8; b++) {
-            const uint64_t m = __ballot(((d >> b) & 1u) != 0u);
-            peers &= ((d >> b) & 1u) ? m : ~m;
-        }
-        const uint32_t rank = (uint32_t)__popcll(peers & lt);
-        if (valid && rank == 0) wcnt[wave][d] = (uint32_t)__popcll(peers);
-        __syncthreads();
-        {
-            const uint32_t dd = threadIdx.x;
-            uint32_t s = running[dd];
-            for (int w = 0; w < 4; w++) {
-                const uint32_t c = wcnt[w][dd];
-                wbase[w][dd] = s;
-                s += c;
-                wcnt[w][dd] = 0;
-            }
-            running[dd] = s;
-        }
-        __syncthreads();
-        if (valid) {
-            const uint32_t pos = gbase[d] + wbase[wave][d] + rank;
-            kout[pos] = key;
-            vout[pos] = val;
-        }
-        __syncthreads();
-    }
-}
-
 // ------------------------------------------------------------ treelets
 __global__ void __launch_bounds__(256) k_treelet_count(const uint32_t* keys, uint32_t n, uint32_t* counts)
 {
@@ -271,25 +156,18 @@ __global__ void __launch_bounds__(256) k_treelet_count(const uint32_t* keys, uin
 // pool slot j for treelet j
 __global__ void __launch_bounds__(1024) k_treelet_list(const uint32_t* counts, Item* items, Ctl* ctl)
 {
-    __shared__ uint32_t ne[1024], st[1024];
+    __shared__ uint64_t part[1024];
     uint32_t c[4], nonempty = 0, total = 0;
     for (int i = 0; i < 4; i++) {
         c[i] = counts[threadIdx.x * 4u + i];
         nonempty += c[i] != 0u;
         total += c[i];
     }
-    ne[threadIdx.x] = nonempty;
-    st[threadIdx.x] = total;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024u; off <<= 1) {
-        const uint32_t a = threadIdx.x >= off ? ne[threadIdx.x - off] : 0u;
-        const uint32_t b = threadIdx.x >= off ? st[threadIdx.x - off] : 0u;
-        __syncthreads();
-        ne[threadIdx.x] += a;
-        st[threadIdx.x] += b;
-        __syncthreads();
-    }
-    uint32_t j = ne[threadIdx.x] - nonempty, start = st[threadIdx.x] - total;
+    // one scan for both: the treelets before this thread's (high word) and their primitives
+    // (low word; the totals are at most 4096 and the triangle count: no carry between them)
+    const uint64_t incl = rtk::block_scan_inclusive<1024>(part, ((uint64_t)nonempty << 32) | total);
+    const uint32_t ne_incl = (uint32_t)(incl >> 32);
+    uint32_t j = ne_incl - nonempty, start = (uint32_t)incl - total;
     for (int i = 0; i < 4; i++) {
         if (c[i]) {
             items[j] = Item{start, c[i], 17, j};
@@ -298,10 +176,10 @@ __global__ void __launch_bounds__(1024) k_treelet_list(const uint32_t* counts, I
         start += c[i];
     }
     if (threadIdx.x == 1023u) {
-        ctl->ntreelets = ne[1023];
-        ctl->items[0] = ne[1023];
+        ctl->ntreelets = ne_incl;
+        ctl->items[0] = ne_incl;
         ctl->items[1] = 0;
-        ctl->pool = ne[1023];
+        ctl->pool = ne_incl;
         ctl->res = 0;
         ctl->emits = 0;
     }
@@ -451,15 +329,6 @@ __global__ void __launch_bounds__(256) k_scatter_nodes(const rt_gpu_node* src, c
 // (tests/test_gpu_build.py).
 namespace upper {
 constexpr uint32_t kMax = 4096;   // treelets: 12-bit Morton prefixes
-__device__ __forceinline__ uint32_t fkey(float f)   // f32::total_cmp order (-0 < +0)
-{
-    const uint32_t b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float funkey(uint32_t k)
-{
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
 struct Seg {
     uint32_t lo, hi, depth, rights, ord;
 };
@@ -543,7 +412,7 @@ __global__ void __launch_bounds__(1024) k_upper_tree(const Ctl* ctl, BNode* pool
             const Seg g = descend(n, p, lev);
             if (g.hi - g.lo >= 2u)
                 for (uint32_t k = 0; k < 3; k++) {
-                    const uint32_t c = fkey(cc[r][k]);
+                    const uint32_t c = rtk::ord_key(cc[r][k]);
                     atomicMin(&bmn[k * (kMax / 2) + g.ord], c);
                     atomicMax(&bmx[k * (kMax / 2) + g.ord], c);
                 }
@@ -565,9 +434,9 @@ __global__ void __launch_bounds__(1024) k_upper_tree(const Ctl* ctl, BNode* pool
             if (g.hi - g.lo >= 2u) {
                 float d[3];
                 for (uint32_t k = 0; k < 3; k++)
-                    d[k] = funkey(bmx[k * (kMax / 2) + g.ord]) - funkey(bmn[k * (kMax / 2) + g.ord]);
+                    d[k] = rtk::ord_unkey(bmx[k * (kMax / 2) + g.ord]) - rtk::ord_unkey(bmn[k * (kMax / 2) + g.ord]);
                 const uint32_t dim = d[0] > d[1] ? (d[0] > d[2] ? 0u : 2u) : (d[1] > d[2] ? 1u : 2u);
-                k32 = fkey(dim == 0u ? cc[r][0] : dim == 1u ? cc[r][1] : cc[r][2]);
+                k32 = rtk::ord_key(dim == 0u ? cc[r][0] : dim == 1u ? cc[r][1] : cc[r][2]);
             }
             // a single-member segment that stopped above this level keeps its block at
             // its ordinal scaled to this depth (no real segment lives under it)
@@ -602,16 +471,8 @@ __global__ void __launch_bounds__(1024) k_upper_tree(const Ctl* ctl, BNode* pool
             loc[r] = p < n ? pool[perm[p]].size : 0u;
             sum += loc[r];
         }
-        uint32_t* part = bmn;   // 1024 partial sums (the sort scratch is free)
-        part[tid] = sum;
-        __syncthreads();
-        for (uint32_t off = 1; off < 1024u; off <<= 1) {
-            const uint32_t v = tid >= off ? part[tid - off] : 0u;
-            __syncthreads();
-            part[tid] += v;
-            __syncthreads();
-        }
-        uint32_t run = part[tid] - sum;
+        // (in the sort scratch, which is free: 1024 partial sums)
+        uint32_t run = rtk::block_scan_inclusive<1024>(bmn, sum) - sum;
         for (uint32_t r = 0; r < 4; r++) {
             const uint32_t p = tid * 4u + r;
             if (p <= n) pre[p] = run;
@@ -688,159 +549,9 @@ __global__ void __launch_bounds__(256) k_fill_nodes_dev(rt_gpu_node* out, uint32
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) out[i] = f;
 }
 
-// ------------------------------------------------------------ device-wide exclusive scan
-// out[0..n] = exclusive prefix sums of in[0..n), out[n] = total (in == out allowed).
-// Reduce-then-scan: 4096-element blocks (256 threads x 16), one-block scan of
-// the block sums, then each block scans its elements with its offset.
-constexpr uint32_t kScanBlock = 4096;
-__global__ void __launch_bounds__(256) k_scan_reduce(const uint32_t* in, uint32_t n, uint32_t* bsum)
-{
-    __shared__ uint32_t red[256];
-    const uint32_t base = blockIdx.x * kScanBlock;
-    uint32_t s = 0;
-    for (uint32_t i = threadIdx.x; i < kScanBlock; i += 256u)
-        if (base + i < n) s += in[base + i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t st = 128; st > 0; st >>= 1) {
-        if (threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsum[blockIdx.x] = red[0];
-}
-
-__global__ void __launch_bounds__(256) k_scan_down(const uint32_t* in, uint32_t n, const uint32_t* bsum,
-                                                   uint32_t* out)
-{
-    __shared__ uint32_t part[256];
-    const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * 16u;
-    uint32_t v[16], s = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        v[i] = base + i < n ? in[base + i] : 0u;
-        s += v[i];
-    }
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (uint32_t off = 1; off < 256u; off <<= 1) {
-        const uint32_t a = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += a;
-        __syncthreads();
-    }
-    uint32_t run = bsum[blockIdx.x] + part[threadIdx.x] - s;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        if (base + i < n) out[base + i] = run;
-        run += v[i];
-    }
-    if (blockIdx.x == gridDim.x - 1u && threadIdx.x == 255u) out[n] = run;
-}
-
 }  // namespace rtb
 
 namespace rtk {
-
-int scan_exclusive_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* scratch, hipStream_t s)
-{
-    using namespace rtb;
-    const uint32_t nb = n ? (n + kScanBlock - 1) / kScanBlock : 1;
-    if (n == 0) {
-        (void)hipMemsetAsync(out, 0, 4, s);
-        return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
-    }
-    hipLaunchKernelGGL(k_scan_reduce, dim3(nb), dim3(256), 0, s, in, n, scratch);
-    hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, s, scratch, nb);
-    hipLaunchKernelGGL(k_scan_down, dim3(nb), dim3(256), 0, s, in, n, scratch, out);
-    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
-}
-size_t scan_scratch_words(uint32_t n) { return (size_t)(n + rtb::kScanBlock - 1) / rtb::kScanBlock + 16; }
-
-// Stable LSD radix sort of (key, value) pairs over the low 8*passes key bits;
-// ping-pongs between (k0,v0) and (k1,v1); returns which pair holds the result.
-int radix_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, uint32_t passes,
-                     uint32_t* hist, hipStream_t s, int& result_in_second)
-{
-    using namespace rtb;
-    const uint32_t ntiles = (n + kTile - 1) / kTile;
-    result_in_second = 0;
-    for (uint32_t pass = 0; pass < passes && n; pass++) {
-        const uint32_t sh = pass * 8u;
-        hipLaunchKernelGGL(k_rs_hist, dim3(ntiles), dim3(256), 0, s, k0, n, sh, ntiles, hist);
-        hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, s, hist, 256u * ntiles);
-        hipLaunchKernelGGL(k_rs_scatter, dim3(ntiles), dim3(256), 0, s, k0, v0, n, sh, ntiles, hist, k1, v1);
-        std::swap(k0, k1);
-        std::swap(v0, v1);
-        result_in_second ^= 1;
-    }
-    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
-}
-size_t radix_hist_words(uint32_t n) { return (size_t)256 * ((n + rtb::kTile - 1) / rtb::kTile) + 16; }
-
-// Traversal layout (rt_api.cpp rt_upload_bvh): node record {min.xyz, w0}{max.xyz, w1}
-// with byte offsets, and 48-B triangle records {v0, e0, e1, n} in tri_ids order.
-__global__ void __launch_bounds__(256) k_bvh_repack(const rt_gpu_node* nodes, uint32_t nnodes, uint32_t rec_off,
-                                                    uint4* blob)
-{
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nnodes; i += gridDim.x * 256u) {
-        const rt_gpu_node n = nodes[i];
-        uint32_t w0, w1;
-        if (n.n_prims > 0) {
-            w0 = rec_off + 48u * n.offset_ptr;
-            w1 = 48u * n.n_prims;
-        } else {
-            w0 = 32u * n.offset_ptr;
-            w1 = 0u;
-        }
-        blob[2u * i] = make_uint4(__float_as_uint(n.min[0]), __float_as_uint(n.min[1]), __float_as_uint(n.min[2]), w0);
-        blob[2u * i + 1u] =
-            make_uint4(__float_as_uint(n.max[0]), __float_as_uint(n.max[1]), __float_as_uint(n.max[2]), w1);
-    }
-}
-
-__global__ void __launch_bounds__(256) k_tri_records(const float4* pos, const uint4* idx, const uint32_t* ids,
-                                                     uint32_t nids, float4* recs)
-{
-    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < nids; k += gridDim.x * 256u) {
-        const uint4 ix = idx[ids[k]];
-        const float4 a = pos[ix.x], b = pos[ix.y], c = pos[ix.z];
-        const float e0[3] = {b.x - a.x, b.y - a.y, b.z - a.z};
-        const float e1[3] = {c.x - a.x, c.y - a.y, c.z - a.z};
-        const float n[3] = {e0[1] * e1[2] - e0[2] * e1[1], e0[2] * e1[0] - e0[0] * e1[2], e0[0] * e1[1] - e0[1] * e1[0]};
-        recs[3u * k] = make_float4(a.x, a.y, a.z, e0[0]);
-        recs[3u * k + 1u] = make_float4(e0[1], e0[2], e1[0], e1[1]);
-        recs[3u * k + 2u] = make_float4(e1[2], n[0], n[1], n[2]);
-    }
-}
-
-int launch_bvh_repack(const rt_gpu_node* nodes, uint32_t nnodes, uint32_t rec_off, void* blob, const float4* pos,
-                      const uint4* idx, const uint32_t* ids, uint32_t nids, hipStream_t s)
-{
-    const uint32_t g1 = std::min<uint32_t>(8192, (nnodes + 255) / 256 + 1);
-    hipLaunchKernelGGL(k_bvh_repack, dim3(g1), dim3(256), 0, s, nodes, nnodes, rec_off, reinterpret_cast<uint4*>(blob));
-    const uint32_t g2 = std::min<uint32_t>(8192, (nids + 255) / 256 + 1);
-    hipLaunchKernelGGL(k_tri_records, dim3(g2), dim3(256), 0, s, pos, idx, ids, nids,
-                       reinterpret_cast<float4*>(reinterpret_cast<uint8_t*>(blob) + rec_off));
-    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
-}
-
-namespace {
-struct Scratch {   // freed at scope exit
-    std::vector<void*> p;
-    ~Scratch()
-    {
-        for (void* q : p) (void)hipFree(q);
-    }
-    template <class T>
-    T* alloc(size_t count, hipError_t& e)
-    {
-        void* q = nullptr;
-        if (e == hipSuccess) e = hipMalloc(&q, std::max<size_t>(16, count * sizeof(T)));
-        if (e == hipSuccess) p.push_back(q);
-        return reinterpret_cast<T*>(q);
-    }
-};
-}  // namespace
 
 int build_bvh_device(const float4* pos, const uint4* idx, uint32_t nt, uint32_t max_prims, int num_cus,
                      hipStream_t s, BvhDeviceOut& out, rt_bvh_build_times* times, std::string& err)
@@ -857,26 +568,26 @@ int build_bvh_device(const float4* pos, const uint4* idx, uint32_t nt, uint32_t 
     // bit lower, so up to 2 new nodes per item per level
     const size_t pool_cap = (max_prims >= 3 ? (size_t)2 * nt : (size_t)2 * kLevels * nt) + 4096;
     const size_t item_cap = (max_prims >= 3 ? (size_t)nt : (size_t)2 * nt) + 4096;
-    Scratch S;
+    DevScratch S;
     const uint32_t grid = (uint32_t)std::max(1, num_cus) * 8u;
-    const uint32_t ntiles = (nt + kTile - 1) / kTile;
-    float4* boxes = S.alloc<float4>((size_t)nt * 2, e);
-    float* partial = S.alloc<float>((size_t)grid * 6, e);
-    float* bound = S.alloc<float>(8, e);
-    uint32_t* k0 = S.alloc<uint32_t>(nt, e);
-    uint32_t* v0 = S.alloc<uint32_t>(nt, e);
-    uint32_t* k1 = S.alloc<uint32_t>(nt, e);
-    uint32_t* v1 = S.alloc<uint32_t>(nt, e);
-    uint32_t* hist = S.alloc<uint32_t>((size_t)256 * ntiles, e);
-    uint32_t* tcount = S.alloc<uint32_t>(4096, e);
-    Item* items0 = S.alloc<Item>(item_cap, e);
-    Item* items1 = S.alloc<Item>(item_cap, e);
-    BNode* pool = S.alloc<BNode>(pool_cap, e);
-    uint32_t* res = S.alloc<uint32_t>(pool_cap, e);
-    Ctl* ctl = S.alloc<Ctl>(1, e);
-    rt_gpu_node* d_up = S.alloc<rt_gpu_node>(upper::kMax, e);   // upper-tree records and their DFS slots
-    uint32_t* d_upat = S.alloc<uint32_t>(upper::kMax, e);
-    float* d_rootbox = S.alloc<float>(8, e);
+    float4* boxes = S.alloc<float4>((size_t)nt * 2);
+    float* partial = S.alloc<float>((size_t)grid * 6);
+    float* bound = S.alloc<float>(8);
+    uint32_t* k0 = S.alloc<uint32_t>(nt);
+    uint32_t* v0 = S.alloc<uint32_t>(nt);
+    uint32_t* k1 = S.alloc<uint32_t>(nt);
+    uint32_t* v1 = S.alloc<uint32_t>(nt);
+    uint32_t* hist = S.alloc<uint32_t>(radix_hist_words(nt));
+    uint32_t* tcount = S.alloc<uint32_t>(4096);
+    Item* items0 = S.alloc<Item>(item_cap);
+    Item* items1 = S.alloc<Item>(item_cap);
+    BNode* pool = S.alloc<BNode>(pool_cap);
+    uint32_t* res = S.alloc<uint32_t>(pool_cap);
+    Ctl* ctl = S.alloc<Ctl>(1);
+    rt_gpu_node* d_up = S.alloc<rt_gpu_node>(upper::kMax);   // upper-tree records and their DFS slots
+    uint32_t* d_upat = S.alloc<uint32_t>(upper::kMax);
+    float* d_rootbox = S.alloc<float>(8);
+    e = S.e;
     if (e != hipSuccess) {
         err = std::string("rt_build_bvh_device: scratch allocation: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_DEVICE;
@@ -906,15 +617,15 @@ int build_bvh_device(const float4* pos, const uint4* idx, uint32_t nt, uint32_t 
     chk("morton");
     (void)hipEventRecord(ev[1], s);
     // -- radix sort (stable; 30-bit codes: 4 passes)
-    for (uint32_t pass = 0; pass < 4; pass++) {
-        const uint32_t sh = pass * 8u;
-        hipLaunchKernelGGL(k_rs_hist, dim3(ntiles), dim3(256), 0, s, k0, nt, sh, ntiles, hist);
-        hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, s, hist, 256u * ntiles);
-        hipLaunchKernelGGL(k_rs_scatter, dim3(ntiles), dim3(256), 0, s, k0, v0, nt, sh, ntiles, hist, k1, v1);
+    int second = 0;
+    if (radix_sort_pairs(k0, v0, k1, v1, nt, 4, hist, s, second) && e == hipSuccess) {
+        e = hipErrorLaunchFailure;   // (radix_sort_pairs has taken the launch error)
+        err = "rt_build_bvh_device: radix sort: launch failed";
+    }
+    if (second) {
         std::swap(k0, k1);
         std::swap(v0, v1);
     }
-    chk("radix sort");
     (void)hipEventRecord(ev[2], s);
     // -- treelets
     (void)hipMemsetAsync(tcount, 0, 4096 * 4, s);

@@ -14,6 +14,7 @@
 
 #include "host_types.h"
 #include "rt_internal.h"
+#include "rt_prims.h"
 
 struct DevBuf {
     void* p = nullptr;
@@ -67,9 +68,6 @@ struct ListScratch {
 
 // The scene: the mesh, the BSP and the BVH in their traversal layouts, the W5 records.
 struct SceneState {
-    // host copies needed to build the triangle records on BVH upload and for the sweep
-    std::vector<float> h_pos;
-    std::vector<uint32_t> h_idx;
     uint32_t nverts = 0, ntris = 0, nmats = 0, nlights = 0;
     bool has_mesh = false, has_bsp = false, has_bvh = false, has_sweep = false;
     DevBuf pos, nrm, idx, mats, lights;

@@ -13,6 +13,7 @@
 
 #include "rt_device_common.h"
 #include "rt_empty.h"
+#include "rt_prims.h"
 
 namespace rtk {
 
@@ -164,13 +165,6 @@ __global__ void __launch_bounds__(256) k_slot_flags(DevLaunch L, const uint32_t*
     flags[s] = f;
 }
 
-__global__ void __launch_bounds__(256) k_slot_scatter(const uint32_t* flags, const uint32_t* offs, uint32_t nslots,
-                                                      uint32_t* active)
-{
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s < nslots && flags[s]) active[offs[s]] = s;   // offs[s] < the number of set flags <= nslots
-}
-
 rtempty::Cam cam_of(const float cam14[14], uint32_t W, uint32_t H, float scale)
 {
     return rtempty::make_cam(cam14, W, H, (double)scale);
@@ -219,15 +213,8 @@ int build_active_list(const DevLaunch& l, const uint32_t* empty_mask, uint32_t* 
     if (nslots == 0) return 0;
     hipLaunchKernelGGL(k_slot_flags, dim3((nslots + 255u) / 256u), dim3(256), 0, stream, l, empty_mask, nslots, flags);
     if (hipGetLastError() != hipSuccess) return RT_E_DEVICE;
-    if (int r = scan_exclusive_u32(flags, offs, nslots, scan, stream)) return r;
-    hipLaunchKernelGGL(k_slot_scatter, dim3((nslots + 255u) / 256u), dim3(256), 0, stream, flags, offs, nslots, active);
-    if (hipGetLastError() != hipSuccess) return RT_E_DEVICE;
-    uint32_t last[2] = {0, 0};
-    if (hipMemcpyAsync(&last[0], offs + (nslots - 1), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return RT_E_DEVICE;
-    if (hipMemcpyAsync(&last[1], flags + (nslots - 1), 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return RT_E_DEVICE;
-    if (hipStreamSynchronize(stream) != hipSuccess) return RT_E_DEVICE;
-    *nactive = last[0] + last[1];
-    return 0;
+    if (int r = compact_flagged(flags, offs, nslots, scan, active, nactive, stream)) return r;
+    return hipStreamSynchronize(stream) == hipSuccess ? 0 : RT_E_DEVICE;
 }
 
 }  // namespace rtk

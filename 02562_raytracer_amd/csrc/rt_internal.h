@@ -28,7 +28,7 @@ struct DevScene {
     // triangles its subtree references), nodes M, 2M, 2M+1, 4M..4M+3 (8 B each:
     // interior {axis, plane bits}, leaf {3 | (48*count) << 2, first record's byte
     // offset}; children implicit, 2i+1, 2i+2 0-based, src/data_structures/bsp_tree.rs:137-140)
-    // and the certification data of its subtree (rt_bsp_build.hip k_bsp_repack).
+    // and the certification data of its subtree (rt_layout.hip k_bsp_repack).
     const uint2* bsp_nodes;       // start of the allocation
     const float4* bsp_recs;       // = bsp_nodes + bsp_rec_off: v0, e0=v1-v0, e1=v2-v0, n=cross(e0,e1)
     uint32_t bsp_bytes;           // size of the allocation (buffer-resource range)
@@ -37,7 +37,7 @@ struct DevScene {
     uint32_t bsp_depth;           // MAX_LEVEL
     float aabb[6];                // root BboxGpu min.xyz, max.xyz
     // BVH: one allocation [32-B node records | 48-B triangle records in bvh_triangles
-    // order] (rt_scene.cpp rt_upload_bvh; links and leaf ranges as byte offsets)
+    // order] (rt_scene.cpp install_bvh; links and leaf ranges as byte offsets)
     const uint8_t* bvh_base;
     uint32_t bvh_bytes;
     uint32_t bvh_rec_off;
@@ -53,7 +53,7 @@ struct DevScene {
     // fast (RT_BSP_CULL_FAST): k1 = k3 = 0, ko = 2^-10, bsp_margin = 2^-10 x scene
     float bsp_margin;
     float cull_k1, cull_k3, cull_ko;
-    // the eye the treelets' camera terms are for (rt_bsp_build.hip
+    // the eye the treelets' camera terms are for (rt_layout.hip
     // launch_bsp_camera): rays starting exactly there use them (NaN: none)
     float cam_eye[3];
     // the cap of the cull's gap tolerance (bsp_box_miss): FLT_MAX with culling on, so a
@@ -65,7 +65,7 @@ struct DevScene {
     // so shading resolves a hit with one load (rt_walk.h resolve)
     const uint2* bsp_tm;
     // RT_BSP_CULL_SILHOUETTE: per 1-based node M, the camera term's two excluded
-    // triangles' normals and the rest's term, 16 B at [M] (rt_bsp_build.hip k_treelet_hcam)
+    // triangles' normals and the rest's term, 16 B at [M] (rt_layout.hip k_treelet_hcam)
     const uint4* bsp_sil;
     uint32_t bsp_cull_mode;   // RT_BSP_CULL_* (the host picks k_path's instantiation by it)
     // 1: some interior plane lies outside {0} U [2^-76, 2^99] in magnitude, so the walk's
@@ -308,7 +308,13 @@ struct BvhDeviceOut {
 };
 int build_bvh_device(const float4* pos, const uint4* idx, uint32_t ntris, uint32_t max_prims, int num_cus,
                      hipStream_t stream, BvhDeviceOut& out, rt_bvh_build_times* times, std::string& err);
-// traversal layout of a BVH from its reference-layout arrays (rt_upload_bvh's repack, on device)
+// The traversal layouts (rt_layout.hip), written on the device from a structure's
+// reference-layout arrays, uploaded or device-built alike.
+// recs[k] = the 48-B record {v0, e0, e1, n} of triangle ids[k] (ids null: of triangle k), k < nids;
+// tm (or null): nids x {triangle id, material}
+int launch_tri_records(const float4* pos, const uint4* idx, const uint32_t* ids, uint32_t nids, float4* recs, uint2* tm,
+                       hipStream_t stream);
+// the BVH's: 32-B node records at blob, the records of the bvh_triangles slots at blob + rec_off
 int launch_bvh_repack(const rt_gpu_node* nodes, uint32_t nnodes, uint32_t rec_off, void* blob, const float4* pos,
                       const uint4* idx, const uint32_t* ids, uint32_t nids, hipStream_t stream);
 
@@ -323,7 +329,7 @@ struct BspDeviceOut {
 };
 int build_bsp_device(const float4* pos, const uint4* idx, uint32_t ntris, uint32_t max_depth, uint32_t max_leaf,
                      int num_cus, hipStream_t stream, BspDeviceOut& out, rt_bsp_build_times* times, std::string& err);
-// traversal layout of a BSP from its reference-layout arrays (rt_upload_bsp's repack, on device):
+// traversal layout of a BSP from its reference-layout arrays (rt_layout.hip):
 // 96-B treelets (content box + 7 nodes + certification data, BSP_TREELET_BYTES)
 // then the 48-B records; box_scratch: nnodes x 64 B of device memory for the
 // content boxes and the certification data
@@ -338,13 +344,7 @@ int launch_plane_range(const uint32_t* tree, const float* planes, uint32_t nnode
 int launch_bsp_repack(const uint32_t* tree, const float* planes, uint32_t nnodes, uint32_t rec_off, void* blob,
                       const float4* pos, const uint4* idx, const uint32_t* ids, uint32_t nids, float margin,
                       void* box_scratch, uint2* tm, hipStream_t stream);
-// device primitives shared by the builders (rt_build.hip)
-// (out holds n + 1 words: the total goes to out[n])
-int scan_exclusive_u32(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* scratch, hipStream_t s);
-size_t scan_scratch_words(uint32_t n);
-int radix_sort_pairs(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t n, uint32_t passes,
-                     uint32_t* hist, hipStream_t s, int& result_in_second);
-size_t radix_hist_words(uint32_t n);
+// (the scan, the sort and the compaction the builders and the lists share: rt_prims.h)
 
 int launch_selftest_math(const float* in, float* out, uint32_t n, hipStream_t stream);
 

@@ -2,52 +2,13 @@
 // (replaces src/bindings/*.rs create_buffer_init) with the MI355X data layout repack,
 // the device builders, downloads, uniforms, environment and textures, and the scene as
 // the kernels read it (dev_scene).
-#include <thread>
-
 #include "rt_ctx.h"
 
 namespace {
 
-// 48-byte triangle record {v0, e0 = v1 - v0, e1 = v2 - v0, n = cross(e0, e1)}
-// for every slot of `ids` (IEEE f32, no contraction: identical to computing
-// them per test in the shader).
-void build_recs(const std::vector<float>& pos, const std::vector<uint32_t>& idx, const uint32_t* ids, size_t nids,
-                std::vector<float>& out)
-{
-    out.resize(nids * 12);
-    auto work = [&](size_t lo, size_t hi) {
-        for (size_t k = lo; k < hi; k++) {
-            const uint32_t* ix = &idx[(size_t)ids[k] * 4];
-            const float* a = &pos[(size_t)ix[0] * 4];
-            const float* b = &pos[(size_t)ix[1] * 4];
-            const float* c = &pos[(size_t)ix[2] * 4];
-            const float e0[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
-            const float e1[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-            const float n[3] = {e0[1] * e1[2] - e0[2] * e1[1], e0[2] * e1[0] - e0[0] * e1[2],
-                                e0[0] * e1[1] - e0[1] * e1[0]};
-            float* o = &out[k * 12];
-            o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = e0[0];
-            o[4] = e0[1]; o[5] = e0[2]; o[6] = e1[0]; o[7] = e1[1];
-            o[8] = e1[2]; o[9] = n[0]; o[10] = n[1]; o[11] = n[2];
-        }
-    };
-    const size_t nthr = std::min<size_t>(std::max(1u, std::thread::hardware_concurrency()), 32);
-    if (nids < 65536 || nthr == 1) {
-        work(0, nids);
-        return;
-    }
-    std::vector<std::thread> th;
-    const size_t chunk = (nids + nthr - 1) / nthr;
-    for (size_t t = 0; t < nthr; t++) {
-        const size_t lo = t * chunk, hi = std::min(nids, lo + chunk);
-        if (lo < hi) th.emplace_back(work, lo, hi);
-    }
-    for (auto& t : th) t.join();
-}
-
 // The traversal layout of the context's BSP (reference arrays already in
 // bsp.ref_tree / bsp.ref_planes / bsp.ids, mesh in pos / idx): content boxes,
-// 96-B treelets and the 48-B records (rt_bsp_build.hip launch_bsp_repack), and
+// 96-B treelets and the 48-B records (rt_layout.hip launch_bsp_repack), and
 // the scale of the content boxes' margins: the largest coordinate magnitude of
 // the BSP's root box (bsp_box_miss in rt_walk_bsp.h adds the ray origin's).
 int repack_bsp(rt_ctx* c, uint32_t nnodes, uint32_t nids, size_t rec_off, size_t total, const float aabb[8])
@@ -113,18 +74,36 @@ int install_bsp(rt_ctx* c, uint32_t nnodes, uint32_t nids, uint32_t max_depth, c
     return RT_OK;
 }
 
-// The BVH's traversal layout: one allocation [32-B node records | 48-B triangle records],
-// read through one buffer resource with 32-bit offsets.
-void bvh_layout(uint32_t nnodes, uint32_t nids, size_t* rec_off, size_t* total)
+// Install a BVH of nnodes nodes and nids triangle slots on the context (rt_upload_bvh,
+// rt_build_bvh_device).  One allocation [32-B node records | 48-B triangle records], read
+// through one buffer resource with 32-bit offsets, laid out on the device by
+// launch_bvh_repack from the reference arrays, which place() puts into bvh.ref / bvh.ids
+// once the size is known to fit.  who: the caller's name in the messages.
+template <class Place>
+int install_bvh(rt_ctx* c, uint32_t nnodes, uint32_t nids, const char* who, Place&& place)
 {
-    *rec_off = ((size_t)nnodes * 32 + 255) & ~(size_t)255;
-    *total = *rec_off + (size_t)nids * 48;
+    SceneState& s = c->scene;
+    const size_t rec_off = ((size_t)nnodes * 32 + 255) & ~(size_t)255;
+    const size_t total = rec_off + (size_t)nids * 48;
+    if (total >= ((size_t)1 << 32))
+        return fail(c, RT_E_UNSUPPORTED, std::string(who) + ": BVH nodes + records must stay below 4 GiB");
+    HIPCHK(c, s.bvh.nodes.alloc(total));
+    if (int r = place()) return r;
+    if (rtk::launch_bvh_repack(s.bvh.ref.as<rt_gpu_node>(), nnodes, (uint32_t)rec_off, s.bvh.nodes.p, s.pos.as<float4>(),
+                               s.idx.as<uint4>(), s.bvh.ids.as<uint32_t>(), nids, c->stream))
+        return fail(c, RT_E_DEVICE, std::string(who) + ": repack launch failed");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    s.bvh.rec_off = (uint32_t)rec_off;
+    s.bvh.nnodes = nnodes;
+    s.bvh.nids = nids;
+    s.has_bvh = true;
+    return RT_OK;
 }
 
 }  // namespace
 
 // The camera terms of the treelets for the uniforms' eye (certified culling,
-// rt_bsp_build.hip launch_bsp_camera): recomputed when the eye moves.
+// rt_layout.hip launch_bsp_camera): recomputed when the eye moves.
 int ensure_hcam(rt_ctx* c)
 {
     SceneState& s = c->scene;
@@ -146,20 +125,19 @@ int ensure_hcam(rt_ctx* c)
 }
 
 // The W5 modes' flat record array (rt_internal.h SweepScene): record i is triangle i of
-// the index buffer -- the BSP repack is in treeIds order and cannot serve -- built from
-// the host copy of the mesh at the first W5 render after an upload, zero-padded to a
-// whole block of the sweep.
+// the index buffer -- the BSP repack is in treeIds order and cannot serve -- written by
+// the record kernel in identity order (rt_layout.hip launch_tri_records) at the first W5
+// render after an upload, zero-padded to a whole block of the sweep.
 int ensure_sweep(rt_ctx* c)
 {
     SceneState& s = c->scene;
     if (s.has_sweep) return RT_OK;
-    std::vector<uint32_t> ids(s.ntris);
-    for (uint32_t i = 0; i < s.ntris; i++) ids[i] = i;
-    std::vector<float> recs;
-    build_recs(s.h_pos, s.h_idx, ids.data(), ids.size(), recs);
     const size_t padded = ((size_t)s.ntris + rtk::SWEEP_PAD_RECS) / rtk::SWEEP_PAD_RECS * rtk::SWEEP_PAD_RECS;
-    recs.resize(padded * 12, 0.0f);
-    if (int r = upload(c, s.sweep_recs, recs.data(), recs.size() * 4)) return r;
+    HIPCHK(c, s.sweep_recs.alloc(padded * 48));
+    HIPCHK(c, hipMemsetAsync(s.sweep_recs.as<uint8_t>() + (size_t)s.ntris * 48, 0, (padded - s.ntris) * 48, c->stream));
+    if (rtk::launch_tri_records(s.pos.as<float4>(), s.idx.as<uint4>(), nullptr, s.ntris, s.sweep_recs.as<float4>(), nullptr,
+                                c->stream))
+        return fail(c, RT_E_DEVICE, "W5 records: launch failed");
     s.has_sweep = true;
     return RT_OK;
 }
@@ -243,15 +221,13 @@ int rt_upload_mesh(rt_ctx* c, const float* pos_vec4, const float* nrm_vec4, uint
     HIPCHK(c, hipStreamSynchronize(c->stream));
     SceneState& s = c->scene;
     s.has_mesh = s.has_bsp = s.has_bvh = s.has_sweep = false;
-    s.h_pos.assign(pos_vec4, pos_vec4 + (size_t)nverts * 4);
-    s.h_idx.assign(idx_vec4u, idx_vec4u + (size_t)ntris * 4);
     std::vector<float> nrm;
     if (nrm_vec4) nrm.assign(nrm_vec4, nrm_vec4 + (size_t)nverts * 4);
     else nrm.assign((size_t)nverts * 4, 0.0f);
     int r;
-    if ((r = upload(c, s.pos, s.h_pos.data(), s.h_pos.size() * 4))) return r;
+    if ((r = upload(c, s.pos, pos_vec4, (size_t)nverts * 16))) return r;
     if ((r = upload(c, s.nrm, nrm.data(), nrm.size() * 4))) return r;
-    if ((r = upload(c, s.idx, s.h_idx.data(), s.h_idx.size() * 4))) return r;
+    if ((r = upload(c, s.idx, idx_vec4u, (size_t)ntris * 16))) return r;
     if ((r = upload(c, s.mats, mats, (size_t)nmats * sizeof(rt_material)))) return r;
     if ((r = upload(c, s.lights, lights.data(), lights.size() * 4))) return r;
     s.nverts = nverts;
@@ -263,7 +239,7 @@ int rt_upload_mesh(rt_ctx* c, const float* pos_vec4, const float* nrm_vec4, uint
     s.mesh_scale = 0.0f;
     for (size_t v = 0; v < nverts; v++)
         for (int a = 0; a < 3; a++) {
-            const float x = s.h_pos[4 * v + a];
+            const float x = pos_vec4[4 * v + a];
             if (x - x == 0.0f) s.mesh_scale = std::max(s.mesh_scale, x < 0 ? -x : x);
         }
     on_new_mesh(c);
@@ -337,44 +313,13 @@ int rt_upload_bvh(rt_ctx* c, const rt_gpu_node* nodes, uint32_t nnodes, const ui
             stack.push_back(n.offset_ptr);
         }
     }
-    std::vector<float> recs;
-    build_recs(s.h_pos, s.h_idx, tri_ids, nids, recs);
     if (int r = set_dev(c)) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     s.has_bvh = false;
-    int r;
-    // Node record: {min.xyz, w0} {max.xyz, w1}; interior: w0 = byte offset of the right
-    // child (offset_ptr), w1 = 0; leaf: w0 = byte offset of its first triangle record,
-    // w1 = 48*n_prims.
-    size_t rec_off, total;
-    bvh_layout(nnodes, nids, &rec_off, &total);
-    if (total >= ((size_t)1 << 32))
-        return fail(c, RT_E_UNSUPPORTED, "rt_upload_bvh: BVH nodes + records must stay below 4 GiB");
-    {
-        std::vector<uint8_t> blob(total, 0);
-        for (uint32_t i = 0; i < nnodes; i++) {
-            const rt_gpu_node& n = nodes[i];
-            uint32_t* o = reinterpret_cast<uint32_t*>(blob.data() + 32 * (size_t)i);
-            memcpy(o, n.min, 12);
-            memcpy(o + 4, n.max, 12);
-            if (n.n_prims > 0) {
-                o[3] = (uint32_t)(rec_off + 48ull * n.offset_ptr);
-                o[7] = 48u * n.n_prims;
-            } else {
-                o[3] = (uint32_t)(32ull * n.offset_ptr);
-                o[7] = 0u;
-            }
-        }
-        memcpy(blob.data() + rec_off, recs.data(), recs.size() * 4);
-        if ((r = upload(c, s.bvh.nodes, blob.data(), blob.size()))) return r;
-    }
-    s.bvh.rec_off = (uint32_t)rec_off;
-    if ((r = upload(c, s.bvh.ids, tri_ids, (size_t)nids * 4))) return r;
-    if ((r = upload(c, s.bvh.ref, nodes, (size_t)nnodes * sizeof(rt_gpu_node)))) return r;
-    s.bvh.nnodes = nnodes;
-    s.bvh.nids = nids;
-    s.has_bvh = true;
-    return RT_OK;
+    return install_bvh(c, nnodes, nids, "rt_upload_bvh", [&] {
+        if (int r = upload(c, s.bvh.ids, tri_ids, (size_t)nids * 4)) return r;
+        return upload(c, s.bvh.ref, nodes, (size_t)nnodes * sizeof(rt_gpu_node));
+    });
 }
 
 int rt_build_bvh_device(rt_ctx* c, uint32_t max_prims, rt_bvh_build_times* times)
@@ -394,25 +339,13 @@ int rt_build_bvh_device(rt_ctx* c, uint32_t max_prims, rt_bvh_build_times* times
     if (o.nodes) nodes_ref.adopt(o.nodes, (size_t)o.nnodes * sizeof(rt_gpu_node));
     if (o.ids) ids.adopt(o.ids, (size_t)o.nids * 4);
     if (r) return fail(c, r, err);
-    // traversal layout, as rt_upload_bvh (records of the bvh_triangles slots)
-    size_t rec_off, total;
-    bvh_layout(o.nnodes, o.nids, &rec_off, &total);
-    if (total >= ((size_t)1 << 32))
-        return fail(c, RT_E_UNSUPPORTED, "rt_build_bvh_device: BVH nodes + records must stay below 4 GiB");
-    HIPCHK(c, s.bvh.nodes.alloc(total));
-    if (rtk::launch_bvh_repack(nodes_ref.as<rt_gpu_node>(), o.nnodes, (uint32_t)rec_off, s.bvh.nodes.p,
-                               s.pos.as<float4>(), s.idx.as<uint4>(), ids.as<uint32_t>(), o.nids, c->stream))
-        return fail(c, RT_E_DEVICE, "rt_build_bvh_device: repack launch failed");
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    s.bvh.ref.adopt(nodes_ref.p, nodes_ref.n);
-    nodes_ref.p = nullptr;
-    s.bvh.ids.adopt(ids.p, ids.n);
-    ids.p = nullptr;
-    s.bvh.rec_off = (uint32_t)rec_off;
-    s.bvh.nnodes = o.nnodes;
-    s.bvh.nids = o.nids;
-    s.has_bvh = true;
-    return RT_OK;
+    return install_bvh(c, o.nnodes, o.nids, "rt_build_bvh_device", [&] {
+        s.bvh.ref.adopt(nodes_ref.p, nodes_ref.n);
+        nodes_ref.p = nullptr;
+        s.bvh.ids.adopt(ids.p, ids.n);
+        ids.p = nullptr;
+        return (int)RT_OK;
+    });
 }
 
 int rt_build_bsp_device(rt_ctx* c, uint32_t max_depth, uint32_t max_leaf, rt_bsp_build_times* times)

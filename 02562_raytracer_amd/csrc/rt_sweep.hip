@@ -39,7 +39,7 @@ typedef const __attribute__((address_space(4))) sw4f* CRecs;   // uniform addres
 // The quantities of intersect_triangle (w5e2.wgsl:251-281) that precede its
 // divisions, on a pre-transformed record r0 = (v0.xyz, e0.x), r1 = (e0.yz, e1.xy),
 // r2 = (e1.z, n.xyz); e0, e1 and n = cross(e0, e1) do not depend on the ray
-// (rt_scene.cpp build_recs evaluates them with the shader's operations).
+// (rt_layout.hip k_tri_records evaluates them with the shader's operations).
 struct TriPre {
     float a, b, c, denom;
 };

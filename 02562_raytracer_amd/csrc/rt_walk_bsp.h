@@ -57,7 +57,7 @@ __device__ __forceinline__ bool bsp_pop(const float* stk, Trav& t)
 // divides out the exact t (the wave runs the exact path in nearly every trip
 // anyway: 28 % of decisions need it), with no approximate test first.
 // chk (wave-uniform, k_path's per-check choice): some lane's ray, or the scene's planes
-// (rt_bsp_build.hip k_plane_range), may put x outside the range where rt_div_by_recip
+// (rt_layout.hip k_plane_range), may put x outside the range where rt_div_by_recip
 // is exact.  Without it every x is 0 or inside the range (x = +-0 gives a zero, whose
 // sign may differ from x / denom's for -0: t values are only compared, and every
 // comparison sees +0 == -0, tests/native/fastdiv_check.c), so the per-lane test and its
@@ -107,7 +107,7 @@ __device__ __forceinline__ uint32_t bsp_decide(float* stk, const uint2 n, uint32
 // (one memory round trip per trip):
 //   * a lane inside a leaf tests its 48-B record (and the next one, below);
 //   * a lane walking nodes reads the 96-B treelet of its node m
-//     (rt_bsp_build.hip k_bsp_repack: m's content box | nodes m | 2m, 2m+1 |
+//     (rt_layout.hip k_bsp_repack: m's content box | nodes m | 2m, 2m+1 |
 //     4m..4m+3), tests the content box (bsp_walk) and walks up to three
 //     levels with no further load.
 // Treelets and records share one buffer resource (out-of-range reads are 0).

@@ -455,7 +455,7 @@ int rt_download_bsp(rt_ctx* ctx, uint32_t* tree, float* planes, uint32_t cap_nod
  * BSP walk's 96-B treelets (slot 0 unused, then one per 1-based node M:
  * content box, nodes M, 2M, 2M+1, 4M..4M+3, and the certified culling's data
  * -- F bf16 | camera term G f16 << 16, normal-box centre and radius as f16;
- * rt_bsp_build.hip k_bsp_repack) to dst, (nnodes + 1) * 96 bytes, followed by
+ * rt_layout.hip k_bsp_repack) to dst, (nnodes + 1) * 96 bytes, followed by
  * RT_BSP_CULL_SILHOUETTE's node data ((nnodes + 1) * 16 bytes: the two excluded
  * triangles' n* / E^2 as f16 triples, the rest's camera term G_x f16; zero when
  * not computed), after bringing the camera terms up to date for the uniforms'

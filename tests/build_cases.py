@@ -5,8 +5,8 @@ with w = 1, indices uint32 (nt, 4)) for Mesh.from_arrays.  Triangle t owns
 vertices 3t, 3t+1, 3t+2; nothing is shared, so a case can be cut or joined
 by rows.
 
-The cases are sized by the device builders' own constants (rt_build.hip:
-kTile 2048, kScanBlock 4096, the 1024-thread scans, the 4096-treelet cap;
+The cases are sized by the device builders' own constants (rt_prims.hip:
+kTile 2048, kScanBlock 4096; rt_build.hip: the 1024-thread scans, the 4096-treelet cap;
 rt_bsp_build.hip: kSlotsPerBlock 4096, `per` of k_tri_boxes); what each test
 does with them is said in tests/test_gpu_build_edges.py,
 tests/test_gpu_bsp_build_edges.py and tests/test_gpu_bsp_depths.py, and

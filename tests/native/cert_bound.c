@@ -77,7 +77,7 @@ static float cert_margin(v3 v0, v3 v1, v3 v2, v3 o, v3 w, float scene, float bmi
         bmin[a] = fminf(fminf(cmp(vs[0], a), cmp(vs[1], a)), cmp(vs[2], a));
         bmax[a] = fmaxf(fmaxf(cmp(vs[0], a), cmp(vs[1], a)), cmp(vs[2], a));
     }
-    /* the repack's certification data (rt_bsp_build.hip k_leaf_boxes / k_bsp_repack) */
+    /* the repack's certification data (rt_layout.hip k_leaf_boxes / k_bsp_repack) */
     v3 e0 = sub(v1, v0), e1 = sub(v2, v0);
     double n[3] = {(double)e0.y * e1.z - (double)e0.z * e1.y, (double)e0.z * e1.x - (double)e0.x * e1.z,
                    (double)e0.x * e1.y - (double)e0.y * e1.x};
@@ -110,14 +110,14 @@ static float cert_margin(v3 v0, v3 v1, v3 v2, v3 o, v3 w, float scene, float bmi
     float den = fmaxf(F, dlb2 - (20.0f * 0x1p-24f) * w1);
     if (g_cam) {
         /* the camera bound, with the ray's origin as the eye: H = |(v0 - o) . n*| / E2
-         * rounded down (rt_bsp_build.hip tri_hcam), bf16-truncated as the treelet stores it */
+         * rounded down (rt_layout.hip tri_hcam), bf16-truncated as the treelet stores it */
         double dd[3] = {(double)v0.x - o.x, (double)v0.y - o.y, (double)v0.z - o.z};
         double dot = dd[0] * n[0] + dd[1] * n[1] + dd[2] * n[2];
         double err = 0x1p-45 * (fabs(dd[0] * n[0]) + fabs(dd[1] * n[1]) + fabs(dd[2] * n[2]));
         double eta = fabs(dot) - err;
         float H = E2 > 0 ? (eta > 0 ? (float)(eta / E2 * (1.0 - 0x1p-19)) : 0.0f) : INFINITY;
         H = nextafterf(H, 0.0f);
-        /* the treelet's camera term G (rt_bsp_build.hip k_treelet_hcam): from H (f32),
+        /* the treelet's camera term G (rt_layout.hip k_treelet_hcam): from H (f32),
          * the box's L1 / L-inf distances to the eye (f64, rounded up), rounded down,
          * an f16 rounded down as the treelet stores it */
         double D1e = 0.0, Dinfe = 0.0;

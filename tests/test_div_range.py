@@ -1,5 +1,5 @@
 """The operand range behind the BSP walk's unchecked plane divisions
-(rt_walk_bsp.h bsp_decide with chk = 0; rt_bsp_build.hip k_plane_range; k_path's
+(rt_walk_bsp.h bsp_decide with chk = 0; rt_layout.hip k_plane_range; k_path's
 per-check ballot).  rt_div_by_recip (include/rt_detmath.h) equals IEEE division for
 x = 0 or 2^-100 <= |x| <= 2^100 (tests/test_fastdiv.py).  The walk skips its per-lane
 range test when every interior plane and every tracing ray's origin coordinate is 0 or

@@ -15,7 +15,7 @@ The boundaries, and the case just below / at / just above each:
     are n = 4097 / 4098, and 8191 is two full blocks -- and over nodes + 1; the
     leaf scan over the leaf count: 2049 leaves below, 4096 at, 4097 above
     (test_leaf_counts);
-  * kTile = 2048 of the leaf list's radix sort (rt_build.hip; (max_depth + 7) / 8
+  * kTile = 2048 of the leaf list's radix sort (rt_prims.hip; (max_depth + 7) / 8
     passes over keys below 2^max_depth): 2047 / 2048 / 2049 leaves
     (test_leaf_counts), and 1, 2 and 3 passes at the depths of test_depth_and_leaf;
   * `per` of k_tri_boxes, triangles per thread, 1 up to 65,536 triangles and 2

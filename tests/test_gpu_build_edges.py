@@ -6,7 +6,7 @@ oracle on every case here (tests/test_build_cases.py).  Meshes:
 tests/build_cases.py.
 
 The boundaries, and the case just below / at / just above each:
-  * kTile = 2048, the radix sort's keys per block (k_rs_hist, k_rs_scatter: the
+  * kTile = 2048, the radix sort's keys per block (rt_prims.hip k_rs_hist, k_rs_scatter: the
     last tile is partial, its tail keys must not be ranked): scatter 2047 /
     2048 / 2049, and 4095 / 4096 / 4097 for two full tiles;
   * the 1024-thread single-block scan k_rs_scan, which the sort runs over
@@ -16,7 +16,7 @@ The boundaries, and the case just below / at / just above each:
   * k_treelet_list, 1024 threads over the 4096 prefix counts (4 each whatever
     the mesh; what changes is how many are non-zero and where): lattice 1023 /
     1024 / 1025 treelets;
-  (kScanBlock = 4096 of scan_exclusive_u32 is in this file too, but the BVH
+  (kScanBlock = 4096 of scan_exclusive_u32 is in rt_prims.hip too, but the BVH
   build does not call it: tests/test_gpu_bsp_build_edges.py, whose builder does)
   * one wave and one block of the per-triangle kernels: scatter 63 / 64 / 65
     and 255 / 256 / 257; 2 and 3 triangles for the smallest trees;

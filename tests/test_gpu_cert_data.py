@@ -1,6 +1,6 @@
 """The data the certified culling's proof rests on (DESIGN.md section 4
 "Certified culling"), as the GPU repack wrote it into the BSP treelets
-(rt_bsp_build.hip k_leaf_boxes / k_node_boxes / k_bsp_repack / k_treelet_hcam),
+(rt_layout.hip k_leaf_boxes / k_node_boxes / k_bsp_repack / k_treelet_hcam),
 checked node by node against an f64 recomputation on the host from the mesh and
 the reference-layout tree (rt_download_bsp):
 
@@ -57,7 +57,7 @@ def _check(rt, mesh, eye, target):
     n = tree.shape[0]
     assert tl.shape == (n + 1, 24) and sil.shape == (n + 1, 4)
 
-    # per triangle, from the records' f32 edges (k_tri_records2)
+    # per triangle, from the records' f32 edges (rt_layout.hip k_tri_records)
     P = V[:, :3].astype(np.float32)
     v0, v1, v2 = P[I[:, 0]], P[I[:, 1]], P[I[:, 2]]
     e0 = (v1 - v0).astype(np.float64)

@@ -1,5 +1,5 @@
 """The BSP walk's plane divisions in a scene whose planes leave rt_div_by_recip's
-exact range (rt_walk_bsp.h bsp_decide's chk; rt_bsp_build.hip k_plane_range): the
+exact range (rt_walk_bsp.h bsp_decide's chk; rt_layout.hip k_plane_range): the
 bunny stand-in plus one degenerate triangle at (2^101, 2^101, 2^101), so the root
 splits at 2^100 > 2^99 and the scene's flag keeps every decision's range check.  The
 W9E1 frame (k_path) equals the oracle's bit for bit, as does the same frame without

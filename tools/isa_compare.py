@@ -2,13 +2,15 @@
 and the working tree: the check that a refactor left the compiled kernels alone.
 
 Cross-compiles every .hip file of the library in both trees, each with the flags its
-Makefile rule gives it plus --cuda-device-only -S, and compares every kernel symbol's body (up to .Lfunc_end) and its .amdhsa_kernel block.  Before comparing,
+Makefile rule gives it plus --cuda-device-only -S, and compares every kernel symbol's body (up to .Lfunc_end) and its .amdhsa_kernel block.
+Kernels are matched by symbol across the whole library, not per file, so a kernel that
+moved to another file shows as identical, not as gone plus new.  Before comparing,
 `;` comments are stripped, whitespace is collapsed and the function number leaves the
 basic-block labels (.LBB12_3 -> BB_3): removing or reordering a function renumbers those
 labels and shifts the comment columns, and nothing else.  usage:
   python tools/isa_compare.py [base revision, default HEAD]
-prints one line per file and every kernel that is new, gone or changed; exit status 1
-if any is."""
+prints the totals and every kernel that is new, gone or changed, with its VGPRs, LDS and
+scratch on both sides; exit status 1 if any is."""
 import os
 import re
 import subprocess
@@ -20,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "02562_raytracer_amd"
 # the Makefile's OBJS built from .hip files; those of NO_SLP get -fno-slp-vectorize there
 FILES = ["rt_kernels.hip", "rt_sweep.hip", "rt_analytic.hip", "rt_worksheet1.hip", "rt_noise.hip", "rt_adaptive.hip",
-         "rt_denoise.hip", "rt_empty.hip", "rt_build.hip", "rt_bsp_build.hip"]
+         "rt_denoise.hip", "rt_empty.hip", "rt_prims.hip", "rt_layout.hip", "rt_build.hip", "rt_bsp_build.hip"]
 NO_SLP = {"rt_kernels.hip", "rt_sweep.hip", "rt_analytic.hip", "rt_worksheet1.hip", "rt_noise.hip", "rt_adaptive.hip",
           "rt_denoise.hip"}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -56,27 +58,52 @@ def kernels(s):
     return out
 
 
+def hip_files(root):
+    """Those of FILES a tree has (a base revision may be from before a file was split off)"""
+    return [f for f in FILES if os.path.exists(os.path.join(root, PKG, "csrc", f))]
+
+
+def resources(desc):
+    """VGPRs, LDS bytes and scratch bytes per lane of a normalised .amdhsa_kernel block"""
+    def get(key):
+        m = re.search(r"\." + key + r" (\d+)", desc)
+        return int(m.group(1)) if m else 0
+    return (f"{get('amdhsa_next_free_vgpr')} VGPRs, {get('amdhsa_group_segment_fixed_size')} B LDS, "
+            f"{get('amdhsa_private_segment_fixed_size')} B scratch")
+
+
 def main():
     base = sys.argv[1] if len(sys.argv) > 1 else "HEAD"
-    changed = False
     with tempfile.TemporaryDirectory() as tmp:
         tar = subprocess.run(["git", "-C", ROOT, "archive", base, PKG + "/csrc", "include"], check=True,
                              capture_output=True).stdout
         subprocess.run(["tar", "-x", "-C", tmp], input=tar, check=True)
+        sides = {"base": tmp, "tree": ROOT}
         with ThreadPoolExecutor(8) as pool:
             jobs = {(side, f): pool.submit(device_asm, root, f, os.path.join(tmp, f"{side}_{f}.s"))
-                    for side, root in (("base", tmp), ("tree", ROOT)) for f in FILES}
-        for f in FILES:
-            a, b = kernels(jobs["base", f].result()), kernels(jobs["tree", f].result())
-            gone, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
-            diff = sorted(k for k in set(a) & set(b) if a[k] != b[k])
-            print(f"{f}: {len(a)} kernels in {base}, {len(b)} in the tree, {len(set(a) & set(b)) - len(diff)} identical, "
-                  f"{len(diff)} changed, {len(gone)} gone, {len(new)} new")
-            for what, names in (("changed", diff), ("gone", gone), ("new", new)):
-                for k in names:
-                    print(f"  {what}: {k}")
-            changed |= bool(gone or new or diff)
-    return 1 if changed else 0
+                    for side, root in sides.items() for f in hip_files(root)}
+        # kernels are matched by symbol across the whole library: one that moved to another
+        # file is the same kernel (where: the file that holds it on each side)
+        lib = {side: {} for side in sides}
+        for (side, f), job in jobs.items():
+            for name, k in kernels(job.result()).items():
+                assert name not in lib[side], f"{name} in two files of {side}"
+                lib[side][name] = (f, *k)
+    a, b = lib["base"], lib["tree"]
+    gone, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+    both = sorted(set(a) & set(b))
+    diff = [k for k in both if a[k][1:] != b[k][1:]]
+    moved = [k for k in both if a[k][0] != b[k][0]]
+    print(f"{len(a)} kernels in {base}, {len(b)} in the tree: {len(both) - len(diff)} identical "
+          f"({sum(k not in diff for k in moved)} of them in another file), {len(diff)} changed, {len(gone)} gone, "
+          f"{len(new)} new")
+    for k in diff:
+        where = a[k][0] if a[k][0] == b[k][0] else f"{a[k][0]} -> {b[k][0]}"
+        print(f"  changed: {k} ({where}): {resources(a[k][2])} -> {resources(b[k][2])}")
+    for what, names, side in (("gone", gone, a), ("new", new, b)):
+        for k in names:
+            print(f"  {what}: {k} ({side[k][0]}): {resources(side[k][2])}")
+    return 1 if gone or new or diff else 0
 
 
 if __name__ == "__main__":

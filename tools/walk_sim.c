@@ -189,7 +189,7 @@ static double cert_margin_c(const double* c, v3 o, v3 d, const float* b)
     double fl = 1e-10 / E2;
     if (g_cert_floor_only || den < fl) den = fl;
     if (g_hcam && o.x == g_eye.x && o.y == g_eye.y && o.z == g_eye.z) {
-        /* camera ray: den >= winf (Hmin - 128u D1) / Dinf (rt_bsp_build.hip k_treelet_hcam) */
+        /* camera ray: den >= winf (Hmin - 128u D1) / Dinf (rt_layout.hip k_treelet_hcam) */
         double Dinf = 0, winf = fmax(fmax(fabs(d.x), fabs(d.y)), fabs(d.z));
         for (int k = 0; k < 3; k++) {
             double a = fabs(b[k] - comp(o, k)), e = fabs(b[3 + k] - comp(o, k));
