@@ -6,6 +6,7 @@ test can never pass on a silent CPU path.
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -22,12 +23,63 @@ RT_E_NOT_READY = -4
 RT_E_IO = -5
 RT_E_UNSUPPORTED = -6
 
+# The mode table: the static mirror of csrc/rt_modes.cpp (rt_mode_describe; tests/test_modes.py holds
+# the two together), one row per rt_mode in enum order.  Every list of modes below is derived from it.
+RT_FAMILY_WORKSHEET1, RT_FAMILY_ANALYTIC, RT_FAMILY_SWEEP, RT_FAMILY_PRIMARY, RT_FAMILY_DIRECT, RT_FAMILY_PATH = range(6)
+MESH_FAMILIES = (RT_FAMILY_SWEEP, RT_FAMILY_PRIMARY, RT_FAMILY_DIRECT, RT_FAMILY_PATH)   # RT_FAMILY_NEEDS_MESH
+TREE_FAMILIES = (RT_FAMILY_PRIMARY, RT_FAMILY_DIRECT, RT_FAMILY_PATH)                    # RT_FAMILY_NEEDS_TREE
+RT_MODEF_PROGRESSIVE, RT_MODEF_TEXTURE0, RT_MODEF_LINEAR_DISPLAY, RT_MODEF_AREA_LIGHTS = 1, 2, 4, 8
+ModeRow = namedtuple("ModeRow", "name shader family flags")
+_PROG, _AREA = RT_MODEF_PROGRESSIVE, RT_MODEF_AREA_LIGHTS
+MODE_TABLE = tuple(ModeRow(*r) for r in (
+    ("W1E6", "w1e6.wgsl", RT_FAMILY_WORKSHEET1, 0),
+    ("W6E1", "w6e1.wgsl", RT_FAMILY_PRIMARY, 0),
+    ("PROJECT", "project.wgsl", RT_FAMILY_PRIMARY, 0),
+    ("W7E3", "w7e3.wgsl", RT_FAMILY_PATH, _PROG | _AREA),
+    ("W9E1", "w9e1.wgsl", RT_FAMILY_PATH, _PROG),
+    ("W8E1", "w8e1.wgsl", RT_FAMILY_PATH, _PROG | _AREA),
+    ("W8E2", "w8e2.wgsl", RT_FAMILY_PATH, _PROG | _AREA),
+    ("W8E3", "w8e3.wgsl", RT_FAMILY_PATH, _PROG | _AREA),
+    ("W9E2", "w9e2.wgsl", RT_FAMILY_PATH, _PROG),
+    ("W6E2", "w6e2.wgsl", RT_FAMILY_DIRECT, 0),
+    ("W7E1", "w7e1.wgsl", RT_FAMILY_DIRECT, _PROG),
+    ("W7E2", "w7e2.wgsl", RT_FAMILY_DIRECT, _PROG),
+    ("W6E3", "w6e3.wgsl", RT_FAMILY_DIRECT, 0),
+    ("W9E3", "w9e3.wgsl", RT_FAMILY_PATH, _PROG),
+    ("W5E2", "w5e2.wgsl", RT_FAMILY_SWEEP, 0),
+    ("W5E3", "w5e3.wgsl", RT_FAMILY_SWEEP, 0),
+    ("W5E4", "w5e4.wgsl", RT_FAMILY_SWEEP, 0),
+    ("W5E5", "w5e5.wgsl", RT_FAMILY_SWEEP, 0),
+    ("W2E1", "w2e1.wgsl", RT_FAMILY_ANALYTIC, 0),
+    ("W2E2", "w2e2.wgsl", RT_FAMILY_ANALYTIC, 0),
+    ("W2E3", "w2e3.wgsl", RT_FAMILY_ANALYTIC, 0),
+    ("W2E4", "w2e4.wgsl", RT_FAMILY_ANALYTIC, 0),
+    ("W2E5", "w2e5.wgsl", RT_FAMILY_ANALYTIC, 0),
+    ("W3E1", "w3e1.wgsl", RT_FAMILY_ANALYTIC, RT_MODEF_TEXTURE0),
+    ("W3E2", "w3e2.wgsl", RT_FAMILY_ANALYTIC, RT_MODEF_TEXTURE0),
+    ("W3E3", "w3e3.wgsl", RT_FAMILY_ANALYTIC, RT_MODEF_TEXTURE0),
+    ("W3E4", "w3e4.wgsl", RT_FAMILY_ANALYTIC, RT_MODEF_TEXTURE0),
+    ("W1E2", "w1e2.wgsl", RT_FAMILY_WORKSHEET1, RT_MODEF_LINEAR_DISPLAY),
+    ("W1E3", "w1e3.wgsl", RT_FAMILY_WORKSHEET1, RT_MODEF_LINEAR_DISPLAY),
+    ("W1E4", "w1e4.wgsl", RT_FAMILY_WORKSHEET1, 0),
+    ("W1E5", "w1e5.wgsl", RT_FAMILY_WORKSHEET1, 0),
+))
+RT_MODE_COUNT = len(MODE_TABLE)
+MODES = {r.name: i for i, r in enumerate(MODE_TABLE)}            # name -> rt_mode value
+# the enumerators by name, in the table's order (tests/test_modes.py checks each against its row)
 (RT_MODE_W1E6, RT_MODE_W6E1, RT_MODE_PROJECT, RT_MODE_W7E3, RT_MODE_W9E1, RT_MODE_W8E1, RT_MODE_W8E2, RT_MODE_W8E3,
  RT_MODE_W9E2, RT_MODE_W6E2, RT_MODE_W7E1, RT_MODE_W7E2, RT_MODE_W6E3, RT_MODE_W9E3,
  RT_MODE_W5E2, RT_MODE_W5E3, RT_MODE_W5E4, RT_MODE_W5E5,
  RT_MODE_W2E1, RT_MODE_W2E2, RT_MODE_W2E3, RT_MODE_W2E4, RT_MODE_W2E5,
  RT_MODE_W3E1, RT_MODE_W3E2, RT_MODE_W3E3, RT_MODE_W3E4,
- RT_MODE_W1E2, RT_MODE_W1E3, RT_MODE_W1E4, RT_MODE_W1E5) = range(31)
+ RT_MODE_W1E2, RT_MODE_W1E3, RT_MODE_W1E4, RT_MODE_W1E5) = range(RT_MODE_COUNT)
+MODE_OF_SHADER = {r.shader: r for r in MODE_TABLE}                # shader file -> row
+
+
+def _modes(keep):
+    return tuple(r.name for r in MODE_TABLE if keep(r))
+
+
 RT_TRAVERSE_BSP, RT_TRAVERSE_BVH, RT_TRAVERSE_NONE = range(3)
 RT_OPT_DETAIL_COUNTERS = 1
 RT_OPT_WAVES_PER_CU = 2
@@ -46,30 +98,21 @@ BSP_TREELET_BYTES = 96   # rt_internal.h: the BSP walk's treelet (rt_download_bs
 RT_OPT_KERNEL_TIMING = 7
 RT_COMM_ID_BYTES = 128
 
-MODES = {"W1E6": RT_MODE_W1E6, "W6E1": RT_MODE_W6E1, "PROJECT": RT_MODE_PROJECT, "W7E3": RT_MODE_W7E3,
-         "W9E1": RT_MODE_W9E1, "W8E1": RT_MODE_W8E1, "W8E2": RT_MODE_W8E2, "W8E3": RT_MODE_W8E3,
-         "W9E2": RT_MODE_W9E2, "W6E2": RT_MODE_W6E2, "W7E1": RT_MODE_W7E1, "W7E2": RT_MODE_W7E2,
-         "W6E3": RT_MODE_W6E3, "W9E3": RT_MODE_W9E3,
-         "W5E2": RT_MODE_W5E2, "W5E3": RT_MODE_W5E3, "W5E4": RT_MODE_W5E4, "W5E5": RT_MODE_W5E5,
-         "W2E1": RT_MODE_W2E1, "W2E2": RT_MODE_W2E2, "W2E3": RT_MODE_W2E3, "W2E4": RT_MODE_W2E4,
-         "W2E5": RT_MODE_W2E5, "W3E1": RT_MODE_W3E1, "W3E2": RT_MODE_W3E2, "W3E3": RT_MODE_W3E3,
-         "W3E4": RT_MODE_W3E4,
-         "W1E2": RT_MODE_W1E2, "W1E3": RT_MODE_W1E3, "W1E4": RT_MODE_W1E4, "W1E5": RT_MODE_W1E5}
 # the brute-force W5 scenes: a triangle sweep over the mesh alone (RT_TRAVERSE_NONE, no BSP / BVH)
-SWEEP_MODES = ("W5E2", "W5E3", "W5E4", "W5E5")
+SWEEP_MODES = _modes(lambda r: r.family == RT_FAMILY_SWEEP)
 # the analytic W2 / W3 scenes: three constant objects, materials, bounces (RT_TRAVERSE_NONE, no mesh);
 # the W3 ones sample texture0 (rt_set_texture)
-ANALYTIC_MODES = ("W2E1", "W2E2", "W2E3", "W2E4", "W2E5", "W3E1", "W3E2", "W3E3", "W3E4")
-TEXTURED_MODES = ("W3E1", "W3E2", "W3E3", "W3E4")
+ANALYTIC_MODES = _modes(lambda r: r.family == RT_FAMILY_ANALYTIC)
+TEXTURED_MODES = _modes(lambda r: r.flags & RT_MODEF_TEXTURE0)
 # the worksheet-1 scenes before W1E6: the uniforms alone (RT_TRAVERSE_NONE, no mesh); the shaders of
 # LINEAR_DISPLAY_MODES return their colour without pow(., 1.5) (rt_frame_rgba8_mode)
-WORKSHEET1_MODES = ("W1E2", "W1E3", "W1E4", "W1E5")
-LINEAR_DISPLAY_MODES = ("W1E2", "W1E3")
-# progressive path tracers (per-iteration samples folded in order)
-PATH_MODES = ("W7E3", "W9E1", "W8E1", "W8E2", "W8E3", "W9E2", "W7E1", "W7E2", "W9E3")
+WORKSHEET1_MODES = _modes(lambda r: r.family == RT_FAMILY_WORKSHEET1 and r.name != "W1E6")
+LINEAR_DISPLAY_MODES = _modes(lambda r: r.flags & RT_MODEF_LINEAR_DISPLAY)
+# the progressive modes: a render advances the iteration (the name is historical: W7E1 and W7E2 are direct)
+PATH_MODES = _modes(lambda r: r.flags & RT_MODEF_PROGRESSIVE)
 # ... of which these write per-iteration records (k_path): the modes a noise buffer follows
 # (rt_set_noise_buffer); W7E1 and W7E2 fold inside their kernel
-NOISE_MODES = ("W7E3", "W9E1", "W8E1", "W8E2", "W8E3", "W9E2", "W9E3")
+NOISE_MODES = _modes(lambda r: r.family == RT_FAMILY_PATH)
 TRAVERSALS = {"BSP": RT_TRAVERSE_BSP, "BVH": RT_TRAVERSE_BVH, "NONE": RT_TRAVERSE_NONE}
 
 u32p = C.POINTER(C.c_uint32)
@@ -173,6 +216,11 @@ class AdaptiveSummary(C.Structure):   # include/rt.h rt_adaptive_summary
         return d
 
 
+class ModeDesc(C.Structure):          # include/rt.h rt_mode_desc
+    _fields_ = [("mode", C.c_int32), ("family", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("name", C.c_char_p), ("shader", C.c_char_p)]
+
+
 RT_ADAPT_PIXEL, RT_ADAPT_TILE = 0, 1
 ADAPT_VOTES = {"pixel": RT_ADAPT_PIXEL, "tile": RT_ADAPT_TILE}
 
@@ -184,6 +232,7 @@ SIGNATURES = {
     "rt_set_stream": (C.c_int, [vp, vp]),
     "rt_get_stream": (vp, [vp]),
     "rt_synchronize": (C.c_int, [vp]),
+    "rt_mode_describe": (C.c_int, [C.c_int, C.POINTER(ModeDesc)]),
     "rt_set_option": (C.c_int, [vp, C.c_int, C.c_int64]),
     "rt_bsp_cull_in_use": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rt_last_error": (C.c_char_p, [vp]),

@@ -1,6 +1,6 @@
 // rt_ctx.h -- the context behind the C ABI (include/rt.h) and what the files that
 // implement it share: rt_context.cpp, rt_scene.cpp, rt_render.cpp, rt_estimate.cpp,
-// rt_denoise_api.cpp and rt_gather.cpp.  Not part of the public ABI.
+// rt_denoise_api.cpp and rt_gather.cpp (and rt_modes.cpp's table).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -275,6 +275,8 @@ int upload(rt_ctx* c, DevBuf& b, const void* src, size_t bytes);
 int set_dev_nojoin(rt_ctx* c);
 int set_dev(rt_ctx* c);
 int out_stream(rt_ctx* c, hipStream_t* s);
+// rt_modes.cpp: the mode table's row of `mode`, null for a value that is no rt_mode
+const rt_mode_desc* mode_desc(rt_mode mode);
 // rt_scene.cpp
 int ensure_hcam(rt_ctx* c);
 int ensure_sweep(rt_ctx* c);

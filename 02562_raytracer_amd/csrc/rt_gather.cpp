@@ -120,9 +120,10 @@ int rt_frame_rgba8(rt_ctx* c, const float* accum_rgba32f, uint32_t npix, uint8_t
 int rt_frame_rgba8_mode(rt_ctx* c, rt_mode mode, const float* accum_rgba32f, uint32_t npix, uint8_t* frame_rgba8)
 {
     if (!c || (!accum_rgba32f && npix) || (!frame_rgba8 && npix)) return RT_E_INVALID;
-    if (mode < RT_MODE_W1E6 || mode > RT_MODE_W1E5) return fail(c, RT_E_INVALID, "rt_frame_rgba8_mode: bad mode");
+    const rt_mode_desc* d = mode_desc(mode);
+    if (!d) return fail(c, RT_E_INVALID, "rt_frame_rgba8_mode: bad mode");
     // every shader but w1e2.wgsl and w1e3.wgsl ends in pow(result, 1.5)
-    if (mode != RT_MODE_W1E2 && mode != RT_MODE_W1E3) return rt_frame_rgba8(c, accum_rgba32f, npix, frame_rgba8);
+    if (!(d->flags & RT_MODEF_LINEAR_DISPLAY)) return rt_frame_rgba8(c, accum_rgba32f, npix, frame_rgba8);
     if (int r = rt_frame_rgba8(c, nullptr, 0, nullptr)) return r;   // binds the device and uploads the thresholds
     if (npix == 0) return RT_OK;
     if (rtk::launch_frame_linear(reinterpret_cast<const float4*>(accum_rgba32f), npix, c->srgb_thr.as<float>(),

@@ -265,48 +265,36 @@ int probe_launch(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_
     return RT_OK;
 }
 
-// the worksheet-1 scenes: the uniforms alone (rt_worksheet1.hip)
-bool is_worksheet1(rt_mode m) { return m == RT_MODE_W1E6 || (m >= RT_MODE_W1E2 && m <= RT_MODE_W1E5); }
-// the analytic W2 / W3 scenes: three constant objects, no mesh (rt_analytic.hip)
-bool is_analytic(rt_mode m) { return m >= RT_MODE_W2E1 && m <= RT_MODE_W3E4; }
-// the brute-force W5 scenes: the triangle sweep over the mesh alone (rt_sweep.hip)
-bool is_sweep(rt_mode m) { return m >= RT_MODE_W5E2 && m <= RT_MODE_W5E5; }
-// progressive path tracers: per-iteration samples, folded in order by k_fold
-bool is_path(rt_mode m)
-{
-    return m == RT_MODE_W7E3 || m == RT_MODE_W9E1 || m == RT_MODE_W8E1 || m == RT_MODE_W8E2 || m == RT_MODE_W8E3 ||
-           m == RT_MODE_W9E2 || m == RT_MODE_W9E3;
-}
-
-// Can the context render (mode, trav)?  The status and, for a refusal, its message: the
-// first failing check wins.
+// Can the context render the mode of row d (the mode table, rt_modes.cpp; null: the
+// value is no rt_mode) with trav?  The status and, for a refusal, its message: the first
+// failing check wins.
 struct Verdict {
     int code;
     const char* msg;
 };
-Verdict validate_render(const rt_ctx* c, rt_mode mode, rt_traverse trav)
+Verdict validate_render(const rt_ctx* c, const rt_mode_desc* d, rt_traverse trav)
 {
     const SceneState& s = c->scene;
     if (!c->has_u) return {RT_E_NOT_READY, "rt_render: uniforms not set"};
-    if (mode < RT_MODE_W1E6 || mode > RT_MODE_W1E5) return {RT_E_INVALID, "rt_render: bad mode"};
-    if (is_worksheet1(mode)) {
+    if (!d) return {RT_E_INVALID, "rt_render: bad mode"};
+    if (d->family == RT_FAMILY_WORKSHEET1) {
         if (trav != RT_TRAVERSE_NONE)
-            return {RT_E_UNSUPPORTED, mode == RT_MODE_W1E6 ? "W1E6 is analytic: traverse must be NONE"
+            return {RT_E_UNSUPPORTED, d->mode == RT_MODE_W1E6 ? "W1E6 is analytic: traverse must be NONE"
                                                            : "W1E2..W1E5 are analytic: traverse must be NONE"};
-    } else if (is_analytic(mode)) {
+    } else if (d->family == RT_FAMILY_ANALYTIC) {
         if (trav != RT_TRAVERSE_NONE) return {RT_E_UNSUPPORTED, "W2E1..W3E4 are analytic: traverse must be NONE"};
-        if (mode >= RT_MODE_W3E1 && c->u.use_texture > 0u && !c->tex0_w)
+        if ((d->flags & RT_MODEF_TEXTURE0) && c->u.use_texture > 0u && !c->tex0_w)
             return {RT_E_NOT_READY, "rt_render: uniforms.use_texture is set and no texture is (rt_set_texture)"};
-    } else if (is_sweep(mode)) {
+    } else if (d->family == RT_FAMILY_SWEEP) {
         if (trav != RT_TRAVERSE_NONE)
             return {RT_E_UNSUPPORTED, "W5E2..W5E5 sweep the triangle list: traverse must be NONE"};
         if (!s.has_mesh) return {RT_E_NOT_READY, "rt_render: no mesh uploaded"};
-    } else {
+    } else {   // the families that walk a tree
         if (!s.has_mesh) return {RT_E_NOT_READY, "rt_render: no mesh uploaded"};
         if (trav == RT_TRAVERSE_BSP && !s.has_bsp) return {RT_E_NOT_READY, "rt_render: no BSP uploaded"};
         if (trav == RT_TRAVERSE_BVH && !s.has_bvh) return {RT_E_NOT_READY, "rt_render: no BVH uploaded"};
         if (trav == RT_TRAVERSE_NONE) return {RT_E_UNSUPPORTED, "mesh modes need BSP or BVH"};
-        if (is_path(mode) && mode != RT_MODE_W9E1 && mode != RT_MODE_W9E2 && mode != RT_MODE_W9E3 && s.nlights < 2)
+        if ((d->flags & RT_MODEF_AREA_LIGHTS) && s.nlights < 2)
             return {RT_E_INVALID, "W7E3/W8 sample area lights: the mesh has no emissive (illum 1) triangle"};
     }
     return {RT_OK, nullptr};
@@ -489,11 +477,13 @@ int launch_flat(rt_ctx* c, Launch&& launch)
     return launch_timed(c, kLaunchFailed, launch);
 }
 
-// the modes of one launch: the analytic scenes, the sweep, worksheet 1, and the walks
+// the modes of one launch, by family: the analytic scenes (three constant objects, no
+// mesh), the sweep over the mesh alone, worksheet 1 (the uniforms alone), and the walks
 // that fold in the kernel
-int render_single(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_mode mode, rt_traverse trav)
+int render_single(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, int family, rt_mode mode,
+                  rt_traverse trav)
 {
-    if (is_analytic(mode)) {
+    if (family == RT_FAMILY_ANALYTIC) {
         rtk::AnalyticTex T;
         T.texels = c->tex0_w ? c->tex0.as<uint32_t>() : nullptr;
         T.w = c->tex0_w;
@@ -502,7 +492,7 @@ int render_single(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt
             return rtk::launch_analytic(T, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream);
         });
     }
-    if (is_sweep(mode)) {
+    if (family == RT_FAMILY_SWEEP) {
         rtk::SweepScene W;
         W.recs = c->scene.sweep_recs.as<float4>();
         W.pos = S.pos;
@@ -517,7 +507,7 @@ int render_single(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt
             return rtk::launch_sweep(W, L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream);
         });
     }
-    if (is_worksheet1(mode))
+    if (family == RT_FAMILY_WORKSHEET1)
         return launch_flat(c, [&] {
             return rtk::launch_worksheet1(L, mode, c->detail, c->num_cus, c->waves_per_cu, c->stream);
         });
@@ -531,19 +521,21 @@ int render_single(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt
 int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaunch& L, uint32_t first_iter, uint32_t spp,
                   float* accum, uint32_t* ids, rt_ray_counts* counts)
 {
-    const Verdict v = validate_render(c, mode, trav);
-    if (v.code) return fail(c, v.code, v.msg);
+    const rt_mode_desc* d = mode_desc(mode);
+    const Verdict v = validate_render(c, d, trav);
+    if (v.code) return fail(c, v.code, v.msg);   // (past this line d is a row)
     if (!accum) return fail(c, RT_E_INVALID, "rt_render: accum buffer required");
     L.first_iter = first_iter;
     L.spp = spp;
     L.accum = reinterpret_cast<float4*>(accum);
     L.ids = ids;
-    const bool path = is_path(mode);
+    // the path modes: per-iteration samples, folded in order by k_fold
+    const bool path = d->family == RT_FAMILY_PATH;
     // a path mode orders itself against a pending fold (double-buffered samples,
     // the fold stream); every other mode writes accum / ids on the context stream
     // itself, so a fold of an earlier path render still pending there is joined first
     if (int r = path ? set_dev_nojoin(c) : set_dev(c)) return r;
-    if (is_sweep(mode))
+    if (d->family == RT_FAMILY_SWEEP)
         if (int r = ensure_sweep(c)) return r;
     if (int r = ensure_hcam(c)) return r;
     rtk::DevScene S = dev_scene(c);
@@ -567,13 +559,13 @@ int render_common(rt_ctx* c, rt_mode mode, rt_traverse trav, rtk::DevLaunch& L, 
     if (adaptive && c->async_fold)
         return fail(c, RT_E_UNSUPPORTED, "rt_render: adaptive sampling does not run with RT_OPT_ASYNC_FOLD");
     // (W7E1/W7E2 are progressive too, folded inside k_direct: no iterations, no launch)
-    const bool progressive = path || mode == RT_MODE_W7E1 || mode == RT_MODE_W7E2;
+    const bool progressive = (d->flags & RT_MODEF_PROGRESSIVE) != 0;
     if (L.nwork != 0 && !(L.spp == 0 && progressive)) {
         if (path) {
             PathSetup P = {};
             if (int r = path_setup(c, S, L, mode, trav, sil, adaptive, P)) return r;
             if (int r = path_passes(c, S, L, mode, trav, sil, P)) return r;
-        } else if (int r = render_single(c, S, L, mode, trav)) {
+        } else if (int r = render_single(c, S, L, d->family, mode, trav)) {
             return r;
         }
     }

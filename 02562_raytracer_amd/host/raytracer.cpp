@@ -97,51 +97,36 @@ void CameraController::update_camera(Camera& c) const
 }
 
 // ------------------------------------------------------------------ scenes.rs
-std::optional<rt_mode> SceneDescriptor::mode() const
+// kernel_mode() where its row of the mode table passes `keep`
+template <class Keep>
+static std::optional<rt_mode> mode_if(const std::string& shader, Keep keep)
 {
-    if (shader == "w1e6.wgsl") return RT_MODE_W1E6;
-    if (shader == "w6e1.wgsl") return RT_MODE_W6E1;
-    if (shader == "project.wgsl") return RT_MODE_PROJECT;
-    if (shader == "w7e3.wgsl") return RT_MODE_W7E3;
-    if (shader == "w9e1.wgsl") return RT_MODE_W9E1;
-    if (shader == "w8e1.wgsl") return RT_MODE_W8E1;
-    if (shader == "w8e2.wgsl") return RT_MODE_W8E2;
-    if (shader == "w8e3.wgsl") return RT_MODE_W8E3;
-    if (shader == "w9e2.wgsl") return RT_MODE_W9E2;
-    if (shader == "w6e2.wgsl") return RT_MODE_W6E2;
-    if (shader == "w7e1.wgsl") return RT_MODE_W7E1;
-    if (shader == "w7e2.wgsl") return RT_MODE_W7E2;
-    if (shader == "w6e3.wgsl") return RT_MODE_W6E3;
-    if (shader == "w9e3.wgsl") return RT_MODE_W9E3;
+    const auto d = mode_of_shader(shader);
+    if (d && keep(*d)) return (rt_mode)d->mode;
     return std::nullopt;
 }
+static bool walks_tree_or_w1e6(const rt_mode_desc& d) { return RT_FAMILY_NEEDS_TREE(d.family) || d.mode == RT_MODE_W1E6; }
+
+std::optional<rt_mode> SceneDescriptor::kernel_mode() const
+{
+    return mode_if(shader, [](const rt_mode_desc&) { return true; });
+}
+
+std::optional<rt_mode> SceneDescriptor::mode() const { return mode_if(shader, walks_tree_or_w1e6); }
 
 std::optional<rt_mode> SceneDescriptor::render_mode() const
 {
-    if (const auto m = mode()) return m;
-    if (shader == "w5e2.wgsl") return RT_MODE_W5E2;
-    if (shader == "w5e3.wgsl") return RT_MODE_W5E3;
-    if (shader == "w5e4.wgsl") return RT_MODE_W5E4;
-    if (shader == "w5e5.wgsl") return RT_MODE_W5E5;
-    return std::nullopt;
+    return mode_if(shader, [](const rt_mode_desc& d) { return walks_tree_or_w1e6(d) || d.family == RT_FAMILY_SWEEP; });
 }
 
 std::optional<rt_mode> SceneDescriptor::analytic_mode() const
 {
-    static const char* const files[9] = {"w2e1.wgsl", "w2e2.wgsl", "w2e3.wgsl", "w2e4.wgsl", "w2e5.wgsl",
-                                         "w3e1.wgsl", "w3e2.wgsl", "w3e3.wgsl", "w3e4.wgsl"};
-    for (int i = 0; i < 9; i++)
-        if (shader == files[i]) return (rt_mode)(RT_MODE_W2E1 + i);
-    return std::nullopt;
+    return mode_if(shader, [](const rt_mode_desc& d) { return d.family == RT_FAMILY_ANALYTIC; });
 }
 
 std::optional<rt_mode> SceneDescriptor::worksheet1_mode() const
 {
-    if (shader == "w1e2.wgsl") return RT_MODE_W1E2;
-    if (shader == "w1e3.wgsl") return RT_MODE_W1E3;
-    if (shader == "w1e4.wgsl") return RT_MODE_W1E4;
-    if (shader == "w1e5.wgsl") return RT_MODE_W1E5;
-    return std::nullopt;   // w1e1.wgsl, the blank template, stays unrendered
+    return mode_if(shader, [](const rt_mode_desc& d) { return d.family == RT_FAMILY_WORKSHEET1 && d.mode != RT_MODE_W1E6; });
 }
 
 std::vector<SceneDescriptor> get_scenes()
@@ -374,16 +359,13 @@ void RenderState::release()
     accum_ = ids_ = tile_accum_ = tile_ids_ = noise_ = counts_ = nullptr;
 }
 
-static bool writes_records(rt_mode m)   // the k_path modes (rt.h "noise estimate")
-{
-    return m == RT_MODE_W7E3 || m == RT_MODE_W9E1 || m == RT_MODE_W8E1 || m == RT_MODE_W8E2 || m == RT_MODE_W8E3 ||
-           m == RT_MODE_W9E2 || m == RT_MODE_W9E3;
-}
+// the k_path modes (rt.h "noise estimate")
+static bool writes_records(const rt_mode_desc& row) { return row.family == RT_FAMILY_PATH; }
 
 void RenderState::enable_noise()
 {
     if (tiled_) throw Error(RT_E_UNSUPPORTED, "enable_noise is for an untiled state: a tiled render (set_tiling, any rank count) keeps its states packed per tile");
-    if (!writes_records(mode_))
+    if (!writes_records(row_))
         throw Error(RT_E_UNSUPPORTED, "enable_noise: the mode writes no per-iteration records");
     if (iteration_) throw Error(RT_E_INVALID, "enable_noise: the estimate starts at iteration 0");
     rt_ctx* c = gpu_.ctx();
@@ -447,7 +429,7 @@ static const char* const kAdaptiveUntiled =
 void RenderState::enable_adaptive(float target, float floor, uint32_t min_samples, int vote)
 {
     if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("enable_adaptive") + kAdaptiveUntiled);
-    if (!writes_records(mode_))
+    if (!writes_records(row_))
         throw Error(RT_E_UNSUPPORTED, "enable_adaptive: the mode writes no per-iteration records");
     if (iteration_) throw Error(RT_E_INVALID, "enable_adaptive: the counts start at iteration 0");
     if (min_samples < 2 || !(target >= 0.0f) || !(floor > 0.0f) || (vote != RT_ADAPT_PIXEL && vote != RT_ADAPT_TILE))
@@ -533,39 +515,32 @@ void RenderState::alloc_tiles()
 
 void RenderState::setup_rendering(const SceneDescriptor& scene)
 {
-    const auto m = scene.render_mode()     ? scene.render_mode()
-                   : scene.analytic_mode() ? scene.analytic_mode()
-                                           : scene.worksheet1_mode();
-    if (!m) throw Error(RT_E_UNSUPPORTED, scene.shader + " is outside the hot path (SURVEY.md section 2)");
+    const auto row = mode_of_shader(scene.shader);
+    if (!row) throw Error(RT_E_UNSUPPORTED, scene.shader + " is outside the hot path (SURVEY.md section 2)");
     scene_ = scene;
     camera_ = scene.camera;
-    mode_ = *m;
+    row_ = *row;
     width_ = opts_.resolution ? opts_.resolution->first : scene.res.first;
     height_ = opts_.resolution ? opts_.resolution->second : scene.res.second;
     rt_ctx* c = gpu_.ctx();
-    if (mode_ == RT_MODE_W1E6 || (mode_ >= RT_MODE_W1E2 && mode_ <= RT_MODE_W1E5)) {
-        trav_ = RT_TRAVERSE_NONE;   // the worksheet-1 scenes: the uniforms alone, no mesh
-    } else if (mode_ >= RT_MODE_W2E1 && mode_ <= RT_MODE_W3E4) {
-        // the analytic W2 / W3 scenes: no mesh; the W3 ones sample texture0 (grass.jpg is
-        // not redistributed and this layer decodes no JPEG: the stand-in, or set_texture_image)
-        trav_ = RT_TRAVERSE_NONE;
-        if (mode_ >= RT_MODE_W3E1) {
-            const auto tex = synth_texture();
-            gpu_.check(rt_set_texture(c, tex.data(), 64, 64), "texture0");
-        } else {
-            gpu_.check(rt_set_texture(c, nullptr, 0, 0), "texture0");
-        }
-    } else {
-        trav_ = scene.traverse_type == TraverseType::Bsp ? RT_TRAVERSE_BSP : RT_TRAVERSE_BVH;
+    const bool tree = RT_FAMILY_NEEDS_TREE(row_.family);
+    trav_ = !tree ? RT_TRAVERSE_NONE : scene.traverse_type == TraverseType::Bsp ? RT_TRAVERSE_BSP : RT_TRAVERSE_BVH;
+    if (row_.flags & RT_MODEF_TEXTURE0) {
+        // the W3 scenes sample texture0 (grass.jpg is not redistributed and this layer
+        // decodes no JPEG: the stand-in, or set_texture_image)
+        const auto tex = synth_texture();
+        gpu_.check(rt_set_texture(c, tex.data(), 64, 64), "texture0");
+    } else if (row_.family == RT_FAMILY_ANALYTIC) {
+        gpu_.check(rt_set_texture(c, nullptr, 0, 0), "texture0");
+    }
+    if (RT_FAMILY_NEEDS_MESH(row_.family)) {
         const std::string path = opts_.models_dir + "/" + scene.model.value_or("");
         struct stat st;
         const bool exists = ::stat(path.c_str(), &st) == 0;
         Mesh mesh = (!exists && scene.model == std::string("bunny.obj") && opts_.bunny_standin) ? Mesh::synth_bunny()
                                                                                                  : Mesh::load(path);
         gpu_.check(rt_upload_mesh_host(c, mesh.get()), "upload mesh");
-        if (mode_ >= RT_MODE_W5E2 && mode_ <= RT_MODE_W5E5) {
-            trav_ = RT_TRAVERSE_NONE;   // the brute-force W5 scenes: the mesh alone, no tree
-        } else if (trav_ == RT_TRAVERSE_BSP) {
+        if (trav_ == RT_TRAVERSE_BSP) {
             if (opts_.device_build) {
                 gpu_.check(rt_build_bsp_device(c, 20, 4, nullptr), "BSP device build");
             } else {   // Mesh::bsp_tree, mesh.rs:229-231 (depth 20, leaf 4)
@@ -575,7 +550,7 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
                 rt_bsp_free(b);
                 gpu_.check(rc, "upload BSP");
             }
-        } else {
+        } else if (trav_ == RT_TRAVERSE_BVH) {   // (NONE: the brute-force W5 scenes, the mesh alone)
             if (opts_.device_build) {
                 gpu_.check(rt_build_bvh_device(c, 4, nullptr), "HLBVH device build");
             } else {   // Mesh::bvh, mesh.rs:233-239 (leaf 4)
@@ -597,8 +572,8 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
     gpu_.check(rt_memset_device(c, accum_, 0, npx * 16), "clear accumulation");
     alloc_tiles();
     iteration_ = 0;
-    if (had_noise && writes_records(mode_)) enable_noise();   // the buffer follows the scene
-    if (had_adaptive && writes_records(mode_)) enable_adaptive(ad_target_, ad_floor_, ad_min_, ad_vote_);
+    if (had_noise && writes_records(row_)) enable_noise();   // the buffer follows the scene
+    if (had_adaptive && writes_records(row_)) enable_adaptive(ad_target_, ad_floor_, ad_min_, ad_vote_);
     update();
 }
 
@@ -623,7 +598,7 @@ void RenderState::render(uint32_t spp)
     if (tiled_) {
         // this rank's tiles, then every rank's tiles into rank 0's frame
         const rt_tileset ts{rank_, nranks_};
-        gpu_.check(rt_render_tiles(gpu_.ctx(), mode_, trav_, &ts, iteration_, spp, static_cast<float*>(tile_accum_),
+        gpu_.check(rt_render_tiles(gpu_.ctx(), mode(), trav_, &ts, iteration_, spp, static_cast<float*>(tile_accum_),
                                    static_cast<uint32_t*>(tile_ids_), nullptr),
                    "render tiles");
         const bool root = rank_ == 0;
@@ -633,14 +608,11 @@ void RenderState::render(uint32_t spp)
                    "gather tiles");
     } else {
         const rt_tile region{0, 0, width_, height_};
-        gpu_.check(rt_render(gpu_.ctx(), mode_, trav_, &region, iteration_, spp, static_cast<float*>(accum_),
+        gpu_.check(rt_render(gpu_.ctx(), mode(), trav_, &region, iteration_, spp, static_cast<float*>(accum_),
                              static_cast<uint32_t*>(ids_), nullptr),
                    "render");
     }
-    const bool path = mode_ == RT_MODE_W7E3 || mode_ == RT_MODE_W9E1 || mode_ == RT_MODE_W8E1 ||
-                      mode_ == RT_MODE_W8E2 || mode_ == RT_MODE_W8E3 || mode_ == RT_MODE_W9E2 ||
-                      mode_ == RT_MODE_W7E1 || mode_ == RT_MODE_W7E2 || mode_ == RT_MODE_W9E3;
-    if (progressive_ && path) iteration_ += spp;
+    if (progressive_ && (row_.flags & RT_MODEF_PROGRESSIVE)) iteration_ += spp;
     update();
 }
 
@@ -705,7 +677,7 @@ std::vector<uint8_t> RenderState::frame_rgba8() const
     void* d = nullptr;
     gpu_.check(rt_device_alloc(gpu_.ctx(), npx * 4, &d), "frame buffer");
     std::vector<uint8_t> out(npx * 4);
-    int rc = rt_frame_rgba8_mode(gpu_.ctx(), mode_, static_cast<const float*>(accum_), (uint32_t)npx,
+    int rc = rt_frame_rgba8_mode(gpu_.ctx(), mode(), static_cast<const float*>(accum_), (uint32_t)npx,
                                  static_cast<uint8_t*>(d));
     if (rc == RT_OK) rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), d, out.size());
     rt_device_free(gpu_.ctx(), d);
@@ -717,7 +689,7 @@ std::vector<uint8_t> RenderState::frame_rgba8() const
 void* RenderState::denoise_device(uint32_t levels, float sigma_l, float sigma_z) const
 {
     if (tiled_) throw Error(RT_E_UNSUPPORTED, "denoise is for an untiled state: the filter needs every pixel's neighbours, and a tiled render (set_tiling, any rank count) keeps its buffers packed per tile");
-    if (!writes_records(mode_)) throw Error(RT_E_UNSUPPORTED, "denoise: the mode keeps no noise state");
+    if (!writes_records(row_)) throw Error(RT_E_UNSUPPORTED, "denoise: the mode keeps no noise state");
     if (!noise_) throw Error(RT_E_NOT_READY, "denoise: enable_noise() first");
     if (iteration_ < 2) throw Error(RT_E_INVALID, "denoise: the variance needs at least 2 rendered iterations");
     if (levels < 1 || levels > 5 || !(sigma_l > 0.0f) || !(sigma_z > 0.0f))
@@ -752,7 +724,7 @@ std::vector<uint8_t> RenderState::denoised_rgba8(uint32_t levels, float sigma_l,
     int rc = rt_device_alloc(gpu_.ctx(), npx * 4, &img);
     std::vector<uint8_t> out(npx * 4);
     if (rc == RT_OK)
-        rc = rt_frame_rgba8_mode(gpu_.ctx(), mode_, static_cast<const float*>(d), (uint32_t)npx, static_cast<uint8_t*>(img));
+        rc = rt_frame_rgba8_mode(gpu_.ctx(), mode(), static_cast<const float*>(d), (uint32_t)npx, static_cast<uint8_t*>(img));
     if (rc == RT_OK) rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), img, out.size());
     rt_device_free(gpu_.ctx(), img);
     rt_device_free(gpu_.ctx(), d);

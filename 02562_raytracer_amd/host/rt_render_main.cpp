@@ -95,41 +95,8 @@ static std::string hexf(float f)
 
 static const char* mode_name(std::optional<rt_mode> m)
 {
-    if (!m) return nullptr;
-    switch (*m) {
-    case RT_MODE_W1E6: return "W1E6";
-    case RT_MODE_W6E1: return "W6E1";
-    case RT_MODE_PROJECT: return "PROJECT";
-    case RT_MODE_W7E3: return "W7E3";
-    case RT_MODE_W9E1: return "W9E1";
-    case RT_MODE_W8E1: return "W8E1";
-    case RT_MODE_W8E2: return "W8E2";
-    case RT_MODE_W8E3: return "W8E3";
-    case RT_MODE_W9E2: return "W9E2";
-    case RT_MODE_W6E2: return "W6E2";
-    case RT_MODE_W7E1: return "W7E1";
-    case RT_MODE_W7E2: return "W7E2";
-    case RT_MODE_W6E3: return "W6E3";
-    case RT_MODE_W9E3: return "W9E3";
-    case RT_MODE_W5E2: return "W5E2";
-    case RT_MODE_W5E3: return "W5E3";
-    case RT_MODE_W5E4: return "W5E4";
-    case RT_MODE_W5E5: return "W5E5";
-    case RT_MODE_W2E1: return "W2E1";
-    case RT_MODE_W2E2: return "W2E2";
-    case RT_MODE_W2E3: return "W2E3";
-    case RT_MODE_W2E4: return "W2E4";
-    case RT_MODE_W2E5: return "W2E5";
-    case RT_MODE_W3E1: return "W3E1";
-    case RT_MODE_W3E2: return "W3E2";
-    case RT_MODE_W3E3: return "W3E3";
-    case RT_MODE_W3E4: return "W3E4";
-    case RT_MODE_W1E2: return "W1E2";
-    case RT_MODE_W1E3: return "W1E3";
-    case RT_MODE_W1E4: return "W1E4";
-    case RT_MODE_W1E5: return "W1E5";
-    }
-    return nullptr;
+    rt_mode_desc d;
+    return m && rt_mode_describe(*m, &d) == RT_OK ? d.name : nullptr;
 }
 
 static std::string cam_json(const Camera& c)
@@ -206,13 +173,15 @@ int main(int argc, char** argv)
                 const char* rm = mode_name(s.render_mode());
                 const char* am = mode_name(s.analytic_mode());
                 const char* wm = mode_name(s.worksheet1_mode());
+                const char* km = mode_name(s.kernel_mode());
                 std::printf("{\"name\":%s,\"shader\":%s,\"mode\":%s,\"render_mode\":%s,\"analytic_mode\":%s,"
-                            "\"worksheet1_mode\":%s,\"model\":%s,\"res\":[%u,%u],"
+                            "\"worksheet1_mode\":%s,\"kernel_mode\":%s,\"model\":%s,\"res\":[%u,%u],"
                             "\"vertex_type\":%s,"
                             "\"traverse_type\":%s,\"background_hdri\":%s,\"camera\":%s}\n",
                             jstr(s.name).c_str(), jstr(s.shader).c_str(), m ? jstr(m).c_str() : "null",
                             rm ? jstr(rm).c_str() : "null", am ? jstr(am).c_str() : "null",
-                            wm ? jstr(wm).c_str() : "null", s.model ? jstr(*s.model).c_str() : "null", s.res.first, s.res.second,
+                            wm ? jstr(wm).c_str() : "null", km ? jstr(km).c_str() : "null",
+                            s.model ? jstr(*s.model).c_str() : "null", s.res.first, s.res.second,
                             s.vertex_type == VertexType::Combined ? "\"Combined\"" : "\"Split\"",
                             s.traverse_type == TraverseType::Bsp ? "\"BSP\"" : "\"BVH\"",
                             s.background_hdri ? jstr(*s.background_hdri).c_str() : "null",
@@ -274,10 +243,9 @@ int main(int argc, char** argv)
         if (denoise) {
             if (dn_levels < 1 || dn_levels > 5 || !(dn_sigma_l > 0.0f) || !(dn_sigma_z > 0.0f))
                 throw Error(RT_E_INVALID, "--denoise-levels in 1..5, --denoise-sigma-l and --denoise-sigma-z > 0");
-            const std::optional<rt_mode> m = find_scene(*name).mode();
-            const bool path = m && (*m == RT_MODE_W7E3 || *m == RT_MODE_W9E1 || *m == RT_MODE_W8E1 || *m == RT_MODE_W8E2 ||
-                                    *m == RT_MODE_W8E3 || *m == RT_MODE_W9E2 || *m == RT_MODE_W9E3);
-            if (!path) throw Error(RT_E_UNSUPPORTED, "--denoise: the scene's mode keeps no noise state (a path mode only)");
+            const auto row = mode_of_shader(find_scene(*name).shader);
+            if (!row || row->family != RT_FAMILY_PATH)
+                throw Error(RT_E_UNSUPPORTED, "--denoise: the scene's mode keeps no noise state (a path mode only)");
         }
         int vote = RT_ADAPT_TILE;
         if (const std::string* v = arg("--adaptive-vote")) {

@@ -72,28 +72,20 @@ class RenderState:
 
     # render_state.rs:161-265
     def setup_rendering(self, scene):
-        mode = scene.render_mode or scene.analytic_mode or scene.worksheet1_mode
-        if mode is None:
+        row = F.MODE_OF_SHADER.get(scene.shader)   # (its name is scene.kernel_mode)
+        if row is None:
             raise F.RtError(F.RT_E_UNSUPPORTED, f"{scene.shader} is outside the hot path (SURVEY.md section 2)")
         self.scene = scene
         self.camera = Camera.from_tuple(scene.camera)
-        self.mode = mode
+        self.mode = row.name
         self.width, self.height = self.resolution or scene.res
         self.mesh = self.bsp = self.bvh = None
-        if self.mode == "W1E6" or self.mode in F.WORKSHEET1_MODES:
-            # the worksheet-1 scenes: the uniforms alone, no mesh
-            self.trav = "NONE"
-        elif self.mode in F.ANALYTIC_MODES:
-            # the analytic W2 / W3 scenes: no mesh; the W3 ones sample texture0
-            self.trav = "NONE"
-            self.ctx.set_texture(self._texture0() if self.mode in F.TEXTURED_MODES else None)
-        elif self.mode in F.SWEEP_MODES:
-            # the brute-force W5 scenes: the mesh alone, no tree (w5e2.wgsl:230-239)
-            self.trav = "NONE"
-            self.mesh = self._load_model(scene.model)
-            self.ctx.upload_mesh(self.mesh)
-        else:
-            self.trav = scene.traverse_type
+        self.trav = scene.traverse_type if row.family in F.TREE_FAMILIES else "NONE"
+        if row.flags & F.RT_MODEF_TEXTURE0:
+            self.ctx.set_texture(self._texture0())   # the W3 scenes sample texture0
+        elif row.family == F.RT_FAMILY_ANALYTIC:
+            self.ctx.set_texture(None)
+        if row.family in F.MESH_FAMILIES:
             self.mesh = self._load_model(scene.model)
             self.ctx.upload_mesh(self.mesh)
             if self.trav == "BSP":
@@ -102,7 +94,7 @@ class RenderState:
                 else:
                     self.bsp = self.mesh.bsp_tree()   # Mesh::bsp_tree, mesh.rs:229-231 (depth 20, leaf 4)
                     self.ctx.upload_bsp(self.bsp)
-            else:
+            elif self.trav == "BVH":   # ("NONE": the brute-force W5 scenes, the mesh alone)
                 if self.device_build:
                     self.ctx.build_bvh_device(4)
                 else:

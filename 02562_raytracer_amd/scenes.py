@@ -8,58 +8,22 @@ SURVEY.md section 2).  Paths are relative to the model directory
 from dataclasses import dataclass, field, replace
 from typing import Optional, Tuple
 
-# shader file -> rt_mode name (include/rt.h)
-SHADER_MODES = {
-    "w1e6.wgsl": "W1E6",
-    "w6e1.wgsl": "W6E1",
-    "project.wgsl": "PROJECT",
-    "w7e3.wgsl": "W7E3",
-    "w9e1.wgsl": "W9E1",
-    "w8e1.wgsl": "W8E1",
-    "w8e2.wgsl": "W8E2",
-    "w8e3.wgsl": "W8E3",
-    "w9e2.wgsl": "W9E2",
-    "w6e2.wgsl": "W6E2",
-    "w7e1.wgsl": "W7E1",
-    "w7e2.wgsl": "W7E2",
-    "w6e3.wgsl": "W6E3",
-    "w9e3.wgsl": "W9E3",
-}
+from . import _ffi as F
 
-# shader file -> rt_mode name of the brute-force worksheet-5 scenes: no tree, a
-# sweep over the triangle list (RT_TRAVERSE_NONE).  Kept apart from SHADER_MODES,
-# whose `mode` means the tree-walk / W1E6 hot path.
-SWEEP_MODES = {
-    "w5e2.wgsl": "W5E2",
-    "w5e3.wgsl": "W5E3",
-    "w5e4.wgsl": "W5E4",
-    "w5e5.wgsl": "W5E5",
-}
 
-# shader file -> rt_mode name of the analytic worksheet-2 and worksheet-3 scenes:
-# W1E6's three objects with the control panel's materials, bounces and (W3) the
-# plane's texture (RT_TRAVERSE_NONE, no mesh).  Kept apart for the same reason.
-ANALYTIC_MODES = {
-    "w2e1.wgsl": "W2E1",
-    "w2e2.wgsl": "W2E2",
-    "w2e3.wgsl": "W2E3",
-    "w2e4.wgsl": "W2E4",
-    "w2e5.wgsl": "W2E5",
-    "w3e1.wgsl": "W3E1",
-    "w3e2.wgsl": "W3E2",
-    "w3e3.wgsl": "W3E3",
-    "w3e4.wgsl": "W3E4",
-}
+def _shaders(keep):
+    return {r.shader: r.name for r in F.MODE_TABLE if keep(r)}
 
-# shader file -> rt_mode name of the worksheet-1 scenes before W1E6, partial steps
-# towards it (RT_TRAVERSE_NONE, no mesh).  Kept apart for the same reason.  w1e1.wgsl,
-# the blank template (constant black), has no mode: W1 E1 stays unrendered.
-WORKSHEET1_MODES = {
-    "w1e2.wgsl": "W1E2",
-    "w1e3.wgsl": "W1E3",
-    "w1e4.wgsl": "W1E4",
-    "w1e5.wgsl": "W1E5",
-}
+
+# shader file -> rt_mode name, by kernel family: filters of the mode table (_ffi.MODE_TABLE), kept
+# for the four legacy properties below.  `mode` means the tree-walk / W1E6 hot path; the sweep over
+# the triangle list (W5), the analytic W2 / W3 scenes and the worksheet-1 scenes before W1E6 came
+# later, each under its own property.  w1e1.wgsl, the blank template (constant black), has no mode:
+# W1 E1 stays unrendered.
+SHADER_MODES = _shaders(lambda r: r.family in F.TREE_FAMILIES or r.name == "W1E6")
+SWEEP_MODES = _shaders(lambda r: r.family == F.RT_FAMILY_SWEEP)
+ANALYTIC_MODES = _shaders(lambda r: r.family == F.RT_FAMILY_ANALYTIC)
+WORKSHEET1_MODES = _shaders(lambda r: r.family == F.RT_FAMILY_WORKSHEET1 and r.name != "W1E6")
 
 
 @dataclass(frozen=True)
@@ -84,25 +48,30 @@ class SceneDescriptor:
     background_hdri: Optional[str] = None
 
     @property
+    def kernel_mode(self):
+        """The rt_mode whose kernel restates the shader, the one a RenderState renders
+        (None = no kernel does: W1 E1)."""
+        row = F.MODE_OF_SHADER.get(self.shader)
+        return row and row.name
+
+    # kernel_mode by family, each None for every other scene
+    @property
     def mode(self):
         return SHADER_MODES.get(self.shader)
 
     @property
     def render_mode(self):
-        """The rt_mode that renders the scene: `mode`, or else the sweep mode
-        (None = no kernel restates the shader)."""
+        """`mode`, or else the sweep mode of the brute-force W5 scenes."""
         return self.mode or SWEEP_MODES.get(self.shader)
 
     @property
     def analytic_mode(self):
-        """The rt_mode of an analytic W2 / W3 scene (None for every other scene);
-        a RenderState renders `render_mode or analytic_mode or worksheet1_mode`."""
+        """The rt_mode of an analytic W2 / W3 scene."""
         return ANALYTIC_MODES.get(self.shader)
 
     @property
     def worksheet1_mode(self):
-        """The rt_mode of W1 E2 .. W1 E5 (None for every other scene, W1 E1 included); a
-        RenderState renders `render_mode or analytic_mode or worksheet1_mode`."""
+        """The rt_mode of W1 E2 .. W1 E5 (W1 E1 has none)."""
         return WORKSHEET1_MODES.get(self.shader)
 
     def with_(self, **kw):

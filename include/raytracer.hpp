@@ -88,20 +88,31 @@ struct SceneDescriptor {   /* :20-44 */
     Camera camera;
     std::pair<uint32_t, uint32_t> res{512, 512};
     TraverseType traverse_type = TraverseType::Bsp;
-    /* the HIP kernel that restates the shader; nullopt = a worksheet shader
-     * outside the hot path */
+    /* the rt_mode whose kernel restates the shader (mode_of_shader), the one a RenderState
+     * renders; nullopt = no kernel does (w1e1.wgsl, the blank template) */
+    std::optional<rt_mode> kernel_mode() const;
+    /* kernel_mode() by family, each nullopt for every other scene -- */
+    /* W1E6 or a family that walks a tree (RT_FAMILY_NEEDS_TREE) */
     std::optional<rt_mode> mode() const;
-    /* the rt_mode that renders the scene: mode(), or else the triangle-sweep mode
-     * of the brute-force W5 scenes (RT_MODE_W5E2..W5E5, RT_TRAVERSE_NONE, no tree) */
+    /* mode(), or else the triangle sweep of the brute-force W5 scenes (RT_FAMILY_SWEEP) */
     std::optional<rt_mode> render_mode() const;
-    /* the rt_mode of an analytic W2 / W3 scene (RT_MODE_W2E1..W3E4, RT_TRAVERSE_NONE, no
-     * mesh), nullopt for every other scene; a RenderState renders render_mode() or else this */
+    /* an analytic W2 / W3 scene (RT_FAMILY_ANALYTIC) */
     std::optional<rt_mode> analytic_mode() const;
-    /* the rt_mode of W1 E2 .. W1 E5 (RT_MODE_W1E2..W1E5, RT_TRAVERSE_NONE, no mesh), nullopt for
-     * every other scene, W1 E1 (the blank template) included; a RenderState renders
-     * render_mode(), or else analytic_mode(), or else this */
+    /* W1 E2 .. W1 E5 (RT_FAMILY_WORKSHEET1 but W1E6) */
     std::optional<rt_mode> worksheet1_mode() const;
 };
+
+/* The row of the mode table (rt.h rt_mode_describe) whose shader file is `shader`, nullopt when
+ * no kernel restates it: the lookup behind kernel_mode() and RenderState, part of this header's
+ * interface for a host that wants the family and the flags with the mode.  Inline, so it needs
+ * the C ABI library alone. */
+inline std::optional<rt_mode_desc> mode_of_shader(const std::string& shader)
+{
+    rt_mode_desc d;
+    for (int m = 0; m < RT_MODE_COUNT; m++)
+        if (rt_mode_describe(m, &d) == RT_OK && shader == d.shader) return d;
+    return std::nullopt;
+}
 
 std::vector<SceneDescriptor> get_scenes();            /* :46-488, the 44 scenes in order */
 const SceneDescriptor& find_scene(const std::string& name);
@@ -240,7 +251,7 @@ public:
     uint32_t iteration() const { return iteration_; }
     const Camera& camera() const { return camera_; }
     const SceneDescriptor& scene() const { return scene_; }
-    rt_mode mode() const { return mode_; }   /* the rt_mode this state renders */
+    rt_mode mode() const { return (rt_mode)row_.mode; }   /* the rt_mode this state renders */
     rt_ray_counts last_counts() const;
 
 private:
@@ -253,7 +264,7 @@ private:
     SceneDescriptor scene_;
     Camera camera_;
     CameraController controller_;
-    rt_mode mode_ = RT_MODE_W7E3;
+    rt_mode_desc row_{};   // the mode table's row of the scene's kernel_mode()
     rt_traverse trav_ = RT_TRAVERSE_BSP;
     uint32_t width_ = 0, height_ = 0;
     uint32_t iteration_ = 0, max_iterations_ = 2, subdivision_ = 1, selection1_ = 0;

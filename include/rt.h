@@ -135,13 +135,48 @@ typedef enum rt_mode {
     RT_MODE_W1E4    = 29, /* res/shaders/w1e4.wgsl: W1E3's ray, closest hit, the base colour alone (background on a miss) */
     RT_MODE_W1E5    = 30  /* res/shaders/w1e5.wgsl: as W1E4, the ray with the aspect ratio and the camera constant */
 } rt_mode;
+#define RT_MODE_COUNT 31   /* the rt_mode values are 0 .. RT_MODE_COUNT - 1 */
+
+/* The kernel family of a mode: what a render of it needs uploaded and which traversals it takes. */
+typedef enum rt_family {
+    RT_FAMILY_WORKSHEET1 = 0,  /* the uniforms alone (rt_worksheet1.hip); RT_TRAVERSE_NONE only */
+    RT_FAMILY_ANALYTIC   = 1,  /* three constant objects, materials, bounces, no mesh (rt_analytic.hip); NONE only */
+    RT_FAMILY_SWEEP      = 2,  /* the mesh alone, every ray tests the triangle list (rt_sweep.hip); NONE only */
+    RT_FAMILY_PRIMARY    = 3,  /* mesh + BSP or BVH: camera rays and a directional light, one frame per call */
+    RT_FAMILY_DIRECT     = 4,  /* mesh + BSP or BVH: direct light from the area lights, folded inside the kernel */
+    RT_FAMILY_PATH       = 5   /* mesh + BSP or BVH: every iteration's radiance is a record, folded in order; the
+                                  noise estimate, adaptive sampling and the denoise filter follow these modes */
+} rt_family;
+#define RT_FAMILY_NEEDS_TREE(f) ((f) == RT_FAMILY_PRIMARY || (f) == RT_FAMILY_DIRECT || (f) == RT_FAMILY_PATH)
+#define RT_FAMILY_NEEDS_MESH(f) ((f) == RT_FAMILY_SWEEP || RT_FAMILY_NEEDS_TREE(f))
+
+/* rt_mode_desc.flags */
+#define RT_MODEF_PROGRESSIVE    1u  /* first_iter and spp are read: a host advances its iteration by spp per render */
+#define RT_MODEF_TEXTURE0       2u  /* samples texture0 (rt_set_texture) when uniforms.use_texture > 0 */
+#define RT_MODEF_LINEAR_DISPLAY 4u  /* the shader returns its colour without the pow(., 1.5): rt_frame_rgba8_mode */
+#define RT_MODEF_AREA_LIGHTS    8u  /* samples area lights: refused on a mesh with no emissive triangle */
+
+/* One row of the mode table: everything the library and its hosts know about an rt_mode.
+ * name and shader point to static strings ("W7E3", "w7e3.wgsl": the file under res/shaders). */
+typedef struct rt_mode_desc {
+    int32_t mode;        /* rt_mode */
+    int32_t family;      /* rt_family */
+    uint32_t flags;      /* RT_MODEF_* */
+    uint32_t reserved;   /* 0 */
+    const char* name;
+    const char* shader;
+} rt_mode_desc;
+
+/* The row of `mode` into *out.  Needs no context.  RT_E_INVALID for a value that is no
+ * rt_mode or a NULL out (*out is then left alone). */
+int rt_mode_describe(int mode, rt_mode_desc* out);
 
 /* SceneDescriptor.traverse_type, src/scenes.rs:13-17 */
 typedef enum rt_traverse {
     RT_TRAVERSE_BSP  = 0,
     RT_TRAVERSE_BVH  = 1,
-    RT_TRAVERSE_NONE = 2   /* only valid with RT_MODE_W1E6, RT_MODE_W1E2..W1E5 and RT_MODE_W2E1..W3E4 (analytic) and
-                              with RT_MODE_W5E2..W5E5 (triangle sweep); those modes take no other traversal */
+    RT_TRAVERSE_NONE = 2   /* the one traversal of the families that walk no tree (!RT_FAMILY_NEEDS_TREE); the
+                              tree-walking families take BSP or BVH */
 } rt_traverse;
 
 /* A rectangle of the frame in GLOBAL pixel coordinates. */
