@@ -36,6 +36,7 @@
 
 #include "../../include/rt_detmath.h"
 #include "host_types.h"
+#include "rt_ctx.h"   // (Event)
 #include "rt_internal.h"
 #include "rt_prims.h"
 
@@ -592,15 +593,11 @@ int build_bvh_device(const float4* pos, const uint4* idx, uint32_t nt, uint32_t 
         err = std::string("rt_build_bvh_device: scratch allocation: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? RT_E_OOM : RT_E_DEVICE;
     }
-    hipEvent_t ev[7];
-    for (auto& x : ev) (void)hipEventCreate(&x);
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard()
-        {
-            for (int i = 0; i < 7; i++) (void)hipEventDestroy(e[i]);
-        }
-    } evg{ev};
+    Event ev[7];
+    if ((e = ensure_all(ev)) != hipSuccess) {
+        err = std::string("rt_build_bvh_device: ") + hipGetErrorString(e);
+        return RT_E_DEVICE;
+    }
     auto chk = [&](const char* what) {
         const hipError_t r = hipGetLastError();
         if (r != hipSuccess && e == hipSuccess) {

@@ -22,6 +22,13 @@ int upload(rt_ctx* c, DevBuf& b, const void* src, size_t bytes)
     return RT_OK;
 }
 
+int read_back(rt_ctx* c, void* host, const void* dev, size_t bytes)
+{
+    HIPCHK(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
 // The current device, without joining the fold stream (RT_OPT_ASYNC_FOLD): the
 // render calls and the fold's consumers, which order themselves against it.
 int set_dev_nojoin(rt_ctx* c)
@@ -91,9 +98,9 @@ int rt_create(int device, rt_ctx** out)
     c->device = device;
     c->num_cus = prop.multiProcessorCount;
     memset(&c->u, 0, sizeof c->u);
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking) != hipSuccess ||
-        c->work.alloc(4096) != hipSuccess || c->counters.alloc(32 * sizeof(unsigned long long)) != hipSuccess) {
-        delete c;
+    if (hipSetDevice(device) != hipSuccess || c->own.ensure() != hipSuccess || c->work.alloc(4096) != hipSuccess ||
+        c->counters.alloc(32 * sizeof(unsigned long long)) != hipSuccess) {
+        delete c;   // (with what it got so far: the device is current unless hipSetDevice failed, and then there is nothing)
         return fail(nullptr, RT_E_DEVICE, "rt_create: stream/buffer setup failed");
     }
     c->stream = c->own;
@@ -101,31 +108,23 @@ int rt_create(int device, rt_ctx** out)
     return RT_OK;
 }
 
+// The context's members free what they own -- DevBuf its memory, Event / Stream / EventPool
+// their handles -- in their destructors, and those count on what is arranged here: the
+// context's device is current and idle when `delete c` runs them.  (Members die in reverse
+// order of declaration, so the events and the fold stream go before the context's stream.)
 void rt_destroy(rt_ctx* c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     (void)rt_comm_destroy(c);
-    for (hipEvent_t e : {c->ev_path, c->ev_enter, c->ev_fold, c->ev_free[0], c->ev_free[1], c->ev0, c->ev1})
-        if (e) (void)hipEventDestroy(e);
-    if (c->fold_stream) (void)hipStreamDestroy(c->fold_stream);
-    for (hipEvent_t e : c->ktime.ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->gather.ev) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->cull.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->empty.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->denoise.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->own) (void)hipStreamDestroy(c->own);
     delete c;
 }
 
 int rt_set_stream(rt_ctx* c, void* s)
 {
     if (!c) return RT_E_INVALID;
-    c->stream = s ? (hipStream_t)s : c->own;
+    c->stream = s ? (hipStream_t)s : c->own.get();
     return RT_OK;
 }
 
@@ -178,10 +177,14 @@ int rt_set_option(rt_ctx* c, int option, int64_t value)
     case RT_OPT_ASYNC_FOLD:
         if (value < 0 || value > 1) return fail(c, RT_E_INVALID, "async fold must be 0 or 1");
         if (int r = set_dev(c)) return r;   // joins pending fold work
-        if (value && !c->fold_stream) {
-            HIPCHK(c, hipStreamCreateWithFlags(&c->fold_stream, hipStreamNonBlocking));
-            for (hipEvent_t* e : {&c->ev_path, &c->ev_enter, &c->ev_fold, &c->ev_free[0], &c->ev_free[1]})
-                HIPCHK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+        if (value && !c->fold_stream) {   // all six or none: a failure leaves the context as it was
+            Stream fs;
+            Event ev[5];
+            HIPCHK(c, fs.ensure());
+            for (Event& e : ev) HIPCHK(c, e.ensure(hipEventDisableTiming));
+            c->fold_stream = std::move(fs);
+            Event* const to[5] = {&c->ev_path, &c->ev_enter, &c->ev_fold, &c->ev_free[0], &c->ev_free[1]};
+            for (int i = 0; i < 5; i++) *to[i] = std::move(ev[i]);
         }
         c->async_fold = value != 0;
         return RT_OK;
@@ -258,9 +261,12 @@ int rt_timer_start(rt_ctx* c)
 {
     if (!c) return RT_E_INVALID;
     if (int r = set_dev(c)) return r;
-    if (!c->ev0) {
-        HIPCHK(c, hipEventCreate(&c->ev0));
-        HIPCHK(c, hipEventCreate(&c->ev1));
+    if (!c->ev0) {   // both or neither
+        Event e0, e1;
+        HIPCHK(c, e0.ensure());
+        HIPCHK(c, e1.ensure());
+        c->ev0 = std::move(e0);
+        c->ev1 = std::move(e1);
     }
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     return RT_OK;
@@ -270,17 +276,17 @@ int rt_kernel_time(rt_ctx* c, int reset, double* total_ms, uint32_t* launches)
 {
     if (!c) return RT_E_INVALID;
     if (int r = set_dev(c)) return r;
-    KernelTiming& k = c->ktime;
+    auto& ev = c->ktime.ev;
     double tot = 0.0;
-    for (size_t i = 0; i + 1 < k.used; i += 2) {
-        HIPCHK(c, hipEventSynchronize(k.ev[i + 1]));
+    for (size_t i = 0; i + 1 < ev.used; i += 2) {
+        HIPCHK(c, hipEventSynchronize(ev[i + 1]));
         float ms = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&ms, k.ev[i], k.ev[i + 1]));
+        HIPCHK(c, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
         tot += ms;
     }
     if (total_ms) *total_ms = tot;
-    if (launches) *launches = (uint32_t)(k.used / 2);
-    if (reset) k.used = 0;
+    if (launches) *launches = (uint32_t)(ev.used / 2);
+    if (reset) ev.used = 0;
     return RT_OK;
 }
 
@@ -300,8 +306,7 @@ int rt_last_counts(rt_ctx* c, rt_ray_counts* counts)
     if (int r = set_dev(c)) return r;
     unsigned long long h[32];
     static_assert(sizeof(rt_ray_counts) <= sizeof h, "counter buffer");
-    HIPCHK(c, hipMemcpyAsync(h, c->counters.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int r = read_back(c, h, c->counters.p, sizeof h)) return r;
     uint64_t* dst = reinterpret_cast<uint64_t*>(counts);
     for (size_t i = 0; i < sizeof(rt_ray_counts) / sizeof(uint64_t); i++) dst[i] = h[i];
     // the camera rays RT_OPT_EMPTY_PIXELS did not cast are rays the reference's shader casts
@@ -320,9 +325,8 @@ int rt_last_elided_shadows(rt_ctx* c, uint64_t* elided)
     // the counter after rt_ray_counts' members (C_ELIDED); the timed instantiations leave it 0
     static_assert(sizeof(rt_ray_counts) / sizeof(uint64_t) < 32, "counter buffer");
     unsigned long long h = 0;
-    HIPCHK(c, hipMemcpyAsync(&h, c->counters.as<unsigned long long>() + sizeof(rt_ray_counts) / sizeof(uint64_t),
-                             sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int r = read_back(c, &h, c->counters.as<unsigned long long>() + sizeof(rt_ray_counts) / sizeof(uint64_t), sizeof h))
+        return r;
     *elided = h;
     return RT_OK;
 }
@@ -349,10 +353,7 @@ int rt_download_empty_mask(rt_ctx* c, uint32_t* mask_words, uint64_t nwords)
     if (!c->empty.used) return RT_OK;
     if (int r = set_dev(c)) return r;
     const uint64_t have = ((uint64_t)c->u.resolution[0] * c->u.resolution[1] + 31) / 32;
-    HIPCHK(c, hipMemcpyAsync(mask_words, c->empty.mask.p, (size_t)std::min(have, nwords) * 4, hipMemcpyDeviceToHost,
-                             c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RT_OK;
+    return read_back(c, mask_words, c->empty.mask.p, (size_t)std::min(have, nwords) * 4);
 }
 
 int rt_last_pixel_depth(rt_ctx* c, float* near_out, float* far_out, uint64_t npix, int* in_use)
@@ -367,8 +368,7 @@ int rt_last_pixel_depth(rt_ctx* c, float* near_out, float* far_out, uint64_t npi
     if (int r = set_dev(c)) return r;
     const uint64_t have = std::min<uint64_t>((uint64_t)c->u.resolution[0] * c->u.resolution[1], npix);
     std::vector<float> pairs((size_t)have * 2);
-    HIPCHK(c, hipMemcpyAsync(pairs.data(), c->empty.depth.p, pairs.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int r = read_back(c, pairs.data(), c->empty.depth.p, pairs.size() * 4)) return r;
     for (uint64_t i = 0; i < have; i++) {
         near_out[i] = pairs[2 * i];
         far_out[i] = pairs[2 * i + 1];
@@ -393,8 +393,7 @@ int rt_selftest_math(rt_ctx* c, uint32_t n, float lo, float hi, uint32_t* mismat
     HIPCHK(c, dres.alloc(dout.size() * 4));
     if (rtk::launch_selftest_math(din.as<float>(), dres.as<float>(), n, c->stream))
         return fail(c, RT_E_DEVICE, "rt_selftest_math: launch failed");
-    HIPCHK(c, hipMemcpyAsync(dout.data(), dres.p, dout.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int r = read_back(c, dout.data(), dres.p, dout.size() * 4)) return r;
     uint32_t bad = 0;
     for (size_t i = 0; i < dout.size(); i++) {
         uint32_t a, b;

@@ -1,6 +1,7 @@
 // rt_ctx.h -- the context behind the C ABI (include/rt.h) and what the files that
 // implement it share: rt_context.cpp, rt_scene.cpp, rt_render.cpp, rt_estimate.cpp,
-// rt_denoise_api.cpp and rt_gather.cpp (and rt_modes.cpp's table).  Not part of the public ABI.
+// rt_denoise_api.cpp and rt_gather.cpp (and rt_modes.cpp's table); rt_build.hip takes Event
+// from here.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +15,7 @@
 
 #include "host_types.h"
 #include "rt_internal.h"
+#include "rt_own.h"
 #include "rt_prims.h"
 
 struct DevBuf {
@@ -51,6 +53,34 @@ struct DevBuf {
         return reinterpret_cast<T*>(p);
     }
 };
+
+// The owners of events and streams (rt_own.h): made at the first ensure(), destroyed with
+// the struct that holds them -- like DevBuf's memory, while the device is current and idle
+// (rt_destroy).  An Event takes hipEventDisableTiming as ensure()'s flags.
+struct EventTraits {
+    using type = hipEvent_t;
+    using status = hipError_t;
+    static hipError_t create(hipEvent_t* e, unsigned flags) { return hipEventCreateWithFlags(e, flags); }
+    static void destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+};
+struct StreamTraits {   // non-blocking
+    using type = hipStream_t;
+    using status = hipError_t;
+    static hipError_t create(hipStream_t* s, unsigned) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
+    static void destroy(hipStream_t s) { (void)hipStreamDestroy(s); }
+};
+using Event = Handle<EventTraits>;
+using Stream = Handle<StreamTraits>;
+template <size_t K, size_t Cap>
+using EventPool = Pool<EventTraits, K, Cap>;
+// all of a fixed set of events, for the loops that record into them
+template <size_t N>
+hipError_t ensure_all(Event (&ev)[N])
+{
+    for (Event& e : ev)
+        if (const hipError_t r = e.ensure()) return r;
+    return hipSuccess;
+}
 
 // The scratch of a compacted slot list (the empty-pixel active list, the adaptive live
 // list): the list, and the flags, offsets and scan scratch of its build.
@@ -109,7 +139,7 @@ struct CullState {
     float ms[2] = {0, 0};
     float reach = 0.0f;
     uint32_t probes = 0, launches = 0;
-    hipEvent_t ev[8] = {};
+    Event ev[8];
 };
 
 // RT_OPT_EMPTY_PIXELS (ensure_empty; rt_empty.hip): the mask of cam -- the camera
@@ -122,7 +152,7 @@ struct EmptyState {
     bool has_cam = false, valid = false, tried = false;
     uint64_t iters = 0, flagged = 0;
     float build_ms = 0.0f;
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    Event ev[2];
     DevBuf mask, hit, cnt, big;
     // RT_OPT_PIXEL_DEPTH: the camera's per-pixel {near, far}, built with the mask and
     // living and dying with it; depth_used: the most recent render's k_path read it
@@ -156,7 +186,7 @@ struct AdaptiveState {
 struct DenoiseState {
     DevBuf a, b, var, nz, dz;
     uint32_t lds_step = 4, lattice_step = 0;
-    hipEvent_t ev[6] = {};
+    Event ev[6];
     uint32_t timed = 0, form[5] = {};
 };
 
@@ -168,21 +198,19 @@ struct GatherState {
     struct ncclComm* comm = nullptr;
     uint32_t nranks = 0, rank = 0;
     DevBuf accum, ids;   // rank 0: every rank's packed tiles, rank-major
-    std::vector<hipEvent_t> ev;
-    size_t used = 0;
+    EventPool<3, 3 * 4096> ev;   // ev.used: events recorded since the last reset
 };
 
 // RT_OPT_KERNEL_TIMING: event pairs around traversal-kernel launches (pool reused after reset)
 struct KernelTiming {
     bool on = false;
-    std::vector<hipEvent_t> ev;
-    size_t used = 0;   // events recorded since the last reset (2 per launch)
+    EventPool<2, 8192> ev;   // ev.used: events recorded since the last reset (2 per launch)
 };
 
 struct rt_ctx {
     int device = 0;
-    hipStream_t own = nullptr;
-    hipStream_t stream = nullptr;
+    Stream own;
+    hipStream_t stream = nullptr;   // own's, or the caller's (rt_set_stream)
     std::string err;
     int num_cus = 256;
     int waves_per_cu = 32;   // 8 waves per SIMD: the k_path register budget (RT_PATH_WAVES_PER_EU)
@@ -208,13 +236,14 @@ struct rt_ctx {
     DevBuf bvh_deep;   // BVH stack entries beyond the kernels' LDS share
     DevBuf srgb_thr;   // rt_frame_rgba8's 8-bit sRGB code thresholds
     uint64_t elided_primaries = 0;   // the most recent render: the camera rays it did not cast
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;   // rt_timer_start / rt_timer_stop: both or neither
     KernelTiming ktime;
     // RT_OPT_ASYNC_FOLD: the fold and its consumers on a second stream, the
     // per-sample scratch double-buffered (ev_free[b]: the fold that last read buffer b)
+    // (the stream and the five events exist together or not at all)
     bool async_fold = false;
-    hipStream_t fold_stream = nullptr;
-    hipEvent_t ev_path = nullptr, ev_enter = nullptr, ev_fold = nullptr, ev_free[2] = {nullptr, nullptr};
+    Stream fold_stream;
+    Event ev_path, ev_enter, ev_fold, ev_free[2];
     DevBuf samples2;
     uint32_t sbuf = 0;
     bool fold_pending = false;   // work on fold_stream the context stream has not joined yet
@@ -272,6 +301,8 @@ int fail(rt_ctx* c, int code, const std::string& msg);
     } while (0)
 
 int upload(rt_ctx* c, DevBuf& b, const void* src, size_t bytes);
+// bytes from the device into host memory on the context stream, and the stream synchronised
+int read_back(rt_ctx* c, void* host, const void* dev, size_t bytes);
 int set_dev_nojoin(rt_ctx* c);
 int set_dev(rt_ctx* c);
 int out_stream(rt_ctx* c, hipStream_t* s);
@@ -336,20 +367,16 @@ inline uint32_t cull_in_use(const rt_ctx* c, bool sil = true)
 template <class Launch>
 int launch_timed(rt_ctx* c, const char* what, Launch&& launch)
 {
-    KernelTiming& k = c->ktime;
-    const bool t = k.on && k.used + 2 <= 8192;
+    auto& ev = c->ktime.ev;
+    const bool t = c->ktime.on && !ev.full();
     if (t) {
-        while (k.ev.size() < k.used + 2) {
-            hipEvent_t e;
-            HIPCHK(c, hipEventCreate(&e));
-            k.ev.push_back(e);
-        }
-        HIPCHK(c, hipEventRecord(k.ev[k.used], c->stream));
+        HIPCHK(c, ev.ensure_group());
+        HIPCHK(c, hipEventRecord(ev[ev.used], c->stream));
     }
     if (const int r = launch()) return fail(c, r, std::string(what) + hipGetErrorString(hipGetLastError()));
     if (t) {
-        HIPCHK(c, hipEventRecord(k.ev[k.used + 1], c->stream));
-        k.used += 2;
+        HIPCHK(c, hipEventRecord(ev[ev.used + 1], c->stream));
+        ev.used += 2;
     }
     return RT_OK;
 }

@@ -49,9 +49,7 @@ int dn_run_levels(rt_ctx* c, const char* who, uint32_t width, uint32_t height, c
         return fail(c, RT_E_DEVICE, std::string(who) + ": pack launch failed");
     const bool timed = c->ktime.on;
     d.timed = 0;
-    if (timed)
-        for (hipEvent_t& e : d.ev)
-            if (!e) HIPCHK(c, hipEventCreate(&e));
+    if (timed) HIPCHK(c, ensure_all(d.ev));
     float* src = d.a.as<float>();
     float* dst = d.b.as<float>();
     for (uint32_t i = 0; i < levels; i++) {

@@ -94,8 +94,7 @@ int rt_noise_summarize(rt_ctx* c, const rt_noise_state* state, uint32_t npix, ui
     if (rtk::launch_noise_summary(state, npix, n, threshold, floor, c->noise_sum.as<unsigned long long>(), c->stream))
         return fail(c, RT_E_DEVICE, "rt_noise_summarize: launch failed");
     unsigned long long h[3] = {0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(h, c->noise_sum.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int r = read_back(c, h, c->noise_sum.p, sizeof h)) return r;
     out->above = h[0];
     out->nonfinite = h[1];
     const uint32_t bits = (uint32_t)h[2];
@@ -184,8 +183,7 @@ int rt_adaptive_summarize(rt_ctx* c, const rt_noise_state* state, const uint32_t
     if (rtk::launch_adaptive_summary(L, state, count, P, stats.as<unsigned long long>(), c->stream))
         return fail(c, RT_E_DEVICE, "rt_adaptive_summarize: launch failed");
     unsigned long long h[9] = {};
-    HIPCHK(c, hipMemcpyAsync(h, stats.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int r = read_back(c, h, stats.p, sizeof h)) return r;
     out->live_next = h[0];
     out->above = h[2];
     out->nonfinite = h[3];

@@ -35,19 +35,12 @@ void srgb_code_thresholds(float* t)
 // only when the first was recorded, so the pool stays in whole triples).
 hipEvent_t gather_event(rt_ctx* c, hipStream_t s)
 {
-    GatherState& g = c->gather;
+    auto& ev = c->gather.ev;
     if (!c->ktime.on) return nullptr;
-    if (g.used % 3 == 0) {
-        if (g.used >= 3 * 4096) return nullptr;
-        while (g.ev.size() < g.used + 3) {
-            hipEvent_t e;
-            if (hipEventCreate(&e) != hipSuccess) return nullptr;
-            g.ev.push_back(e);
-        }
-    }
-    hipEvent_t e = g.ev[g.used];
+    if (ev.used % 3 == 0 && (ev.full() || ev.ensure_group() != hipSuccess)) return nullptr;
+    hipEvent_t e = ev[ev.used];
     (void)hipEventRecord(e, s);
-    g.used++;
+    ev.used++;
     return e;
 }
 
@@ -261,20 +254,20 @@ int rt_gather_time(rt_ctx* c, int reset, double* transfer_ms, double* unpack_ms,
 {
     if (!c) return RT_E_INVALID;
     if (int r = set_dev(c)) return r;
-    GatherState& g = c->gather;
+    auto& ev = c->gather.ev;
     double tx = 0.0, up = 0.0;
-    for (size_t i = 0; i + 2 < g.used; i += 3) {
-        HIPCHK(c, hipEventSynchronize(g.ev[i + 2]));
+    for (size_t i = 0; i + 2 < ev.used; i += 3) {
+        HIPCHK(c, hipEventSynchronize(ev[i + 2]));
         float a = 0.0f, b = 0.0f;
-        HIPCHK(c, hipEventElapsedTime(&a, g.ev[i], g.ev[i + 1]));
-        HIPCHK(c, hipEventElapsedTime(&b, g.ev[i + 1], g.ev[i + 2]));
+        HIPCHK(c, hipEventElapsedTime(&a, ev[i], ev[i + 1]));
+        HIPCHK(c, hipEventElapsedTime(&b, ev[i + 1], ev[i + 2]));
         tx += a;
         up += b;
     }
     if (transfer_ms) *transfer_ms = tx;
     if (unpack_ms) *unpack_ms = up;
-    if (calls) *calls = (uint32_t)(g.used / 3);
-    if (reset) g.used = 0;
+    if (calls) *calls = (uint32_t)(ev.used / 3);
+    if (reset) ev.used = 0;
     return RT_OK;
 }
 

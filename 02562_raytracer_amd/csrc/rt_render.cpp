@@ -170,14 +170,12 @@ int ensure_empty(rt_ctx* c, const float cam14[14], uint32_t spp, bool* use)
         unsigned long long area = 0;
         uint32_t nbig = 0;
         HIPCHK(c, hipMemcpyAsync(&area, area_d, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&nbig, nbig_d, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (int r = read_back(c, &nbig, nbig_d, 4)) return r;   // (one synchronise for both)
         if (area <= kEmptyBudgetPerPixel * npix) {
             HIPCHK(c, m.hit.ensure(npix));
             HIPCHK(c, m.mask.ensure((npix + 31) / 32 * 4));
             HIPCHK(c, m.depth.ensure(npix * sizeof(uint2)));
-            for (hipEvent_t& e : m.ev)
-                if (!e) HIPCHK(c, hipEventCreate(&e));
+            HIPCHK(c, ensure_all(m.ev));
             HIPCHK(c, hipEventRecord(m.ev[0], c->stream));
             if (rtk::launch_empty_mask(s.pos.as<float4>(), s.idx.as<uint4>(), s.nverts, s.ntris, cam14, W, H,
                                        s.mesh_scale, m.big.as<uint32_t>(), std::min(nbig, s.ntris), m.hit.as<uint8_t>(),
@@ -185,8 +183,7 @@ int ensure_empty(rt_ctx* c, const float cam14[14], uint32_t spp, bool* use)
                 return fail(c, RT_E_DEVICE, "empty-pixel mask: launch failed");
             HIPCHK(c, hipEventRecord(m.ev[1], c->stream));
             uint32_t flagged = 0;
-            HIPCHK(c, hipMemcpyAsync(&flagged, flagged_d, 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (int r = read_back(c, &flagged, flagged_d, 4)) return r;
             HIPCHK(c, hipEventElapsedTime(&m.build_ms, m.ev[0], m.ev[1]));
             m.flagged = flagged;
             m.valid = true;
@@ -249,8 +246,7 @@ int probe_launch(rt_ctx* c, const rtk::DevScene& S, const rtk::DevLaunch& L, rt_
 {
     if (slot < 0) return launch_walk(c, S, L, mode, trav);
     CullState& k = c->cull;
-    for (hipEvent_t& e : k.ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
+    HIPCHK(c, ensure_all(k.ev));
     if (slot == 0) {
         k.probes++;
         k.reach = eye_reach(c);
@@ -319,7 +315,7 @@ int fill_launch(rt_ctx* c, rt_traverse trav, rtk::DevLaunch& L)
     L.cap_max = c->cap_max;
     if (trav == RT_TRAVERSE_BVH) {
         const size_t need = rtk::bvh_deep_bytes(c->num_cus, c->waves_per_cu);
-        if (c->bvh_deep.n < need) HIPCHK(c, c->bvh_deep.alloc(need));
+        HIPCHK(c, c->bvh_deep.ensure(need));
         L.bvh_deep = c->bvh_deep.as<uint32_t>();
     }
     return RT_OK;
@@ -394,8 +390,8 @@ int path_setup(rt_ctx* c, const rtk::DevScene& S, rtk::DevLaunch& L, rt_mode mod
     P.pass_spp = (uint32_t)std::min<uint64_t>(L.spp, std::max<uint64_t>(1, budget / per_it));
     const uint64_t need = per_it * P.pass_spp;
     P.async = c->async_fold && c->fold_stream;
-    if (c->samples.n < need) HIPCHK(c, c->samples.alloc(need));
-    if (P.async && c->samples2.n < need) HIPCHK(c, c->samples2.alloc(need));
+    HIPCHK(c, c->samples.ensure(need));   // (need > 0: a launch has pixels and a path pass an iteration)
+    if (P.async) HIPCHK(c, c->samples2.ensure(need));
     L.samples = c->samples.as<float4>();
     // (a counting render, RT_OPT_DETAIL_COUNTERS, runs other kernels: it never probes)
     P.autop = sil && c->bsp_cull == RT_BSP_CULL_AUTO && c->cull.cam_valid && !c->detail && !P.nothing_active;
@@ -410,7 +406,7 @@ int path_setup(rt_ctx* c, const rtk::DevScene& S, rtk::DevLaunch& L, rt_mode mod
 int path_passes(rt_ctx* c, rtk::DevScene& S, rtk::DevLaunch& L, rt_mode mode, rt_traverse trav, bool sil,
                 const PathSetup& P)
 {
-    const hipStream_t fs = P.async ? c->fold_stream : c->stream;
+    const hipStream_t fs = P.async ? c->fold_stream.get() : c->stream;
     if (P.async) {   // the folds follow the context stream's work up to here
         HIPCHK(c, hipEventRecord(c->ev_enter, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c->fold_stream, c->ev_enter, 0));
@@ -638,9 +634,7 @@ int rt_ray_capture_count(rt_ctx* c, uint64_t* n)
     if (int r = set_dev(c)) return r;
     *n = 0;
     if (!c->cap_count.p) return RT_OK;
-    HIPCHK(c, hipMemcpyAsync(n, c->cap_count.p, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RT_OK;
+    return read_back(c, n, c->cap_count.p, 8);
 }
 
 int rt_trace_batch(rt_ctx* c, rt_traverse trav, const float* rays_dev, const uint32_t* flags_dev, uint32_t n,
@@ -677,7 +671,7 @@ int rt_trace_rays(rt_ctx* c, rt_traverse trav, const float* rays, const uint32_t
     uint32_t* deep = nullptr;
     if (trav == RT_TRAVERSE_BVH) {
         const size_t need = rtk::bvh_deep_bytes(c->num_cus, 16);
-        if (c->bvh_deep.n < need) HIPCHK(c, c->bvh_deep.alloc(need));
+        HIPCHK(c, c->bvh_deep.ensure(need));
         deep = c->bvh_deep.as<uint32_t>();
     }
     if (trav == RT_TRAVERSE_BSP)

@@ -28,8 +28,7 @@ int repack_bsp(rt_ctx* c, uint32_t nnodes, uint32_t nids, size_t rec_off, size_t
                                 s.bsp.plane_flag.as<uint32_t>(), c->stream))
         return fail(c, RT_E_DEVICE, "BSP plane range launch failed");
     uint32_t pflag = 1;
-    HIPCHK(c, hipMemcpyAsync(&pflag, s.bsp.plane_flag.p, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int r = read_back(c, &pflag, s.bsp.plane_flag.p, 4)) return r;
     s.bsp.div_checked = pflag != 0u;
     float scale = 0.0f;
     for (int k : {0, 1, 2, 4, 5, 6})
