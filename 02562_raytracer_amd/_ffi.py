@@ -93,6 +93,7 @@ RT_OPT_EMPTY_PIXELS = 11   # 0 off, 1 on (default), 2 on and built at the first 
 RT_OPT_PIXEL_DEPTH = 12    # 0 off, 1 on (default): camera rays start on their pixel's certified depth range
 RT_OPT_DENOISE_LDS_STEP = 13   # the largest step whose denoise level stages its tile in LDS: 0, 1, 2, 4 or 8
 RT_OPT_DENOISE_LATTICE_STEP = 14   # the smallest step that runs the lattice form: 0 (never, default), 2, 4, 8 or 16
+RT_OPT_TEMPORAL_VAR_LDS = 15   # 1 (default) / 0: rt_temporal_variance stages its tile in LDS or loads every neighbour
 RT_BSP_CULL_OFF, RT_BSP_CULL_CERTIFIED, RT_BSP_CULL_FAST, RT_BSP_CULL_SILHOUETTE, RT_BSP_CULL_AUTO = range(5)
 BSP_TREELET_BYTES = 96   # rt_internal.h: the BSP walk's treelet (rt_download_bsp_treelets)
 RT_OPT_KERNEL_TIMING = 7
@@ -284,6 +285,11 @@ SIGNATURES = {
     "rt_denoise": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_float, C.c_float,
                              vp]),
     "rt_denoise_level_times": (C.c_int, [vp, f32p, u32p]),
+    "rt_temporal_accumulate": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, C.c_float, vp, C.POINTER(Uniform), vp, vp, vp,
+                                         vp, C.c_uint32, C.c_float, C.c_float, vp, vp, vp]),
+    "rt_temporal_variance": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_float, C.c_float,
+                                       vp]),
+    "rt_temporal_times": (C.c_int, [vp, f32p, f32p, u32p]),
     "rt_unpack_tiles": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "rt_comm_unique_id": (C.c_int, [vp]),
     "rt_comm_init": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),

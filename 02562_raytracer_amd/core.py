@@ -525,6 +525,35 @@ class Context:
         self._chk(F.lib().rt_denoise_level_times(self._h, ms, form))
         return [float(x) for x in ms], [int(x) for x in form]
 
+    # ---- temporal accumulation (include/rt.h "temporal accumulation"; device pointers, asynchronous)
+    def temporal_accumulate(self, width, height, color_ptr, color_scale, nz_ptr, prev_uniform, hist, out,
+                            max_history=32, normal_min=0.9, plane_tol=0.01):
+        """rt_temporal_accumulate: the frame in color_ptr (x color_scale) blended with the history
+        reprojected from prev_uniform's camera.  hist: (color, moments, length, nz) device pointers
+        with prev_uniform, or None with None (a first frame); out: (color, moments, length)."""
+        h = tuple(hist) if hist is not None else (None,) * 4
+        vpn = (lambda p: C.c_void_p(p) if p else None)
+        self._chk(F.lib().rt_temporal_accumulate(
+            self._h, width, height, vpn(color_ptr), float(color_scale), vpn(nz_ptr),
+            C.byref(prev_uniform) if prev_uniform is not None else None, vpn(h[0]), vpn(h[1]), vpn(h[2]), vpn(h[3]),
+            int(max_history), float(normal_min), float(plane_tol), vpn(out[0]), vpn(out[1]), vpn(out[2])))
+
+    def temporal_variance(self, width, height, mom_ptr, len_ptr, nz_ptr, dz_ptr, var_ptr, min_len=4, normal_min=0.9,
+                          plane_tol=0.01):
+        """rt_temporal_variance: the variance of the integrated mean luminance; a pixel with fewer
+        than min_len frames takes its 7 x 7 neighbours' moments."""
+        vpn = (lambda p: C.c_void_p(p) if p else None)
+        self._chk(F.lib().rt_temporal_variance(self._h, width, height, vpn(mom_ptr), vpn(len_ptr), vpn(nz_ptr),
+                                               vpn(dz_ptr), int(min_len), float(normal_min), float(plane_tol),
+                                               vpn(var_ptr)))
+
+    def temporal_times(self):
+        """rt_temporal_times: (accumulate ms, variance ms, variance form: 0 direct, 1 LDS tile) of the
+        most recent calls (RT_OPT_KERNEL_TIMING); synchronizes."""
+        a, v, f = C.c_float(0), C.c_float(0), C.c_uint32(0)
+        self._chk(F.lib().rt_temporal_times(self._h, C.byref(a), C.byref(v), C.byref(f)))
+        return float(a.value), float(v.value), int(f.value)
+
     # ---- the tile gather over RCCL (include/rt.h "multi-GPU")
     @staticmethod
     def comm_unique_id():

@@ -202,6 +202,8 @@ int rt_set_option(rt_ctx* c, int option, int64_t value)
             return fail(c, RT_E_INVALID, "denoise lattice step must be 0, 2, 4, 8 or 16");
         c->denoise.lattice_step = (uint32_t)value;
         return RT_OK;
+    case RT_OPT_TEMPORAL_VAR_LDS:
+        return ranged(0, 1, "temporal variance LDS must be 0 (global loads) or 1 (LDS tile)", c->temporal.var_lds);
     case RT_OPT_SAMPLE_BUDGET_MB:
         return ranged(1, 1 << 20, "sample budget must be in [1,2^20] MiB", c->sample_budget_mb);
     default:

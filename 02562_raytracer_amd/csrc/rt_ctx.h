@@ -1,6 +1,6 @@
 // rt_ctx.h -- the context behind the C ABI (include/rt.h) and what the files that
 // implement it share: rt_context.cpp, rt_scene.cpp, rt_render.cpp, rt_estimate.cpp,
-// rt_denoise_api.cpp and rt_gather.cpp (and rt_modes.cpp's table); rt_build.hip takes Event
+// rt_denoise_api.cpp, rt_temporal_api.cpp and rt_gather.cpp (and rt_modes.cpp's table); rt_build.hip takes Event
 // from here.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -190,6 +190,16 @@ struct DenoiseState {
     uint32_t timed = 0, form[5] = {};
 };
 
+// temporal accumulation (rt.h "temporal accumulation"): RT_OPT_TEMPORAL_VAR_LDS; the events
+// around the most recent rt_temporal_accumulate (ev[0], ev[1]) and rt_temporal_variance
+// (ev[2], ev[3]) with RT_OPT_KERNEL_TIMING, and the form the latter ran
+struct TemporalState {
+    bool var_lds = true;   // measured 2.2 x faster than the direct form (profiles/r13/temporal_bench.txt)
+    Event ev[4];
+    bool acc_timed = false, var_timed = false;
+    uint32_t var_form = 0;
+};
+
 // rt_comm_init: the tile gather's RCCL communicator (rt_gather_tiles; an ncclComm_t,
 // named here without the RCCL header), rank 0's buffers, and -- RT_OPT_KERNEL_TIMING,
 // rt_gather_time -- event triples {before the transfers, after them, after the unpack}
@@ -258,6 +268,7 @@ struct rt_ctx {
     AdaptiveState adapt;
     EmptyState empty;
     DenoiseState denoise;
+    TemporalState temporal;
     GatherState gather;
 };
 

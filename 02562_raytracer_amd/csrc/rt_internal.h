@@ -289,6 +289,38 @@ int launch_denoise_level(const float* cv, const float* nz, const float* dz, uint
                          float sigma_l, float sigma_z, int form, float* out_cv, float* out_color, float* out_var,
                          hipStream_t stream);
 
+// Temporal accumulation (rt_temporal.hip; rt.h "temporal accumulation").  cam / pcam:
+// camera_basis's terms of the current and the previous uniform; the history pointers are all
+// null on a first frame; still: the two cameras are bit-equal (the tap is the pixel itself).
+struct TemporalArgs {
+    float cam[14], pcam[14];
+    uint32_t w, h;
+    const float* color;
+    const float* nz;
+    const float* hist_color;
+    const float* hist_mom;
+    const uint32_t* hist_len;
+    const float* hist_nz;
+    float color_scale, normal_min, plane_tol;
+    uint32_t max_history, still;
+    float* out_color;
+    float* out_mom;
+    uint32_t* out_len;
+};
+int launch_temporal_accumulate(const TemporalArgs& a, hipStream_t stream);
+struct TemporalVarArgs {
+    const float* mom;
+    const uint32_t* len;
+    const float* nz;
+    const float* dz;
+    float* var;
+    int w, h;
+    uint32_t min_len;
+    float normal_min, plane_tol;
+};
+// lds: the block's 22 x 22 tile staged in LDS; else every neighbour from global memory.  The same bits
+int launch_temporal_variance(const TemporalVarArgs& a, bool lds, hipStream_t stream);
+
 // display frame: RGBA32F accum -> 8-bit sRGB (thr: 255 device floats, srgb_code_thresholds)
 int launch_frame(const float4* accum, uint32_t npix, const float* thr, uchar4* out, hipStream_t stream);
 // the same without the pow, for the modes whose shader returns its colour as it is

@@ -357,6 +357,7 @@ void RenderState::release()
         rt_device_free(gpu_.ctx(), noise_);
     }
     accum_ = ids_ = tile_accum_ = tile_ids_ = noise_ = counts_ = nullptr;
+    disable_temporal();
 }
 
 // the k_path modes (rt.h "noise estimate")
@@ -491,6 +492,7 @@ void RenderState::set_tiling(uint32_t nranks, uint32_t rank, const uint8_t comm_
     if (counts_) throw Error(RT_E_UNSUPPORTED, "set_tiling: adaptive sampling is enabled (it is for an untiled state)");
     // the noise buffer is width x height states, row-major; tile renders would write it packed per tile
     if (noise_) throw Error(RT_E_UNSUPPORTED, "set_tiling: the noise estimate is enabled (it is for an untiled state)");
+    if (temporal_) throw Error(RT_E_UNSUPPORTED, "set_tiling: temporal accumulation is enabled (it is for an untiled state)");
     gpu_.check(rt_comm_init(gpu_.ctx(), nranks, rank, comm_id), "communicator");
     nranks_ = nranks;
     rank_ = rank;
@@ -564,7 +566,7 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
     }
     gpu_.check(rt_set_environment(c, opts_.environment.data()), "environment");
     gpu_.check(rt_set_environment_map(c, nullptr, 0, 0), "environment map");
-    const bool had_noise = noise_ != nullptr, had_adaptive = counts_ != nullptr;
+    const bool had_noise = noise_ != nullptr, had_adaptive = counts_ != nullptr, had_temporal = temporal_;
     release();
     const size_t npx = (size_t)width_ * height_;
     gpu_.check(rt_device_alloc(c, npx * 16, &accum_), "accumulation buffer");
@@ -574,6 +576,7 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
     iteration_ = 0;
     if (had_noise && writes_records(row_)) enable_noise();   // the buffer follows the scene
     if (had_adaptive && writes_records(row_)) enable_adaptive(ad_target_, ad_floor_, ad_min_, ad_vote_);
+    if (had_temporal && writes_records(row_)) enable_temporal(tp_max_history_, tp_normal_min_, tp_plane_tol_, tp_min_len_);
     update();
 }
 
@@ -587,10 +590,10 @@ void RenderState::update()
 {
     camera_.aspect = (float)width_ / (float)height_;
     controller_.update_camera(camera_);
-    const rt_uniform u = make_uniform(camera_, width_, height_, selection1_, subdivision_, iteration_, selection2_,
-                                      use_texture_, uv_scale_);
+    uniform_ = make_uniform(camera_, width_, height_, selection1_, subdivision_, iteration_, selection2_, use_texture_,
+                            uv_scale_);
     const auto jit = compute_jitters(1.0 / (double)height_, subdivision_);
-    gpu_.check(rt_set_uniforms(gpu_.ctx(), &u, &jit[0][0]), "set uniforms");
+    gpu_.check(rt_set_uniforms(gpu_.ctx(), &uniform_, &jit[0][0]), "set uniforms");
 }
 
 void RenderState::render(uint32_t spp)
@@ -730,6 +733,179 @@ std::vector<uint8_t> RenderState::denoised_rgba8(uint32_t levels, float sigma_l,
     rt_device_free(gpu_.ctx(), d);
     gpu_.check(rc, "denoised_rgba8");
     return out;
+}
+
+// ---- temporal accumulation (rt.h "temporal accumulation")
+static const char* const kTemporalUntiled =
+    " is for an untiled state: reprojection needs every pixel's neighbours, and a tiled render (set_tiling, any rank "
+    "count) keeps its buffers packed per tile";
+
+void RenderState::enable_temporal(uint32_t max_history, float normal_min, float plane_tol, uint32_t min_len)
+{
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("enable_temporal") + kTemporalUntiled);
+    if (!writes_records(row_))
+        throw Error(RT_E_UNSUPPORTED, "enable_temporal: the mode writes no per-iteration records (a path mode only)");
+    if (max_history < 1 || min_len < 1 || !(plane_tol >= 0.0f) || normal_min != normal_min)
+        throw Error(RT_E_INVALID, "enable_temporal: max_history and min_len >= 1, plane_tol >= 0, normal_min a number");
+    disable_temporal();
+    rt_ctx* c = gpu_.ctx();
+    const size_t npx = (size_t)width_ * height_;
+    try {
+        gpu_.check(rt_device_alloc(c, npx * 16, &tp_cur_), "temporal frame buffer");
+        gpu_.check(rt_device_alloc(c, npx * 4, &tp_ids_), "temporal id buffer");
+        gpu_.check(rt_device_alloc(c, npx * 8, &tp_dz_), "temporal guide buffer");
+        for (TemporalSet& s : tp_set_) {
+            gpu_.check(rt_device_alloc(c, npx * 16, &s.color), "temporal history colour");
+            gpu_.check(rt_device_alloc(c, npx * 8, &s.mom), "temporal history moments");
+            gpu_.check(rt_device_alloc(c, npx * 4, &s.len), "temporal history length");
+            gpu_.check(rt_device_alloc(c, npx * 16, &s.nz), "temporal history guide");
+        }
+    } catch (...) {
+        disable_temporal();   // a failed allocation leaves the state off, with nothing held
+        throw;
+    }
+    temporal_ = true;
+    tp_max_history_ = max_history;
+    tp_normal_min_ = normal_min;
+    tp_plane_tol_ = plane_tol;
+    tp_min_len_ = min_len;
+    tp_latest_ = -1;
+    tp_k_ = 0;
+}
+
+void RenderState::disable_temporal()
+{
+    rt_ctx* c = gpu_.ctx();
+    void** const bufs[] = {&tp_cur_,          &tp_ids_,        &tp_dz_,         &tp_set_[0].color, &tp_set_[0].mom, &tp_set_[0].len,
+                           &tp_set_[0].nz,    &tp_set_[1].color, &tp_set_[1].mom, &tp_set_[1].len,   &tp_set_[1].nz};
+    for (void** b : bufs) {
+        if (*b) rt_device_free(c, *b);
+        *b = nullptr;
+    }
+    temporal_ = false;
+    tp_latest_ = -1;
+}
+
+void RenderState::temporal_step(uint32_t spp)
+{
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("temporal_step") + kTemporalUntiled);
+    if (!temporal_) throw Error(RT_E_NOT_READY, "temporal_step: enable_temporal() first");
+    if (spp < 1) throw Error(RT_E_INVALID, "temporal_step: spp must be at least 1");
+    rt_ctx* c = gpu_.ctx();
+    const size_t npx = (size_t)width_ * height_;
+    gpu_.check(rt_memset_device(c, tp_cur_, 0, npx * 16), "clear temporal frame");
+    // the frame is not the progressive render's: its noise state and counts stay as they are
+    if (counts_) gpu_.check(rt_set_adaptive(c, nullptr, 0.0f, 0.0f, 0, 0), "set adaptive");
+    if (noise_) gpu_.check(rt_set_noise_buffer(c, nullptr), "set noise buffer");
+    const rt_tile region{0, 0, width_, height_};
+    const int rc = rt_render(c, mode(), trav_, &region, tp_k_, spp, static_cast<float*>(tp_cur_),
+                             static_cast<uint32_t*>(tp_ids_), nullptr);
+    if (noise_) gpu_.check(rt_set_noise_buffer(c, static_cast<rt_noise_state*>(noise_)), "set noise buffer");
+    if (counts_)
+        gpu_.check(rt_set_adaptive(c, static_cast<uint32_t*>(counts_), ad_target_, ad_floor_, ad_min_, ad_vote_), "set adaptive");
+    gpu_.check(rc, "temporal render");
+    const TemporalSet& out = tp_set_[tp_latest_ < 0 ? 0 : 1 - tp_latest_];
+    // the guide of the camera that rendered the frame: before update() moves it
+    gpu_.check(rt_denoise_guide(c, width_, height_, static_cast<const uint32_t*>(tp_ids_), static_cast<float*>(out.nz),
+                                static_cast<float*>(tp_dz_)),
+               "temporal guide");
+    const TemporalSet* old = tp_latest_ < 0 ? nullptr : &tp_set_[tp_latest_];
+    const float scale = (float)(tp_k_ + spp) / (float)spp;
+    gpu_.check(rt_temporal_accumulate(c, width_, height_, static_cast<const float*>(tp_cur_), scale,
+                                      static_cast<const float*>(out.nz), old ? &tp_uniform_ : nullptr,
+                                      old ? static_cast<const float*>(old->color) : nullptr,
+                                      old ? static_cast<const float*>(old->mom) : nullptr,
+                                      old ? static_cast<const uint32_t*>(old->len) : nullptr,
+                                      old ? static_cast<const float*>(old->nz) : nullptr, tp_max_history_, tp_normal_min_,
+                                      tp_plane_tol_, static_cast<float*>(out.color), static_cast<float*>(out.mom),
+                                      static_cast<uint32_t*>(out.len)),
+               "temporal accumulate");
+    tp_latest_ = tp_latest_ < 0 ? 0 : 1 - tp_latest_;
+    tp_uniform_ = uniform_;
+    tp_k_ += spp;
+    update();
+}
+
+// the filtered latest frame on the device (the caller frees it)
+void* RenderState::temporal_device(uint32_t levels, float sigma_l, float sigma_z) const
+{
+    if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("temporal_frame") + kTemporalUntiled);
+    if (!temporal_ || tp_latest_ < 0) throw Error(RT_E_NOT_READY, "temporal_frame: enable_temporal() and temporal_step() first");
+    if (levels < 1 || levels > 5 || !(sigma_l > 0.0f) || !(sigma_z > 0.0f))
+        throw Error(RT_E_INVALID, "temporal_frame: levels in 1..5, sigmas > 0");
+    rt_ctx* c = gpu_.ctx();
+    const size_t npx = (size_t)width_ * height_;
+    const TemporalSet& s = tp_set_[tp_latest_];
+    void *var = nullptr, *d = nullptr;
+    gpu_.check(rt_device_alloc(c, npx * 4, &var), "temporal variance buffer");
+    int rc = rt_device_alloc(c, npx * 16, &d);
+    if (rc == RT_OK)
+        rc = rt_temporal_variance(c, width_, height_, static_cast<const float*>(s.mom), static_cast<const uint32_t*>(s.len),
+                                  static_cast<const float*>(s.nz), static_cast<const float*>(tp_dz_), tp_min_len_,
+                                  tp_normal_min_, tp_plane_tol_, static_cast<float*>(var));
+    if (rc == RT_OK)
+        rc = rt_denoise_filter(c, width_, height_, static_cast<const float*>(s.color), static_cast<const float*>(var),
+                               static_cast<const float*>(s.nz), static_cast<const float*>(tp_dz_), levels, sigma_l, sigma_z,
+                               static_cast<float*>(d), nullptr);
+    if (rc == RT_OK) rc = rt_synchronize(c);
+    rt_device_free(c, var);
+    if (rc != RT_OK && d) rt_device_free(c, d);
+    gpu_.check(rc, "temporal_frame");
+    return d;
+}
+
+std::vector<float> RenderState::temporal_frame(uint32_t levels, float sigma_l, float sigma_z) const
+{
+    void* d = temporal_device(levels, sigma_l, sigma_z);
+    std::vector<float> out((size_t)width_ * height_ * 4);
+    const int rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), d, out.size() * 4);
+    rt_device_free(gpu_.ctx(), d);
+    gpu_.check(rc, "temporal_frame");
+    return out;
+}
+
+std::vector<uint8_t> RenderState::temporal_rgba8(uint32_t levels, float sigma_l, float sigma_z) const
+{
+    void* d = temporal_device(levels, sigma_l, sigma_z);
+    const size_t npx = (size_t)width_ * height_;
+    void* img = nullptr;
+    int rc = rt_device_alloc(gpu_.ctx(), npx * 4, &img);
+    std::vector<uint8_t> out(npx * 4);
+    if (rc == RT_OK)
+        rc = rt_frame_rgba8_mode(gpu_.ctx(), mode(), static_cast<const float*>(d), (uint32_t)npx, static_cast<uint8_t*>(img));
+    if (rc == RT_OK) rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), img, out.size());
+    rt_device_free(gpu_.ctx(), img);
+    rt_device_free(gpu_.ctx(), d);
+    gpu_.check(rc, "temporal_rgba8");
+    return out;
+}
+
+RenderState::TemporalCurrent RenderState::temporal_current() const
+{
+    if (!temporal_ || tp_latest_ < 0) throw Error(RT_E_NOT_READY, "temporal_current: enable_temporal() and temporal_step() first");
+    const size_t npx = (size_t)width_ * height_;
+    TemporalCurrent cur;
+    cur.accum.resize(npx * 4);
+    cur.ids.resize(npx);
+    cur.uniform = tp_uniform_;
+    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), cur.accum.data(), tp_cur_, npx * 16), "download temporal frame");
+    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), cur.ids.data(), tp_ids_, npx * 4), "download temporal ids");
+    return cur;
+}
+
+RenderState::TemporalHistory RenderState::temporal_history() const
+{
+    if (!temporal_ || tp_latest_ < 0) throw Error(RT_E_NOT_READY, "temporal_history: enable_temporal() and temporal_step() first");
+    const size_t npx = (size_t)width_ * height_;
+    const TemporalSet& s = tp_set_[tp_latest_];
+    TemporalHistory h;
+    h.color.resize(npx * 4);
+    h.moments.resize(npx * 2);
+    h.length.resize(npx);
+    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), h.color.data(), s.color, npx * 16), "download temporal colour");
+    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), h.moments.data(), s.mom, npx * 8), "download temporal moments");
+    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), h.length.data(), s.len, npx * 4), "download temporal length");
+    return h;
 }
 
 rt_ray_counts RenderState::last_counts() const

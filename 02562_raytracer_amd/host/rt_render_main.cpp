@@ -36,6 +36,22 @@
 //                                        also writes PREFIX.denoised.f32 (H*W*4 float32) and
 //                                        PREFIX.denoised.rgba8 (its sRGB frame); refused with
 //                                        --comm-file / --nranks)
+//             [--temporal-frames N [--temporal-history M] [--temporal-normal-min D] [--temporal-plane-tol P]]
+//                                        (a path-mode scene: after the --updates, N frames of --spp (1)
+//                                        iterations each with the --keys held -- temporal_step: every
+//                                        frame is blended with the history reprojected from the camera
+//                                        before it, rt_temporal_accumulate, at most M (32) frames long,
+//                                        rejecting taps whose normal differs (dot below D, 0.9) or that
+//                                        lie off the pixel's plane (P (0.01) x depth); --out writes
+//                                        PREFIX.temporal.f32 (the integrated frame, H*W*4 float32),
+//                                        PREFIX.temporal.len.u32 (H*W history lengths),
+//                                        PREFIX.temporal.denoised.f32 and PREFIX.temporal.denoised.rgba8
+//                                        (through rt_temporal_variance and rt_denoise_filter, with the
+//                                        parameters of --denoise --denoise-levels / --denoise-sigma-l /
+//                                        --denoise-sigma-z if given: no progressive frame is rendered, so
+//                                        PREFIX.denoised.* is not written) beside the progressive frame's
+//                                        files; refused with --comm-file / --nranks, --noise-target,
+//                                        --adaptive-target and --samples)
 //   rt_render ... --nranks N --rank R --comm-file PATH [--comm-token T] [--device D]
 //                                        (one process per GPU: rank R renders its
 //                                        interleaved tiles, rank 0 gathers the frame
@@ -247,6 +263,26 @@ int main(int argc, char** argv)
             if (!row || row->family != RT_FAMILY_PATH)
                 throw Error(RT_E_UNSUPPORTED, "--denoise: the scene's mode keeps no noise state (a path mode only)");
         }
+        // temporal accumulation reprojects between whole frames of a path mode, one camera move per frame
+        const bool temporal = arg("--temporal-frames") != nullptr;
+        if (!temporal && (arg("--temporal-history") || arg("--temporal-normal-min") || arg("--temporal-plane-tol")))
+            throw Error(RT_E_INVALID, "--temporal-history / --temporal-normal-min / --temporal-plane-tol need --temporal-frames N");
+        if (temporal && (nranks > 1 || arg("--comm-file")))
+            throw Error(RT_E_UNSUPPORTED, "--temporal-frames does not go with --comm-file / --nranks (a tiled render)");
+        if (temporal && (arg("--noise-target") || arg("--adaptive-target") || arg("--samples")))
+            throw Error(RT_E_INVALID, "--temporal-frames does not go with --noise-target, --adaptive-target or --samples");
+        const int tp_frames = temporal ? std::atoi(arg("--temporal-frames")->c_str()) : 0;
+        const int tp_history = arg("--temporal-history") ? std::atoi(arg("--temporal-history")->c_str()) : 32;
+        const float tp_normal_min = arg("--temporal-normal-min") ? (float)std::atof(arg("--temporal-normal-min")->c_str()) : 0.9f;
+        const float tp_plane_tol = arg("--temporal-plane-tol") ? (float)std::atof(arg("--temporal-plane-tol")->c_str()) : 0.01f;
+        if (temporal) {
+            if (tp_frames < 1 || tp_history < 1 || !(tp_plane_tol >= 0.0f) || tp_normal_min != tp_normal_min)
+                throw Error(RT_E_INVALID, "--temporal-frames and --temporal-history >= 1, --temporal-plane-tol >= 0");
+            if (arg("--spp") && std::atoi(arg("--spp")->c_str()) < 1) throw Error(RT_E_INVALID, "--temporal-frames: --spp >= 1");
+            const auto row = mode_of_shader(find_scene(*name).shader);
+            if (!row || row->family != RT_FAMILY_PATH)
+                throw Error(RT_E_UNSUPPORTED, "--temporal-frames: the scene's mode writes no per-iteration records (a path mode only)");
+        }
         int vote = RT_ADAPT_TILE;
         if (const std::string* v = arg("--adaptive-vote")) {
             if (*v == "pixel") vote = RT_ADAPT_PIXEL;
@@ -301,7 +337,8 @@ int main(int argc, char** argv)
             rs.update();
         }
         // --denoise: the noise estimate from iteration 0 on, unless --noise-target / --adaptive-target enable it
-        if (denoise && !arg("--noise-target") && !arg("--adaptive-target")) rs.enable_noise();
+        // (with --temporal-frames it only carries the filter's parameters: no progressive frame is rendered)
+        if (denoise && !temporal && !arg("--noise-target") && !arg("--adaptive-target")) rs.enable_noise();
         uint32_t frames = 0;
         std::string noise_json;
         if (const std::string* t = arg("--noise-target")) {   // render until converged (render_until)
@@ -348,6 +385,11 @@ int main(int argc, char** argv)
                           (unsigned long long)as.above, (unsigned long long)as.nonfinite,
                           (unsigned long long)as.total_samples, as.min_count, as.max_count, hexf(as.max_rel_err).c_str());
             noise_json = b;
+        } else if (temporal) {   // N frames with the keys held (temporal_step); the progressive frame stays as it is
+            const uint32_t spp = arg("--spp") ? (uint32_t)std::atoi(arg("--spp")->c_str()) : 1;
+            rs.enable_temporal((uint32_t)tp_history, tp_normal_min, tp_plane_tol);
+            for (int i = 0; i < tp_frames; i++) rs.temporal_step(spp);
+            frames = (uint32_t)tp_frames;
         } else if (const std::string* s = arg("--samples")) {   // the progressive loop, SetSamples
             rs.set_samples((uint32_t)std::atoi(s->c_str()), true);
             while (rs.step()) frames++;
@@ -365,7 +407,16 @@ int main(int argc, char** argv)
             write_file(*out + ".accum.f32", f.data(), f.size() * 4);
             write_file(*out + ".ids.u32", ids.data(), ids.size() * 4);
             write_file(*out + ".rgba8", rgba.data(), rgba.size());
-            if (denoise) {
+            if (temporal) {
+                const auto th = rs.temporal_history();
+                const auto tf = rs.temporal_frame(dn_levels, dn_sigma_l, dn_sigma_z);
+                const auto trgba = rs.temporal_rgba8(dn_levels, dn_sigma_l, dn_sigma_z);
+                write_file(*out + ".temporal.f32", th.color.data(), th.color.size() * 4);
+                write_file(*out + ".temporal.len.u32", th.length.data(), th.length.size() * 4);
+                write_file(*out + ".temporal.denoised.f32", tf.data(), tf.size() * 4);
+                write_file(*out + ".temporal.denoised.rgba8", trgba.data(), trgba.size());
+            }
+            if (denoise && !temporal) {
                 const auto df = rs.denoise(dn_levels, dn_sigma_l, dn_sigma_z);
                 const auto drgba = rs.denoised_rgba8(dn_levels, dn_sigma_l, dn_sigma_z);
                 write_file(*out + ".denoised.f32", df.data(), df.size() * 4);

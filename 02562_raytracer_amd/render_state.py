@@ -50,6 +50,7 @@ class RenderState:
         self.noise = None   # enable_noise(): the device buffer of rt_noise_state
         self.counts = None  # enable_adaptive(): the device buffer of per-pixel sample counts
         self.adaptive = None   # its parameters: target, floor, min_samples, vote
+        self.temporal = None   # enable_temporal(): its buffers, parameters and frame counter
         self.setup_rendering(scene)
 
     def _background(self, scene):
@@ -120,6 +121,12 @@ class RenderState:
                 self.enable_noise()
         if adaptive is not None and self.mode in F.NOISE_MODES:
             self.enable_adaptive(**adaptive)   # and so do the sample counts
+        temporal = self.temporal
+        if temporal is not None:
+            # ... and the temporal buffers: a new sequence for a path mode, none otherwise
+            self.disable_temporal()
+            if self.mode in F.NOISE_MODES:
+                self.enable_temporal(min_len=temporal["min_len"], **temporal["params"])
         self.update()
 
     def _load_model(self, model):
@@ -376,6 +383,151 @@ class RenderState:
         img = self.ctx.alloc(npx * 4)
         try:
             self._denoise_into(out, levels, sigma_l, sigma_z)
+            self.ctx.frame_rgba8(out.ptr, npx, img.ptr, mode=self.mode)
+            return img.to_numpy(np.uint8, (self.height, self.width, 4))
+        finally:
+            out.free()
+            img.free()
+
+    # ---- temporal accumulation (include/rt.h "temporal accumulation"; single process, no tiles)
+    def enable_temporal(self, max_history=32, normal_min=0.9, plane_tol=0.01, min_len=4):
+        """Frames that follow a moving camera: temporal_step() renders a frame of its own and
+        blends it with the history reprojected from the previous camera; temporal_frame() filters
+        the result.  Allocates the current frame's accumulation and ids, a guide and two history
+        sets; the progressive accum, ids, iteration, noise and adaptive state are not touched.
+        Reallocated by load_scene."""
+        if self.mode not in F.NOISE_MODES:
+            raise ValueError(f"{self.mode} writes no per-iteration records: temporal accumulation follows "
+                             f"{', '.join(F.NOISE_MODES)}")
+        if int(max_history) < 1 or int(min_len) < 1:
+            raise ValueError("enable_temporal: max_history and min_len must be at least 1")
+        if not float(plane_tol) >= 0.0 or float(normal_min) != float(normal_min):
+            raise ValueError("enable_temporal: plane_tol must be >= 0 and normal_min a number")
+        if getattr(self, "temporal", None) is not None:
+            self.disable_temporal()
+        npx = self.width * self.height
+        bufs = []
+
+        def alloc(nbytes):
+            bufs.append(self.ctx.alloc(nbytes))
+            return bufs[-1]
+        try:
+            sets = [{"color": alloc(npx * 16), "mom": alloc(npx * 8), "len": alloc(npx * 4), "nz": alloc(npx * 16)}
+                    for _ in range(2)]
+            cur, ids, dz = alloc(npx * 16), alloc(npx * 4), alloc(npx * 8)
+        except Exception:
+            for b in bufs:   # a failed allocation leaves the state off, with nothing held
+                b.free()
+            raise
+        self.temporal = {"params": {"max_history": int(max_history), "normal_min": float(normal_min),
+                                    "plane_tol": float(plane_tol)}, "min_len": int(min_len),
+                         "cur": cur, "ids": ids, "dz": dz, "sets": sets, "latest": None, "uniform": None, "k": 0}
+
+    def disable_temporal(self):
+        t, self.temporal = self.temporal, None
+        if t is not None:
+            for b in [t["cur"], t["ids"], t["dz"]] + [b for s in t["sets"] for b in s.values()]:
+                b.free()
+
+    def _temporal_or_raise(self, stepped=False):
+        if self.temporal is None:
+            raise ValueError("temporal accumulation is off: enable_temporal() first")
+        if stepped and self.temporal["latest"] is None:
+            raise ValueError("no temporal frame yet: temporal_step() first")
+        return self.temporal
+
+    def temporal_step(self, spp=1):
+        """One frame of the sequence: spp iterations from the sequence's own counter into a zeroed
+        buffer, its guide, the blend with the reprojected history (rt_temporal_accumulate), then
+        update() -- which moves the camera for the next frame."""
+        t = self._temporal_or_raise()
+        if int(spp) < 1:
+            raise ValueError("temporal_step: spp must be at least 1")
+        w, h, k = self.width, self.height, t["k"]
+        t["cur"].zero()
+        # the frame is not the progressive render's: its noise state and counts stay as they are
+        if self.counts is not None:
+            self.ctx.set_adaptive(None)
+        if self.noise is not None:
+            self.ctx.set_noise_buffer(None)
+        try:
+            self.ctx.render(self.mode, self.trav, (0, 0, w, h), k, spp, t["cur"].ptr, t["ids"].ptr)
+        finally:
+            if self.noise is not None:
+                self.ctx.set_noise_buffer(self.noise.ptr)
+            if self.counts is not None:
+                self.ctx.set_adaptive(self.counts.ptr, **self.adaptive)
+        new = 0 if t["latest"] is None else 1 - t["latest"]
+        out = t["sets"][new]
+        self.ctx.denoise_guide(w, h, t["ids"].ptr, out["nz"].ptr, t["dz"].ptr)   # before update() moves the camera
+        hist = None
+        if t["latest"] is not None:
+            old = t["sets"][t["latest"]]
+            hist = (old["color"].ptr, old["mom"].ptr, old["len"].ptr, old["nz"].ptr)
+        scale = float(np.float32(k + spp) / np.float32(spp))
+        self.ctx.temporal_accumulate(w, h, t["cur"].ptr, scale, out["nz"].ptr, t["uniform"], hist,
+                                     (out["color"].ptr, out["mom"].ptr, out["len"].ptr), **t["params"])
+        t["latest"] = new
+        t["uniform"] = F.Uniform.from_buffer_copy(self.uniform)
+        t["k"] = k + spp
+        self.update()
+
+    def temporal_current(self):
+        """(accumulation float32 [H, W, 4], ids uint32 [H, W], uniform) of the most recent
+        temporal_step's own render, for tests and tools."""
+        t = self._temporal_or_raise(stepped=True)
+        return (t["cur"].to_numpy(np.float32, (self.height, self.width, 4)),
+                t["ids"].to_numpy(np.uint32, (self.height, self.width)), t["uniform"])
+
+    def temporal_history(self):
+        """(colour float32 [H, W, 4], moments float32 [H, W, 2], length uint32 [H, W]) of the latest frame."""
+        t = self._temporal_or_raise(stepped=True)
+        s = t["sets"][t["latest"]]
+        return (s["color"].to_numpy(np.float32, (self.height, self.width, 4)),
+                s["mom"].to_numpy(np.float32, (self.height, self.width, 2)),
+                s["len"].to_numpy(np.uint32, (self.height, self.width)))
+
+    def _temporal_check(self, levels, sigma_l, sigma_z):
+        """(no device: the checks come before any allocation)"""
+        self._temporal_or_raise(stepped=True)
+        if not 1 <= int(levels) <= 5:
+            raise ValueError("temporal_frame: levels must be in 1..5")
+        if not (float(sigma_l) > 0.0 and float(sigma_z) > 0.0):
+            raise ValueError("temporal_frame: the sigmas must be > 0")
+
+    def _temporal_filter_into(self, out, levels, sigma_l, sigma_z):
+        t = self.temporal
+        s = t["sets"][t["latest"]]
+        var = self.ctx.alloc(self.width * self.height * 4)
+        try:
+            self.ctx.temporal_variance(self.width, self.height, s["mom"].ptr, s["len"].ptr, s["nz"].ptr, t["dz"].ptr,
+                                       var.ptr, min_len=t["min_len"], normal_min=t["params"]["normal_min"],
+                                       plane_tol=t["params"]["plane_tol"])
+            self.ctx.denoise_filter(self.width, self.height, s["color"].ptr, var.ptr, s["nz"].ptr, t["dz"].ptr, out.ptr,
+                                    None, levels=levels, sigma_l=sigma_l, sigma_z=sigma_z)
+            self.ctx.synchronize()
+        finally:
+            var.free()
+
+    def temporal_frame(self, levels=5, sigma_l=4.0, sigma_z=1.0):
+        """The latest integrated frame through rt_temporal_variance and rt_denoise_filter:
+        float32 [H, W, 4], alpha 1."""
+        self._temporal_check(levels, sigma_l, sigma_z)
+        out = self.ctx.alloc(self.width * self.height * 16)
+        try:
+            self._temporal_filter_into(out, levels, sigma_l, sigma_z)
+            return out.to_numpy(np.float32, (self.height, self.width, 4))
+        finally:
+            out.free()
+
+    def temporal_rgba8(self, levels=5, sigma_l=4.0, sigma_z=1.0):
+        """temporal_frame() as the sRGB surface would hold it: uint8 [H, W, 4] (rt_frame_rgba8_mode)."""
+        self._temporal_check(levels, sigma_l, sigma_z)
+        npx = self.width * self.height
+        out = self.ctx.alloc(npx * 16)
+        img = self.ctx.alloc(npx * 4)
+        try:
+            self._temporal_filter_into(out, levels, sigma_l, sigma_z)
             self.ctx.frame_rgba8(out.ptr, npx, img.ptr, mode=self.mode)
             return img.to_numpy(np.uint8, (self.height, self.width, 4))
         finally:

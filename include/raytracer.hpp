@@ -241,6 +241,35 @@ public:
     /* ... as the sRGB surface would hold it, H x W x 4 (rt_frame_rgba8_mode of denoise()) */
     std::vector<uint8_t> denoised_rgba8(uint32_t levels = 5, float sigma_l = 4.0f, float sigma_z = 1.0f) const;
 
+    /* Temporal accumulation (rt.h "temporal accumulation"): frames that follow a moving camera.
+     * temporal_step renders spp iterations of the sequence's own counter into a buffer of its
+     * own, makes the guide, blends the frame with the history reprojected from the previous
+     * camera (rt_temporal_accumulate), then update()s -- which moves the camera.  The progressive
+     * accumulation, ids, iteration, noise and adaptive state are not touched; load_scene
+     * reallocates.  Throws for a mode that writes no per-iteration records and on a tiled state
+     * (reprojection needs every pixel's neighbours). */
+    void enable_temporal(uint32_t max_history = 32, float normal_min = 0.9f, float plane_tol = 0.01f,
+                         uint32_t min_len = 4);
+    void disable_temporal();
+    void temporal_step(uint32_t spp = 1);
+    /* the latest integrated frame through rt_temporal_variance and rt_denoise_filter, H x W x 4 */
+    std::vector<float> temporal_frame(uint32_t levels = 5, float sigma_l = 4.0f, float sigma_z = 1.0f) const;
+    std::vector<uint8_t> temporal_rgba8(uint32_t levels = 5, float sigma_l = 4.0f, float sigma_z = 1.0f) const;
+    /* the latest history: colour H x W x 4, luminance moments H x W x 2, length H x W */
+    struct TemporalHistory {
+        std::vector<float> color, moments;
+        std::vector<uint32_t> length;
+    };
+    TemporalHistory temporal_history() const;
+    /* the most recent temporal_step's own render -- its accumulation (the iterations folded into
+     * zero, H x W x 4), its ids and the uniform it used -- for tests and tools */
+    struct TemporalCurrent {
+        std::vector<float> accum;
+        std::vector<uint32_t> ids;
+        rt_uniform uniform;
+    };
+    TemporalCurrent temporal_current() const;
+
     std::vector<float> frame() const;        /* linear RGBA32F accumulation, H x W x 4 */
     std::vector<uint32_t> hit_ids() const;   /* primary-hit triangle ids, H x W */
     /* the sRGB surface frame, H x W x 4 (rt_frame_rgba8_mode: W1E2 and W1E3 without the pow) */
@@ -283,6 +312,19 @@ private:
     float ad_target_ = 0.0f, ad_floor_ = 1e-3f;
     uint32_t ad_min_ = 16;
     int ad_vote_ = RT_ADAPT_TILE;
+    rt_uniform uniform_{};             // what update() last set
+    // enable_temporal: the current frame, the guide's dz and two history sets {colour, moments, length, nz}
+    struct TemporalSet {
+        void *color = nullptr, *mom = nullptr, *len = nullptr, *nz = nullptr;
+    };
+    bool temporal_ = false;
+    void *tp_cur_ = nullptr, *tp_ids_ = nullptr, *tp_dz_ = nullptr;
+    TemporalSet tp_set_[2];
+    int tp_latest_ = -1;               // the set of the latest frame; -1 before the first
+    rt_uniform tp_uniform_{};          // the uniform that frame was rendered with
+    uint32_t tp_k_ = 0, tp_max_history_ = 32, tp_min_len_ = 4;
+    float tp_normal_min_ = 0.9f, tp_plane_tol_ = 0.01f;
+    void* temporal_device(uint32_t levels, float sigma_l, float sigma_z) const;
 };
 
 }  // namespace raytracer

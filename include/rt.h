@@ -316,6 +316,9 @@ typedef struct rt_ray_counts {
 #define RT_OPT_DENOISE_LATTICE_STEP 14 /* the smallest step from which a level runs the lattice form instead (a block per
                                      16 x 16 lattice of stride 2^i, a 20 x 20 LDS tile at every step): 0 (never, the
                                      default: it measured slower), 2, 4, 8 or 16; it takes precedence over the above */
+#define RT_OPT_TEMPORAL_VAR_LDS 15 /* 1 (default) / 0: rt_temporal_variance stages its block's 22 x 22 tile of moments and
+                                     guide in LDS, or loads every neighbour from global memory (the LDS form measured
+                                     2.2 x faster: DESIGN.md section 4 "Temporal accumulation"); the same bits */
 
 /* ---- device / context (replaces src/gpu_handles.rs) -------------------- */
 
@@ -848,6 +851,107 @@ int rt_denoise(rt_ctx* ctx, uint32_t width, uint32_t height, const float* accum_
  * or rt_denoise in milliseconds (level_ms: 5 floats, 0 past its levels) and the form the level
  * ran (lds_form: 5 uint32, or NULL: 0 every tap from global memory, 1 the LDS tile, 2 the lattice).  Synchronizes.  All 0 when the option was off. */
 int rt_denoise_level_times(rt_ctx* ctx, float* level_ms, uint32_t* lds_form);
+
+/* ---- temporal accumulation: reprojected history across camera moves (DESIGN.md section 4
+ * "Temporal accumulation") ----
+ * The temporal half of SVGF for the path modes: the previous frame's integrated colour, the
+ * moments of its luminance and its history length are carried to the new camera by
+ * reprojecting the primary hit, rejected where the new pixel does not see them, and blended
+ * with the new frame; rt_temporal_variance turns the moments into the variance
+ * rt_denoise_filter takes.  No reference counterpart; off unless called.  Pinned f32
+ * arithmetic as "denoise" (no contraction, correctly rounded / and sqrt, every line one
+ * operation, sums left to right, max(a, 0) = (a > 0 ? a : 0), |a| clears the sign bit,
+ * dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; a vector line is that operation per component).
+ *
+ * Frames.  The sample seed is tea16(pixel, iteration), so frame t of a sequence renders the
+ * iterations [k, k + spp), k = t * spp, into a ZEROED accumulation: the progressive fold then
+ * leaves A = (sum of the samples) / (k + spp), and the frame's mean is
+ *     cur = A.rgb * color_scale,   color_scale = (float)(k + spp) / (float)spp   (the host's)
+ * (no noise buffer on such a render: its Welford state would be wrong for first_iter > 0).
+ *     l = (0.2126f*cur.x + 0.7152f*cur.y) + 0.0722f*cur.z;   l2 = l * l
+ *
+ * History of one frame: hist_color float4 {rgb, 1}, hist_mom float2 {m1, m2} (the integrated
+ * luminance and its square), hist_len u32, hist_nz float4 (that frame's {N, z} of
+ * rt_denoise_guide), all row-major width x height, and the rt_uniform it was rendered with.
+ * A camera (e, v, b1, b2, cc, aspect) and its pixel-centre ray w(x, y) are the uniform's, exactly
+ * as "denoise / Guide" pins them; primed names are the previous uniform's.
+ *
+ * rt_temporal_accumulate, pixel p = (x, y) with guide {N_p, z_p}:
+ *   1. NO HISTORY when the history pointers are NULL, !(z_p > 0) (background), or a component
+ *      of cur is not finite.
+ *   2. P = e + w(x, y) * z_p;   d = P - e'
+ *   3. a = dot(d, v');  no history unless a > 0
+ *   4. ux = ((dot(d, b1') * cc') / a) / aspect';   uy = (dot(d, b2') * cc') / a
+ *      fx = (ux + 0.5f) * (float)width - 0.5f;     fy = (0.5f - uy) * (float)height - 0.5f
+ *      no history unless fx > -1.0f && fx < (float)width && fy > -1.0f && fy < (float)height
+ *      (false for a NaN)
+ *   5. x0 = floorf(fx); tx = fx - x0;  y0 = floorf(fy); ty = fy - y0
+ *   6. the four taps q = (x0 + i, y0 + j), j outer, i inner, both 0..1:
+ *          bw = (i ? tx : 1.0f - tx) * (j ? ty : 1.0f - ty)
+ *      A tap is VALID iff it lies inside the frame, bw > 0, len'_q >= 1, z'_q > 0, the three
+ *      components of c'_q and both of m'_q are finite, dot(N_p, N'_q) >= normal_min, and
+ *          P_q = e' + w'(q) * z'_q;   |dot(P_q - P, N_p)| <= plane_tol * z_p
+ *      (the distance of the tap's own surface point from p's tangent plane: it stays correct at
+ *      grazing angles, where a depth ratio does not).
+ *   7. sw = sc = sm = 0, nh = 0xFFFFFFFF; per valid tap, in order:
+ *          sw = sw + bw;  sc = sc + bw * c'_q;  sm = sm + bw * m'_q;  nh = min(nh, len'_q)
+ *      no history unless sw > 0
+ *   8. with history:  h = sc / sw;  hm = sm / sw
+ *          n = nh >= max_history ? max_history : nh + 1;   al = 1.0f / (float)n
+ *          c = h + (cur - h) * al;  m1 = hm.x + (l - hm.x) * al;  m2 = hm.y + (l2 - hm.y) * al
+ *          len = n
+ *   9. without:  c = cur, {m1, m2} = {l, l2}, len = 1.  A cur that is not finite therefore stays
+ *      one pixel: it is copied, its moments are not finite (rt_temporal_variance then gives the
+ *      quiet NaN and the filter treats it as unfilterable), and as a tap it is not valid.
+ *  10. out_color = {c, 1}, out_mom = {m1, m2}, out_len = len.  The caller keeps the current nz
+ *      beside them as the next frame's hist_nz.
+ * STILL CAMERA.  When the previous uniform's eleven camera floats (camera_pos, camera_constant,
+ * camera_look_at, aspect_ratio, camera_up) are bit-equal to the current ones, steps 3 to 5 are
+ * skipped and the only tap is q = p with bw = 1.0f, under the same validity tests: a camera that
+ * stands still gives exactly the running mean above, up to max_history frames.  The host
+ * decides this per call.  The uniforms' resolutions must both be width x height.
+ * Defaults of the hosts: max_history = 32, normal_min = 0.9, plane_tol = 0.01.
+ *
+ * rt_temporal_variance: the variance of the integrated mean luminance, for rt_denoise_filter.
+ * With {m1, m2} = mom[p], len = len[p], the guide {N_p, z_p}, {dzx_p, dzy_p}:
+ *     v = the quiet NaN 0x7FC00000 when m1 or m2 is not finite; else
+ *     (M1, M2) = (m1, m2) when len >= min_len; else the plain mean over the 7 x 7 neighbourhood:
+ *         s1 = s2 = 0, cnt = 0; for dy = -3..3, dx = -3..3 (dy outer), q = p + (dx, dy); the centre
+ *         counts; any other q counts iff it lies inside the frame, both its moments are finite, it
+ *         is of p's class (background iff !(z > 0)), and for a surface pair
+ *             dot(N_p, N_q) >= normal_min  and
+ *             |z_p - z_q| <= 2.0f * |dzx_p * (float)dx + dzy_p * (float)dy| + plane_tol * |z_p|
+ *         s1 = s1 + m1_q;  s2 = s2 + m2_q;  cnt = cnt + 1;    M1 = s1 / (float)cnt;  M2 = s2 / (float)cnt
+ *     v = max(M2 - M1 * M1, 0) / (float)len
+ * A fresh or disoccluded pixel so borrows its neighbours' spread (one sample has none of its
+ * own) and is blurred more.  Default min_len = 4.
+ *
+ * Limits: reprojection follows the primary hit, so what a mirror or glass surface shows (the
+ * W8 and W9E1 balls) lags behind the camera, as in SVGF; background pixels keep no history;
+ * the scene is static.
+ *
+ * Both calls are asynchronous on the context stream, take DEVICE pointers (prev_uniform: host)
+ * and follow rt_denoise_filter's argument rules: RT_E_INVALID for a null context or buffer,
+ * a pointer that is not aligned (16 B float4, 8 B float2, 4 B otherwise), an output that
+ * overlaps an input or another output, width * height >= 2^31, a history of which some
+ * pointers (prev_uniform included) are NULL and others not, max_history == 0, min_len == 0, a
+ * color_scale, normal_min or plane_tol that is NaN, a plane_tol that is negative,
+ * and uniforms (the context's, or prev_uniform) whose resolution is not width x height or whose
+ * aspect ratios differ.  RT_E_NOT_READY without uniforms.  A zero-sized frame is a no-op. */
+int rt_temporal_accumulate(rt_ctx* ctx, uint32_t width, uint32_t height, const float* color_dev, float color_scale,
+                           const float* nz_dev, const rt_uniform* prev_uniform, const float* hist_color_dev,
+                           const float* hist_mom_dev, const uint32_t* hist_len_dev, const float* hist_nz_dev,
+                           uint32_t max_history, float normal_min, float plane_tol, float* out_color_dev,
+                           float* out_mom_dev, uint32_t* out_len_dev);
+
+int rt_temporal_variance(rt_ctx* ctx, uint32_t width, uint32_t height, const float* mom_dev, const uint32_t* len_dev,
+                         const float* nz_dev, const float* dz_dev, uint32_t min_len, float normal_min, float plane_tol,
+                         float* var_dev);
+
+/* With RT_OPT_KERNEL_TIMING: the device time in milliseconds of the most recent
+ * rt_temporal_accumulate and rt_temporal_variance (0 when that call was not timed), and the form
+ * the latter ran (or NULL: 0 every neighbour from global memory, 1 the LDS tile).  Synchronizes. */
+int rt_temporal_times(rt_ctx* ctx, float* accumulate_ms, float* variance_ms, uint32_t* variance_lds_form);
 
 /* ---- multi-GPU: the tile gather over RCCL -----------------
  * One process per GPU, each with its own context: every rank renders its

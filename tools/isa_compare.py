@@ -22,9 +22,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "02562_raytracer_amd"
 # the Makefile's OBJS built from .hip files; those of NO_SLP get -fno-slp-vectorize there
 FILES = ["rt_kernels.hip", "rt_sweep.hip", "rt_analytic.hip", "rt_worksheet1.hip", "rt_noise.hip", "rt_adaptive.hip",
-         "rt_denoise.hip", "rt_empty.hip", "rt_prims.hip", "rt_layout.hip", "rt_build.hip", "rt_bsp_build.hip"]
+         "rt_denoise.hip", "rt_temporal.hip", "rt_empty.hip", "rt_prims.hip", "rt_layout.hip", "rt_build.hip", "rt_bsp_build.hip"]
 NO_SLP = {"rt_kernels.hip", "rt_sweep.hip", "rt_analytic.hip", "rt_worksheet1.hip", "rt_noise.hip", "rt_adaptive.hip",
-          "rt_denoise.hip"}
+          "rt_denoise.hip", "rt_temporal.hip"}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-std=c++17", "-O3", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-Wno-bitwise-instead-of-logical",
