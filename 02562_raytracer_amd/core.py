@@ -9,6 +9,11 @@ import numpy as np
 from . import _ffi as F
 
 
+def _vp(ptr):
+    """A device or host address as a ctypes argument; 0 and None are the null pointer."""
+    return C.c_void_p(ptr) if ptr else None
+
+
 def _mats_from(ptr, n):
     if n == 0:
         return np.zeros((0, 16), dtype=np.float32)
@@ -257,7 +262,7 @@ class Context:
         return F.check(rc, self._h)
 
     def set_stream(self, hip_stream):
-        self._chk(F.lib().rt_set_stream(self._h, C.c_void_p(hip_stream) if hip_stream else None))
+        self._chk(F.lib().rt_set_stream(self._h, _vp(hip_stream)))
 
     def synchronize(self):
         self._chk(F.lib().rt_synchronize(self._h))
@@ -412,7 +417,7 @@ class Context:
         t = F.Tile(*region)
         cnt = F.RayCounts() if counts else None
         self._chk(F.lib().rt_render(self._h, F.MODES.get(mode, mode), F.TRAVERSALS.get(trav, trav), C.byref(t),
-                                    first_iter, spp, C.c_void_p(accum_ptr), C.c_void_p(ids_ptr) if ids_ptr else None,
+                                    first_iter, spp, C.c_void_p(accum_ptr), _vp(ids_ptr),
                                     C.byref(cnt) if counts else None))
         return cnt.asdict() if counts else None
 
@@ -421,20 +426,19 @@ class Context:
         cnt = F.RayCounts() if counts else None
         self._chk(F.lib().rt_render_tiles(self._h, F.MODES.get(mode, mode), F.TRAVERSALS.get(trav, trav),
                                           C.byref(ts), first_iter, spp, C.c_void_p(accum_ptr),
-                                          C.c_void_p(ids_ptr) if ids_ptr else None,
+                                          _vp(ids_ptr),
                                           C.byref(cnt) if counts else None))
         return cnt.asdict() if counts else None
 
     def unpack_tiles(self, width, height, nranks, packed_accum, packed_ids, frame_accum, frame_ids):
-        vpn = (lambda p: C.c_void_p(p) if p else None)
-        self._chk(F.lib().rt_unpack_tiles(self._h, width, height, nranks, vpn(packed_accum), vpn(packed_ids),
-                                          vpn(frame_accum), vpn(frame_ids)))
+        self._chk(F.lib().rt_unpack_tiles(self._h, width, height, nranks, _vp(packed_accum), _vp(packed_ids),
+                                          _vp(frame_accum), _vp(frame_ids)))
 
     # ---- the noise estimate of the path modes (include/rt.h "noise estimate")
     def set_noise_buffer(self, state_ptr=None):
         """rt_set_noise_buffer: the device buffer of rt_noise_state (8 B per output slot,
         indexed as accum) the path modes' renders update; None turns it off."""
-        self._chk(F.lib().rt_set_noise_buffer(self._h, C.c_void_p(state_ptr) if state_ptr else None))
+        self._chk(F.lib().rt_set_noise_buffer(self._h, _vp(state_ptr)))
 
     def noise_accumulate(self, samples_ptr, npix, spp, pixel_major, first_iter, state_ptr):
         """rt_noise_accumulate: device records (float4) [pixel][iteration] (pixel_major) or
@@ -457,7 +461,7 @@ class Context:
     def set_adaptive(self, count_ptr=None, target=0.0, floor=1e-3, min_samples=16, vote="tile"):
         """rt_set_adaptive: the device buffer of per-slot sample counts (uint32, indexed as
         accum) and the rule's parameters; None turns it off."""
-        self._chk(F.lib().rt_set_adaptive(self._h, C.c_void_p(count_ptr) if count_ptr else None, float(target),
+        self._chk(F.lib().rt_set_adaptive(self._h, _vp(count_ptr), float(target),
                                           float(floor), int(min_samples), F.ADAPT_VOTES.get(vote, vote)))
 
     def adaptive_accumulate(self, samples_ptr, npix, spp, pixel_major, first_iter, last_pass, live_ptr, accum_ptr,
@@ -466,7 +470,7 @@ class Context:
         accumulation, id, noise state and count (device pointers; live: one byte per pixel)."""
         self._chk(F.lib().rt_adaptive_accumulate(self._h, C.c_void_p(samples_ptr), npix, spp, int(bool(pixel_major)),
                                                  first_iter, int(bool(last_pass)), C.c_void_p(live_ptr),
-                                                 C.c_void_p(accum_ptr), C.c_void_p(ids_ptr) if ids_ptr else None,
+                                                 C.c_void_p(accum_ptr), _vp(ids_ptr),
                                                  C.c_void_p(state_ptr), C.c_void_p(count_ptr)))
 
     def adaptive_map(self, state_ptr, count_ptr, npix, floor, rel_ptr):
@@ -500,7 +504,7 @@ class Context:
     def denoise_variance(self, state_ptr, count_ptr, npix, n, var_ptr):
         """rt_denoise_variance: the variance of the mean luminance per slot, with the slot's own
         count (count_ptr) or n iterations (count_ptr None)."""
-        self._chk(F.lib().rt_denoise_variance(self._h, C.c_void_p(state_ptr), C.c_void_p(count_ptr) if count_ptr else None,
+        self._chk(F.lib().rt_denoise_variance(self._h, C.c_void_p(state_ptr), _vp(count_ptr),
                                               npix, n, C.c_void_p(var_ptr)))
 
     def denoise_filter(self, width, height, color_ptr, var_ptr, nz_ptr, dz_ptr, out_color_ptr, out_var_ptr=None,
@@ -509,13 +513,13 @@ class Context:
         self._chk(F.lib().rt_denoise_filter(self._h, width, height, C.c_void_p(color_ptr), C.c_void_p(var_ptr),
                                             C.c_void_p(nz_ptr), C.c_void_p(dz_ptr), int(levels), float(sigma_l),
                                             float(sigma_z), C.c_void_p(out_color_ptr),
-                                            C.c_void_p(out_var_ptr) if out_var_ptr else None))
+                                            _vp(out_var_ptr)))
 
     def denoise(self, width, height, accum_ptr, ids_ptr, state_ptr, count_ptr, n, out_ptr, levels=5, sigma_l=4.0,
                 sigma_z=1.0):
         """rt_denoise: guide, variance and filter of a rendered frame on the context's scratch."""
         self._chk(F.lib().rt_denoise(self._h, width, height, C.c_void_p(accum_ptr), C.c_void_p(ids_ptr),
-                                     C.c_void_p(state_ptr), C.c_void_p(count_ptr) if count_ptr else None, int(n),
+                                     C.c_void_p(state_ptr), _vp(count_ptr), int(n),
                                      int(levels), float(sigma_l), float(sigma_z), C.c_void_p(out_ptr)))
 
     def denoise_level_times(self):
@@ -532,20 +536,18 @@ class Context:
         reprojected from prev_uniform's camera.  hist: (color, moments, length, nz) device pointers
         with prev_uniform, or None with None (a first frame); out: (color, moments, length)."""
         h = tuple(hist) if hist is not None else (None,) * 4
-        vpn = (lambda p: C.c_void_p(p) if p else None)
         self._chk(F.lib().rt_temporal_accumulate(
-            self._h, width, height, vpn(color_ptr), float(color_scale), vpn(nz_ptr),
-            C.byref(prev_uniform) if prev_uniform is not None else None, vpn(h[0]), vpn(h[1]), vpn(h[2]), vpn(h[3]),
-            int(max_history), float(normal_min), float(plane_tol), vpn(out[0]), vpn(out[1]), vpn(out[2])))
+            self._h, width, height, _vp(color_ptr), float(color_scale), _vp(nz_ptr),
+            C.byref(prev_uniform) if prev_uniform is not None else None, _vp(h[0]), _vp(h[1]), _vp(h[2]), _vp(h[3]),
+            int(max_history), float(normal_min), float(plane_tol), _vp(out[0]), _vp(out[1]), _vp(out[2])))
 
     def temporal_variance(self, width, height, mom_ptr, len_ptr, nz_ptr, dz_ptr, var_ptr, min_len=4, normal_min=0.9,
                           plane_tol=0.01):
         """rt_temporal_variance: the variance of the integrated mean luminance; a pixel with fewer
         than min_len frames takes its 7 x 7 neighbours' moments."""
-        vpn = (lambda p: C.c_void_p(p) if p else None)
-        self._chk(F.lib().rt_temporal_variance(self._h, width, height, vpn(mom_ptr), vpn(len_ptr), vpn(nz_ptr),
-                                               vpn(dz_ptr), int(min_len), float(normal_min), float(plane_tol),
-                                               vpn(var_ptr)))
+        self._chk(F.lib().rt_temporal_variance(self._h, width, height, _vp(mom_ptr), _vp(len_ptr), _vp(nz_ptr),
+                                               _vp(dz_ptr), int(min_len), float(normal_min), float(plane_tol),
+                                               _vp(var_ptr)))
 
     def temporal_times(self):
         """rt_temporal_times: (accumulate ms, variance ms, variance form: 0 direct, 1 LDS tile) of the
@@ -572,9 +574,8 @@ class Context:
 
     def gather_tiles(self, width, height, local_accum, local_ids, frame_accum=None, frame_ids=None):
         """rt_gather_tiles: every rank's packed tiles to rank 0's frame (device pointers)."""
-        vpn = (lambda p: C.c_void_p(p) if p else None)
-        self._chk(F.lib().rt_gather_tiles(self._h, width, height, vpn(local_accum), vpn(local_ids), vpn(frame_accum),
-                                          vpn(frame_ids)))
+        self._chk(F.lib().rt_gather_tiles(self._h, width, height, _vp(local_accum), _vp(local_ids), _vp(frame_accum),
+                                          _vp(frame_ids)))
 
     def trace_rays(self, trav, rays, anyhit=None):
         """rt_trace_rays on host arrays: rays float32[n, 8] (origin, direction,
@@ -675,12 +676,12 @@ class Context:
         """rt_trace_batch: the traversal-only kernel over n device rays (8 f32 each;
         flags bit 0 any-hit, or None) into n x {record offset | 0xFFFFFFFE | ~0, dist}."""
         self._chk(F.lib().rt_trace_batch(self._h, F.TRAVERSALS.get(trav, trav), C.c_void_p(rays_ptr),
-                                          C.c_void_p(flags_ptr) if flags_ptr else None, n, C.c_void_p(hits_ptr)))
+                                          _vp(flags_ptr), n, C.c_void_p(hits_ptr)))
 
     def set_ray_capture(self, rays_ptr=None, flags_ptr=None, cap=0):
         """Arm (device buffers of cap rays) or disarm (None) the counting renders' ray capture."""
-        self._chk(F.lib().rt_set_ray_capture(self._h, C.c_void_p(rays_ptr) if rays_ptr else None,
-                                              C.c_void_p(flags_ptr) if flags_ptr else None, cap))
+        self._chk(F.lib().rt_set_ray_capture(self._h, _vp(rays_ptr),
+                                              _vp(flags_ptr), cap))
 
     def ray_capture_count(self):
         n = C.c_uint64()

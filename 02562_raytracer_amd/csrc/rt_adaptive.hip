@@ -7,24 +7,19 @@
 // (tests/test_isa_guard.py).
 //
 // The arithmetic is pinned (f32, no contraction, correctly rounded / and sqrt; the
-// Makefile's NUMFLAGS) and restates k_fold's average (rt_stream_kernels.h) and k_noise's update
-// and relative error (rt_noise.hip) operation for operation: a slot that took part in n
-// iterations holds the bits a uniform n-iteration render gives it.  tests/adaptive_ref.py
-// restates the rule in numpy.
+// Makefile's NUMFLAGS); the fused fold runs k_fold's and k_noise's own per-record updates
+// (rt_frame_common.h), so a slot that took part in n iterations holds the bits a uniform
+// n-iteration render gives it.  tests/adaptive_ref.py restates the rule in numpy.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rt_device_common.h"
+#include "rt_frame_common.h"
 #include "rt_prims.h"
 
 namespace rtk {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-
 namespace {
 
-// (finitef and noise_rel: rt_device_common.h, shared with rt_noise.hip)
 // rt.h: does a valid slot with this state and count want more at a call's first_iter > 0?
 __device__ __forceinline__ bool wants_more(const v2f s, uint32_t cnt, uint32_t first, const AdaptParams& P)
 {
@@ -129,10 +124,9 @@ __global__ void __launch_bounds__(256) k_adaptive_live(DevLaunch L, const uint32
 
 // ------------------------------------------------------------------ the fused fold
 // k_fold's progressive average and k_noise's Welford update over one read of the pass's
-// records, for the live output slots alone; every other slot keeps its accumulation, id,
-// state and count.  One thread per output slot, k_fold's addressing: [pixel][iteration]
-// records eight (one 128-B line) at a time with a scalar tail, [iteration][pixel]
-// records streamed.  last != 0 (the call's last pass): count = the iterations folded.
+// records (walk_records with both steps), for the live output slots alone; every other slot
+// keeps its accumulation, id, state and count.  One thread per output slot.  last != 0 (the
+// call's last pass): count = the iterations folded.
 __global__ void __launch_bounds__(256) k_adaptive_fold(DevLaunch L, const uint32_t* empty_mask,
                                                        const uint8_t* __restrict__ live,
                                                        rt_noise_state* __restrict__ state, uint32_t* __restrict__ count,
@@ -157,42 +151,10 @@ __global__ void __launch_bounds__(256) k_adaptive_fold(DevLaunch L, const uint32
             mean = s.x;
             m2 = s.y;
         }
-        v4f r = {0.0f, 0.0f, 0.0f, 0.0f};
-        auto step = [&](const v4f x, uint32_t i) {
-            const uint32_t it = L.first_iter + i;
-            // k_fold's fold1
-            const float fi = (float)it, fi1 = (float)(it + 1u);
-            a0 = rt_max0f((x.x + a0 * fi) / fi1);
-            a1 = rt_max0f((x.y + a1 * fi) / fi1);
-            a2 = rt_max0f((x.z + a2 * fi) / fi1);
-            // k_noise's noise1
-            const float y = (0.2126f * x.x + 0.7152f * x.y) + 0.0722f * x.z;
-            const float n = (float)(it + 1u);
-            const float d = y - mean;
-            mean = mean + d / n;
-            m2 = m2 + d * (y - mean);
-        };
-        uint32_t i = 0;
-        if (L.unit_order) {
-            const v4f* sp = reinterpret_cast<const v4f*>(L.samples + (size_t)o * L.spp);
-            for (; i + 8u <= L.spp; i += 8u) {
-                v4f q[8];
-                path_records(fl, cst, sp + i, q);
-#pragma unroll
-                for (int k = 0; k < 8; k++) step(q[k], i + k);
-                r = q[7];
-            }
-            for (; i < L.spp; i++) {
-                r = path_record(fl, cst, sp + i);
-                step(r, i);
-            }
-        } else {
-            const v4f* sp = reinterpret_cast<const v4f*>(L.samples + o);
-            for (; i < L.spp; i++) {
-                r = path_record<true>(fl, cst, sp + (size_t)i * L.stride);
-                step(r, i);
-            }
-        }
+        const v4f r = walk_records(L, o, fl, cst, [&](const v4f x, uint32_t i) {
+            fold1(a0, a1, a2, x, L.first_iter + i);
+            welford1(mean, m2, x, L.first_iter + i);
+        });
         L.accum[o] = make_float4(a0, a1, a2, 1.0f);
         if (L.ids && L.spp) L.ids[o] = __float_as_uint(r.w);
         const v2f s = {mean, m2};
@@ -210,8 +172,8 @@ __global__ void __launch_bounds__(256) k_adaptive_map(const rt_noise_state* __re
         const v2f s = *reinterpret_cast<const v2f*>(state + o);
         const uint32_t n = count[o];
         const float nf = (float)n;
-        rel[o] = n >= 2u && finitef(s.x) && finitef(s.y) ? __float_as_uint(noise_rel(s.x, s.y, nf * (nf - 1.0f), floor))
-                                                         : 0x7FC00000u;
+        rel[o] = __float_as_uint(n >= 2u && finitef(s.x) && finitef(s.y) ? noise_rel(s.x, s.y, nf * (nf - 1.0f), floor)
+                                                                         : qnanf());
     }
 }
 
@@ -230,7 +192,7 @@ int build_adaptive_list(const DevLaunch& l, const uint32_t* empty_mask, const rt
     if (hipMemsetAsync(live, 0, nout, stream) != hipSuccess) return RT_E_DEVICE;
     hipLaunchKernelGGL(k_adaptive_live<false>, dim3(stream_blocks(nslots, 512)), dim3(256), 0, stream, l, empty_mask, state,
                        count, p, live, flags, stats);
-    if (hipGetLastError() != hipSuccess) return RT_E_DEVICE;
+    if (int r = launch_status()) return r;
     uint32_t nlist = 0;
     unsigned long long st[2] = {0, 0};
     if (int r = compact_flagged(flags, offs, nslots, scan, list, &nlist, stream)) return r;
@@ -248,7 +210,7 @@ int launch_adaptive_fold(const DevLaunch& l, const uint32_t* empty_mask, const u
     const uint64_t nout = l.tileset ? (uint64_t)l.nwork * 64u : (uint64_t)l.w * l.h;
     hipLaunchKernelGGL(k_adaptive_fold, dim3(stream_blocks(nout, 16384)), dim3(256), 0, stream, l, empty_mask, live, state,
                        count, last_pass ? 1u : 0u);
-    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
+    return launch_status();
 }
 
 int launch_adaptive_map(const rt_noise_state* state, const uint32_t* count, uint32_t npix, float floor, float* rel,
@@ -256,7 +218,7 @@ int launch_adaptive_map(const rt_noise_state* state, const uint32_t* count, uint
 {
     hipLaunchKernelGGL(k_adaptive_map, dim3(stream_blocks(npix, 2048)), dim3(256), 0, stream, state, count, npix, floor,
                        reinterpret_cast<uint32_t*>(rel));
-    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
+    return launch_status();
 }
 
 int launch_adaptive_summary(const DevLaunch& l, const rt_noise_state* state, const uint32_t* count,
@@ -266,7 +228,7 @@ int launch_adaptive_summary(const DevLaunch& l, const rt_noise_state* state, con
     if (nslots == 0) return 0;
     hipLaunchKernelGGL(k_adaptive_live<true>, dim3(stream_blocks(nslots, 512)), dim3(256), 0, stream, l, nullptr, state, count,
                        p, (uint8_t*)nullptr, (uint32_t*)nullptr, stats);
-    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
+    return launch_status();
 }
 
 }  // namespace rtk

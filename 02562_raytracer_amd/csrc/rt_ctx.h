@@ -1,7 +1,8 @@
 // rt_ctx.h -- the context behind the C ABI (include/rt.h) and what the files that
 // implement it share: rt_context.cpp, rt_scene.cpp, rt_render.cpp, rt_estimate.cpp,
 // rt_denoise_api.cpp, rt_temporal_api.cpp and rt_gather.cpp (and rt_modes.cpp's table); rt_build.hip takes Event
-// from here.  Not part of the public ABI.
+// from here.  The argument checks of the post-process entry points are rt_args.h's (plain host
+// code); refuse() below gives them the context's error.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +15,7 @@
 #include <vector>
 
 #include "host_types.h"
+#include "rt_args.h"
 #include "rt_internal.h"
 #include "rt_own.h"
 #include "rt_prims.h"
@@ -311,6 +313,12 @@ int fail(rt_ctx* c, int code, const std::string& msg);
                         std::string(#expr ": ") + hipGetErrorString(e_));                          \
     } while (0)
 
+// an argument check of rt_args.h as `who`'s status: RT_OK for no reason to refuse
+inline int refuse(rt_ctx* c, const char* who, const std::string& why)
+{
+    return why.empty() ? RT_OK : fail(c, RT_E_INVALID, std::string(who) + ": " + why);
+}
+
 int upload(rt_ctx* c, DevBuf& b, const void* src, size_t bytes);
 // bytes from the device into host memory on the context stream, and the stream synchronised
 int read_back(rt_ctx* c, void* host, const void* dev, size_t bytes);
@@ -389,5 +397,26 @@ int launch_timed(rt_ctx* c, const char* what, Launch&& launch)
         HIPCHK(c, hipEventRecord(ev[ev.used + 1], c->stream));
         ev.used += 2;
     }
+    return RT_OK;
+}
+
+// The same around launch() -- any rt status -- with two events of the subsystem's own, which
+// keep the time of its most recent call (rt_denoise_level_times, rt_temporal_times).  before
+// is null where the previous launch's `after` already marks the start (a chain of launches
+// timed one by one).  The caller notes that the events were recorded: kernel timing was on and
+// the status is RT_OK.
+template <class Launch>
+int timed(rt_ctx* c, Event* before, Event& after, Launch&& launch)
+{
+    const bool t = c->ktime.on;
+    if (t) {
+        HIPCHK(c, after.ensure());
+        if (before) {
+            HIPCHK(c, before->ensure());
+            HIPCHK(c, hipEventRecord(*before, c->stream));
+        }
+    }
+    if (const int r = launch()) return r;
+    if (t) HIPCHK(c, hipEventRecord(after, c->stream));
     return RT_OK;
 }

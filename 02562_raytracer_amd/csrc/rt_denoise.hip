@@ -11,40 +11,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rt_device_common.h"
+#include "rt_frame_common.h"
 
 namespace rtk {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool dn_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-__device__ __forceinline__ float dn_abs(float x) { return __uint_as_float(__float_as_uint(x) & 0x7FFFFFFFu); }
-__device__ __forceinline__ float dn_qnan() { return __uint_as_float(0x7FC00000u); }
-
 // ------------------------------------------------------------------ guide
-// the pixel-centre ray of (x, y): pixel_uv and cam_dir with zero jitter; (x, y) may lie
-// one past the frame (the neighbour of the last column / row)
-__device__ __forceinline__ f3 centre_dir(const Cam& c, uint32_t W, uint32_t H, uint32_t x, uint32_t y)
-{
-    const float ux = ((float)x + 0.5f) / (float)W - 0.5f;
-    const float uy = 0.5f - ((float)y + 0.5f) / (float)H;
-    return cam_dir(c, ux, uy, 0.0f, 0.0f);
-}
-
+// (the pixel-centre ray: rt_frame_common.h centre_dir, temporal accumulation's too)
 __global__ void __launch_bounds__(256) k_denoise_guide(DenoiseCam G, const float4* __restrict__ pos,
                                                        const uint4* __restrict__ tri_idx, uint32_t ntris,
                                                        const uint32_t* __restrict__ ids, v4f* __restrict__ nz,
                                                        v2f* __restrict__ dz)
 {
     const uint32_t npix = G.w * G.h;
-    Cam c;
-    c.e = ld3(G.cam + 0);
-    c.v = ld3(G.cam + 3);
-    c.b1 = ld3(G.cam + 6);
-    c.b2 = ld3(G.cam + 9);
-    c.d = G.cam[12];
-    c.aspect = G.cam[13];
+    const Cam c = cam_from(G.cam);
     for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < npix; o += gridDim.x * blockDim.x) {
         const uint32_t y = o / G.w, x = o - y * G.w;
         const uint32_t id = ids[o];
@@ -61,13 +40,13 @@ __global__ void __launch_bounds__(256) k_denoise_guide(DenoiseCam G, const float
             const float den = dot(w, g);
             const float num = dot(sub(v0, c.e), g);
             const float z = num / den;
-            if (den != 0.0f && dn_finite(z) && z > 0.0f) {
+            if (den != 0.0f && finitef(z) && z > 0.0f) {
                 const float zx = num / dot(centre_dir(c, G.w, G.h, x + 1u, y), g);
                 const float zy = num / dot(centre_dir(c, G.w, G.h, x, y + 1u), g);
                 const float dzx = zx - z;
                 const float dzy = zy - z;
                 onz = v4f{g.x, g.y, g.z, z};
-                odz = v2f{dn_finite(dzx) ? dzx : 0.0f, dn_finite(dzy) ? dzy : 0.0f};
+                odz = v2f{finitef(dzx) ? dzx : 0.0f, finitef(dzy) ? dzy : 0.0f};
             }
         }
         nz[o] = onz;
@@ -85,8 +64,8 @@ __global__ void __launch_bounds__(256) k_denoise_variance(const rt_noise_state* 
         const uint32_t cnt = count ? count[o] : n;
         const float nf = (float)cnt;
         const float denom = nf * (nf - 1.0f);
-        const float v = (s.y < 0.0f ? 0.0f : s.y) / denom;
-        var[o] = cnt >= 2u && dn_finite(s.x) && dn_finite(s.y) ? v : dn_qnan();
+        const float v = var_of_mean(s.y, denom);
+        var[o] = cnt >= 2u && finitef(s.x) && finitef(s.y) ? v : qnanf();
     }
 }
 
@@ -104,9 +83,8 @@ __global__ void __launch_bounds__(256) k_denoise_pack(const v4f* __restrict__ co
 // finite colour and a finite variance that is not negative
 __device__ __forceinline__ bool dn_filterable(const v4f q)
 {
-    return dn_finite(q.x) && dn_finite(q.y) && dn_finite(q.z) && dn_finite(q.w) && !(q.w < 0.0f);
+    return finitef(q.x) && finitef(q.y) && finitef(q.z) && finitef(q.w) && !(q.w < 0.0f);
 }
-__device__ __forceinline__ float dn_lum(const v4f q) { return (0.2126f * q.x + 0.7152f * q.y) + 0.0722f * q.z; }
 
 // The filter of one filterable centre (pc, pn, pdz) at (x, y).  fetch_sd(qx, qy, cv) gives a
 // tap of the 3x3 neighbourhood at step 1, fetch(dx, dy, cv, nz) the tap at (x + s dx, y + s dy); both return
@@ -133,8 +111,8 @@ __device__ __forceinline__ v4f denoise_pixel(FetchSd fetch_sd, Fetch fetch, int 
     }
     const float sd = rt_det_sqrtf(sv / sk);
     const float lden = sigma_l * sd + 1e-6f;
-    const float zfloor = 1e-3f * dn_abs(pn.w);
-    const float lp = dn_lum(pc);
+    const float zfloor = 1e-3f * rt_absf(pn.w);
+    const float lp = lum709(pc.x, pc.y, pc.z);
     const bool pbg = !(pn.w > 0.0f);
     // 2. the 25 taps, dy outer, dx inner
     const float h[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
@@ -166,10 +144,10 @@ __device__ __forceinline__ v4f denoise_pixel(FetchSd fetch_sd, Fetch fetch, int 
                     wn = wn * wn;
                     wn = wn * wn;
                     const float gr = pdz.x * (float)(s * dx) + pdz.y * (float)(s * dy);
-                    const float zden = sigma_z * dn_abs(gr) + zfloor;
-                    xz = dn_abs(pn.w - qn.w) / zden;
+                    const float zden = sigma_z * rt_absf(gr) + zfloor;
+                    xz = rt_absf(pn.w - qn.w) / zden;
                 }
-                const float xl = dn_abs(lp - dn_lum(q)) / lden;
+                const float xl = rt_absf(lp - lum709(q.x, q.y, q.z)) / lden;
                 const float xx = xz + xl;
                 float t = 1.0f - xx * 0.125f;
                 t = t > 0.0f ? t : 0.0f;
@@ -210,6 +188,22 @@ __device__ __forceinline__ void level_store(const LevelArgs& A, uint32_t o, cons
     }
 }
 
+// the {rgb, v} and {N, z} tiles of the two staged forms; an entry outside the frame holds v = NaN
+// (unfilterable: weight 0, as the frame test gives) and z = -1
+__device__ __forceinline__ void stage_level_tile(const LevelArgs& A, v4f* tcv, v4f* tnz, int T, int bx, int by, int stride)
+{
+    stage_tile(T, bx, by, stride, A.w, A.h, [&](int i, bool in, uint32_t g) {
+        v4f q = {0.0f, 0.0f, 0.0f, qnanf()};
+        v4f qn = {0.0f, 0.0f, 0.0f, -1.0f};
+        if (in) {
+            q = A.cv[g];
+            qn = A.nz[g];
+        }
+        tcv[i] = q;
+        tnz[i] = qn;
+    });
+}
+
 // Direct form: every tap is two 16-B loads from global memory (the caches hold the
 // neighbourhood; at the large steps the taps of a block are 25 separate 16 x 16 patches).
 __global__ void __launch_bounds__(256) k_denoise_level(LevelArgs A)
@@ -242,8 +236,7 @@ __global__ void __launch_bounds__(256) k_denoise_level(LevelArgs A)
 }
 
 // LDS form: the block's 16 x 16 tile and its halo of 2 s, (16 + 4 s)^2 entries of 32 B, staged
-// once; an entry outside the frame holds v = NaN (unfilterable: weight 0, as the frame test
-// gives).  Dynamic LDS: 12.8 / 18 / 32 / 73 KiB for s = 1, 2, 4, 8.
+// once (stage_level_tile).  Dynamic LDS: 12.8 / 18 / 32 / 73 KiB for s = 1, 2, 4, 8.
 __global__ void __launch_bounds__(256) k_denoise_level_lds(LevelArgs A)
 {
     extern __shared__ v4f dn_tile[];
@@ -252,19 +245,7 @@ __global__ void __launch_bounds__(256) k_denoise_level_lds(LevelArgs A)
     v4f* const tcv = dn_tile;
     v4f* const tnz = dn_tile + T * T;
     const int bx = (int)(blockIdx.x * 16u) - 2 * s, by = (int)(blockIdx.y * 16u) - 2 * s;
-    for (int i = (int)threadIdx.x; i < T * T; i += 256) {
-        const int ty = i / T, tx = i - ty * T;
-        const int qx = bx + tx, qy = by + ty;
-        v4f q = {0.0f, 0.0f, 0.0f, dn_qnan()};
-        v4f qn = {0.0f, 0.0f, 0.0f, -1.0f};
-        if (qx >= 0 && qy >= 0 && qx < A.w && qy < A.h) {
-            const uint32_t g = (uint32_t)qy * (uint32_t)A.w + (uint32_t)qx;
-            q = A.cv[g];
-            qn = A.nz[g];
-        }
-        tcv[i] = q;
-        tnz[i] = qn;
-    }
+    stage_level_tile(A, tcv, tnz, T, bx, by, 1);
     __syncthreads();
     const int x = (int)(blockIdx.x * 16u + (threadIdx.x & 15u));
     const int y = (int)(blockIdx.y * 16u + (threadIdx.x >> 4));
@@ -305,19 +286,7 @@ __global__ void __launch_bounds__(256) k_denoise_level_lattice(LevelArgs A)
     const int sx = (int)blockIdx.x / s, px = (int)blockIdx.x - sx * s;
     const int sy = (int)blockIdx.y / s, py = (int)blockIdx.y - sy * s;
     const int bx = sx * 16 * s + px - 2 * s, by = sy * 16 * s + py - 2 * s;   // lattice point (0, 0) of the tile
-    for (int i = (int)threadIdx.x; i < 400; i += 256) {
-        const int ty = i / 20, tx = i - ty * 20;
-        const int qx = bx + s * tx, qy = by + s * ty;
-        v4f q = {0.0f, 0.0f, 0.0f, dn_qnan()};
-        v4f qn = {0.0f, 0.0f, 0.0f, -1.0f};
-        if (qx >= 0 && qy >= 0 && qx < A.w && qy < A.h) {
-            const uint32_t g = (uint32_t)qy * (uint32_t)A.w + (uint32_t)qx;
-            q = A.cv[g];
-            qn = A.nz[g];
-        }
-        tcv[i] = q;
-        tnz[i] = qn;
-    }
+    stage_level_tile(A, tcv, tnz, 20, bx, by, s);
     __syncthreads();
     const int lx = (int)(threadIdx.x & 15u) + 2, ly = (int)(threadIdx.x >> 4) + 2;
     const int x = bx + s * lx, y = by + s * ly;
@@ -346,14 +315,12 @@ __global__ void __launch_bounds__(256) k_denoise_level_lattice(LevelArgs A)
 }
 
 // ------------------------------------------------------------------ launchers
-static int dn_ok() { return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE; }
-
 int launch_denoise_guide(const DenoiseCam& g, const float4* pos, const uint4* tri_idx, uint32_t ntris,
                          const uint32_t* ids, float* nz, float* dz, hipStream_t stream)
 {
     hipLaunchKernelGGL(k_denoise_guide, dim3(stream_blocks((uint64_t)g.w * g.h, 4096)), dim3(256), 0, stream, g, pos,
                        tri_idx, ntris, ids, reinterpret_cast<v4f*>(nz), reinterpret_cast<v2f*>(dz));
-    return dn_ok();
+    return launch_status();
 }
 
 int launch_denoise_variance(const rt_noise_state* state, const uint32_t* count, uint32_t npix, uint32_t n, float* var,
@@ -361,14 +328,14 @@ int launch_denoise_variance(const rt_noise_state* state, const uint32_t* count, 
 {
     hipLaunchKernelGGL(k_denoise_variance, dim3(stream_blocks(npix, 4096)), dim3(256), 0, stream, state, count, npix, n,
                        var);
-    return dn_ok();
+    return launch_status();
 }
 
 int launch_denoise_pack(const float* color, const float* var, uint32_t npix, float* cv, hipStream_t stream)
 {
     hipLaunchKernelGGL(k_denoise_pack, dim3(stream_blocks(npix, 4096)), dim3(256), 0, stream,
                        reinterpret_cast<const v4f*>(color), var, npix, reinterpret_cast<v4f*>(cv));
-    return dn_ok();
+    return launch_status();
 }
 
 size_t denoise_lds_bytes(uint32_t step)
@@ -414,7 +381,7 @@ int launch_denoise_level(const float* cv, const float* nz, const float* dz, uint
     } else {
         hipLaunchKernelGGL(k_denoise_level, grid, dim3(256), 0, stream, A);
     }
-    return dn_ok();
+    return launch_status();
 }
 
 }  // namespace rtk

@@ -1,6 +1,6 @@
 // rt_device_common.h -- device helpers shared by the kernel translation units
-// (rt_kernels.hip and its headers, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip, rt_noise.hip,
-// rt_adaptive.hip): the f32 vector
+// (rt_kernels.hip and its headers, rt_sweep.hip, rt_analytic.hip, rt_worksheet1.hip, and through
+// rt_frame_common.h the post-process units): the f32 vector
 // math of the WGSL builtins, the per-launch counters and the wave sum, the camera ray
 // of get_camera_ray and the work mapping of one 8x8 tile per wave.  Not part of the
 // public ABI.
@@ -83,17 +83,18 @@ struct Cam {
 // The basis v = normalize(p - e), b1 = normalize(cross(v, u)), b2 = cross(b1, v)
 // is loop-invariant: rt_api.cpp evaluates it once on the host with the same
 // IEEE operations (no contraction) and passes it as kernel arguments (SGPRs).
-__device__ __forceinline__ Cam make_cam(const DevLaunch& L)
+__device__ __forceinline__ Cam cam_from(const float* cam)   // camera_basis's 14 floats
 {
     Cam c;
-    c.e = ld3(L.cam + 0);
-    c.v = ld3(L.cam + 3);
-    c.b1 = ld3(L.cam + 6);
-    c.b2 = ld3(L.cam + 9);
-    c.d = L.cam[12];
-    c.aspect = L.cam[13];
+    c.e = ld3(cam + 0);
+    c.v = ld3(cam + 3);
+    c.b1 = ld3(cam + 6);
+    c.b2 = ld3(cam + 9);
+    c.d = cam[12];
+    c.aspect = cam[13];
     return c;
 }
+__device__ __forceinline__ Cam make_cam(const DevLaunch& L) { return cam_from(L.cam); }
 // Kernel arguments made opaque where a sample starts or a lane is refilled:
 // the values derived from them (the camera products, float resolutions,
 // integer-division reciprocals) are then recomputed there from SGPRs instead
@@ -156,8 +157,8 @@ __device__ __forceinline__ uint32_t fetch_work(uint32_t* ctr, uint32_t lane)
 }
 // ------------------------------------------------------------------ records of flagged pixels
 // RT_OPT_EMPTY_PIXELS: k_path writes no record for a pixel whose bit is set in
-// the launch's empty mask (no camera ray of it can hit the mesh, rt_empty.h).  k_fold and k_noise
-// read every record through path_record: the stored one, or for a flagged pixel what
+// the launch's empty mask (no camera ray of it can hit the mesh, rt_empty.h).  The record walk
+// (rt_frame_common.h walk_records) reads every record through path_record: the stored one, or for a flagged pixel what
 // each of its iterations would have stored -- W9E1's miss with the constant
 // environment, result = vec3(0) + env * factor with factor = vec3(1), primary id none.
 typedef float rec4 __attribute__((ext_vector_type(4)));
@@ -200,23 +201,16 @@ __device__ __forceinline__ rec4 path_record(bool flagged, const rec4 cst, const 
     return STREAM ? __builtin_nontemporal_load(p) : *p;
 }
 
-// ------------------------------------------------------------------ noise estimate
-// (k_noise_map / k_noise_summary, rt_noise.hip; the live rule and the count-aware map, rt_adaptive.hip)
-__device__ __forceinline__ bool finitef(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-
-// the relative standard error of the mean of a finite state after n >= 2 iterations
-// (denom = nf * (nf - 1)); never NaN: m2 is clamped, denom and the floor are positive
-__device__ __forceinline__ float noise_rel(float mean, float m2, float denom, float floor)
+// ------------------------------------------------------------------ pixel centre
+// the centre of pixel (x, y) of a W x H frame on the image plane, before the jitter
+__device__ __forceinline__ void pixel_uv(uint32_t W, uint32_t H, uint32_t x, uint32_t y, float& ux, float& uy)
 {
-    const float var = (m2 < 0.0f ? 0.0f : m2) / denom;
-    const float a = rt_absf(mean);
-    return rt_det_sqrtf(var) / (a < floor ? floor : a);
+    ux = ((float)x + 0.5f) / (float)W - 0.5f;
+    uy = 0.5f - ((float)y + 0.5f) / (float)H;
 }
-
 __device__ __forceinline__ void pixel_uv(const rt_uniform& u, uint32_t x, uint32_t y, float& ux, float& uy)
 {
-    ux = ((float)x + 0.5f) / (float)u.resolution[0] - 0.5f;
-    uy = 0.5f - ((float)y + 0.5f) / (float)u.resolution[1];
+    pixel_uv(u.resolution[0], u.resolution[1], x, y, ux, uy);
 }
 
 }  // namespace rtk

@@ -4,25 +4,6 @@
 
 namespace {
 
-int noise_args(rt_ctx* c, const char* who, const void* state, uint32_t npix, uint32_t n, float floor)
-{
-    if (n < 2) return fail(c, RT_E_INVALID, std::string(who) + ": the standard error needs n >= 2 iterations");
-    if (!(floor > 0.0f)) return fail(c, RT_E_INVALID, std::string(who) + ": floor must be > 0");
-    if (!state && npix) return fail(c, RT_E_INVALID, std::string(who) + ": null state");
-    if ((uintptr_t)state % 8) return fail(c, RT_E_INVALID, std::string(who) + ": the state must be 8-byte aligned");
-    return RT_OK;
-}
-
-int adaptive_args(rt_ctx* c, const char* who, float target, float floor, uint32_t min_samples, int vote)
-{
-    if (min_samples < 2) return fail(c, RT_E_INVALID, std::string(who) + ": min_samples must be >= 2");
-    if (!(target >= 0.0f)) return fail(c, RT_E_INVALID, std::string(who) + ": target must be >= 0 and not NaN");
-    if (!(floor > 0.0f)) return fail(c, RT_E_INVALID, std::string(who) + ": floor must be > 0");
-    if (vote != RT_ADAPT_PIXEL && vote != RT_ADAPT_TILE)
-        return fail(c, RT_E_INVALID, std::string(who) + ": vote must be RT_ADAPT_PIXEL or RT_ADAPT_TILE");
-    return RT_OK;
-}
-
 // k_noise's and the adaptive fold's view of caller-owned records: a region of npix x 1
 // pixels, one pass
 rtk::DevLaunch records_launch(const float* samples, uint32_t npix, uint32_t spp, int pixel_major, uint32_t first_iter)
@@ -53,38 +34,45 @@ int rt_set_noise_buffer(rt_ctx* c, rt_noise_state* state_dev)
 int rt_noise_accumulate(rt_ctx* c, const float* samples, uint32_t npix, uint32_t spp, int pixel_major,
                         uint32_t first_iter, rt_noise_state* state)
 {
-    if (!c) return fail(nullptr, RT_E_INVALID, "rt_noise_accumulate: null context");
+    const char* const who = "rt_noise_accumulate";
+    if (!c) return fail(nullptr, RT_E_INVALID, std::string(who) + ": null context");
     if (npix == 0 || spp == 0) return RT_OK;
-    if (!samples || !state) return fail(c, RT_E_INVALID, "rt_noise_accumulate: null buffer");
-    if ((uintptr_t)samples % 16 || (uintptr_t)state % 8)
-        return fail(c, RT_E_INVALID, "rt_noise_accumulate: the records must be 16-byte and the state 8-byte aligned");
+    const BufRange rg[] = {{samples, (uint64_t)npix * spp * 16, 16, false, false, "samples"},
+                           {state, (uint64_t)npix * 8, 8, true, false, "state"}};
+    if (int r = refuse(c, who, placement_fault(rg))) return r;
     if (int r = set_dev(c)) return r;
     const rtk::DevLaunch L = records_launch(samples, npix, spp, pixel_major, first_iter);
     if (rtk::launch_noise(L, nullptr, state, c->stream))
-        return fail(c, RT_E_DEVICE, std::string("rt_noise_accumulate: launch failed: ") +
-                                        hipGetErrorString(hipGetLastError()));
+        return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed: " + hipGetErrorString(hipGetLastError()));
     return RT_OK;
 }
 
 int rt_noise_map(rt_ctx* c, const rt_noise_state* state, uint32_t npix, uint32_t n, float floor, float* rel)
 {
-    if (!c) return fail(nullptr, RT_E_INVALID, "rt_noise_map: null context");
-    if (int r = noise_args(c, "rt_noise_map", state, npix, n, floor)) return r;
-    if (!rel && npix) return fail(c, RT_E_INVALID, "rt_noise_map: null map");
+    const char* const who = "rt_noise_map";
+    if (!c) return fail(nullptr, RT_E_INVALID, std::string(who) + ": null context");
+    if (int r = refuse(c, who, noise_fault(n, floor))) return r;
+    // (an empty frame may pass null buffers; the map's alignment is not checked)
+    const BufRange rg[] = {{state, (uint64_t)npix * 8, 8, false, npix == 0, "state"},
+                           {rel, (uint64_t)npix * 4, 1, true, npix == 0, "rel"}};
+    if (int r = refuse(c, who, placement_fault(rg))) return r;
     if (npix == 0) return RT_OK;
     if (int r = set_dev(c)) return r;
     if (rtk::launch_noise_map(state, npix, n, floor, rel, c->stream))
-        return fail(c, RT_E_DEVICE, "rt_noise_map: launch failed");
+        return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed");
     return RT_OK;
 }
 
 int rt_noise_summarize(rt_ctx* c, const rt_noise_state* state, uint32_t npix, uint32_t n, float threshold,
                        float floor, rt_noise_summary* out)
 {
-    if (!c) return fail(nullptr, RT_E_INVALID, "rt_noise_summarize: null context");
-    if (!out) return fail(c, RT_E_INVALID, "rt_noise_summarize: null summary");
-    if (int r = noise_args(c, "rt_noise_summarize", state, npix, n, floor)) return r;
-    if (threshold != threshold) return fail(c, RT_E_INVALID, "rt_noise_summarize: the threshold is NaN");
+    const char* const who = "rt_noise_summarize";
+    if (!c) return fail(nullptr, RT_E_INVALID, std::string(who) + ": null context");
+    if (!out) return fail(c, RT_E_INVALID, std::string(who) + ": null summary");
+    if (int r = refuse(c, who, noise_fault(n, floor))) return r;
+    const BufRange rg[] = {{state, (uint64_t)npix * 8, 8, false, npix == 0, "state"}};
+    if (int r = refuse(c, who, placement_fault(rg))) return r;
+    if (threshold != threshold) return fail(c, RT_E_INVALID, std::string(who) + ": the threshold is NaN");
     memset(out, 0, sizeof *out);
     out->pixels = npix;
     if (npix == 0) return RT_OK;
@@ -92,7 +80,7 @@ int rt_noise_summarize(rt_ctx* c, const rt_noise_state* state, uint32_t npix, ui
     HIPCHK(c, c->noise_sum.ensure(32));
     HIPCHK(c, hipMemsetAsync(c->noise_sum.p, 0, 32, c->stream));
     if (rtk::launch_noise_summary(state, npix, n, threshold, floor, c->noise_sum.as<unsigned long long>(), c->stream))
-        return fail(c, RT_E_DEVICE, "rt_noise_summarize: launch failed");
+        return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed");
     unsigned long long h[3] = {0, 0, 0};
     if (int r = read_back(c, h, c->noise_sum.p, sizeof h)) return r;
     out->above = h[0];
@@ -110,7 +98,7 @@ int rt_set_adaptive(rt_ctx* c, uint32_t* count_dev, float target, float floor, u
         return RT_OK;
     }
     if ((uintptr_t)count_dev % 4) return fail(c, RT_E_INVALID, "rt_set_adaptive: the counts must be 4-byte aligned");
-    if (int r = adaptive_args(c, "rt_set_adaptive", target, floor, min_samples, vote)) return r;
+    if (int r = refuse(c, "rt_set_adaptive", adaptive_fault(target, floor, min_samples, vote))) return r;
     c->adapt.count = count_dev;
     c->adapt.params = rtk::AdaptParams{target, floor, min_samples, (uint32_t)vote};
     return RT_OK;
@@ -120,16 +108,17 @@ int rt_adaptive_accumulate(rt_ctx* c, const float* samples, uint32_t npix, uint3
                            uint32_t first_iter, int last_pass, const uint8_t* live, float* accum, uint32_t* ids,
                            rt_noise_state* state, uint32_t* count)
 {
-    if (!c) return fail(nullptr, RT_E_INVALID, "rt_adaptive_accumulate: null context");
+    const char* const who = "rt_adaptive_accumulate";
+    if (!c) return fail(nullptr, RT_E_INVALID, std::string(who) + ": null context");
     if (npix == 0 || spp == 0) return RT_OK;
-    if (!samples || !live || !accum || !state || !count)
-        return fail(c, RT_E_INVALID, "rt_adaptive_accumulate: null buffer");
-    if ((uintptr_t)samples % 16 || (uintptr_t)accum % 16 || (uintptr_t)state % 8 || (uintptr_t)count % 4 ||
-        (uintptr_t)ids % 4)
-        return fail(c, RT_E_INVALID, "rt_adaptive_accumulate: the records and the accumulation must be 16-byte, the "
-                                     "state 8-byte, the counts and ids 4-byte aligned");
-    if ((uint64_t)first_iter + spp > 0xFFFFFFFFull)
-        return fail(c, RT_E_INVALID, "rt_adaptive_accumulate: first_iter + spp overflows");
+    const BufRange rg[] = {{samples, (uint64_t)npix * spp * 16, 16, false, false, "samples"},
+                           {live, npix, 1, false, false, "live"},
+                           {accum, (uint64_t)npix * 16, 16, true, false, "accum"},
+                           {state, (uint64_t)npix * 8, 8, true, false, "state"},
+                           {count, (uint64_t)npix * 4, 4, true, false, "count"},
+                           {ids, (uint64_t)npix * 4, 4, true, true, "ids"}};
+    if (int r = refuse(c, who, placement_fault(rg))) return r;
+    if ((uint64_t)first_iter + spp > 0xFFFFFFFFull) return fail(c, RT_E_INVALID, std::string(who) + ": first_iter + spp overflows");
     if (int r = set_dev(c)) return r;
     rtk::DevLaunch L = records_launch(samples, npix, spp, pixel_major, first_iter);
     L.u.resolution[0] = npix;   // (the frame the fold's pixels index: the region itself)
@@ -137,22 +126,23 @@ int rt_adaptive_accumulate(rt_ctx* c, const float* samples, uint32_t npix, uint3
     L.accum = reinterpret_cast<float4*>(accum);
     L.ids = ids;
     if (rtk::launch_adaptive_fold(L, nullptr, live, state, count, last_pass != 0, c->stream))
-        return fail(c, RT_E_DEVICE, std::string("rt_adaptive_accumulate: launch failed: ") +
-                                        hipGetErrorString(hipGetLastError()));
+        return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed: " + hipGetErrorString(hipGetLastError()));
     return RT_OK;
 }
 
 int rt_adaptive_map(rt_ctx* c, const rt_noise_state* state, const uint32_t* count, uint32_t npix, float floor, float* rel)
 {
-    if (!c) return fail(nullptr, RT_E_INVALID, "rt_adaptive_map: null context");
-    if (!(floor > 0.0f)) return fail(c, RT_E_INVALID, "rt_adaptive_map: floor must be > 0");
+    const char* const who = "rt_adaptive_map";
+    if (!c) return fail(nullptr, RT_E_INVALID, std::string(who) + ": null context");
+    if (!(floor > 0.0f)) return fail(c, RT_E_INVALID, std::string(who) + ": floor must be > 0");
     if (npix == 0) return RT_OK;
-    if (!state || !count || !rel) return fail(c, RT_E_INVALID, "rt_adaptive_map: null buffer");
-    if ((uintptr_t)state % 8 || (uintptr_t)count % 4 || (uintptr_t)rel % 4)
-        return fail(c, RT_E_INVALID, "rt_adaptive_map: the state must be 8-byte, the counts and the map 4-byte aligned");
+    const BufRange rg[] = {{state, (uint64_t)npix * 8, 8, false, false, "state"},
+                           {count, (uint64_t)npix * 4, 4, false, false, "count"},
+                           {rel, (uint64_t)npix * 4, 4, true, false, "rel"}};
+    if (int r = refuse(c, who, placement_fault(rg))) return r;
     if (int r = set_dev(c)) return r;
     if (rtk::launch_adaptive_map(state, count, npix, floor, rel, c->stream))
-        return fail(c, RT_E_DEVICE, "rt_adaptive_map: launch failed");
+        return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed");
     return RT_OK;
 }
 
@@ -160,17 +150,17 @@ int rt_adaptive_summarize(rt_ctx* c, const rt_noise_state* state, const uint32_t
                           uint32_t iteration, float target, float floor, uint32_t min_samples, int vote,
                           rt_adaptive_summary* out)
 {
-    if (!c) return fail(nullptr, RT_E_INVALID, "rt_adaptive_summarize: null context");
-    if (!out) return fail(c, RT_E_INVALID, "rt_adaptive_summarize: null summary");
-    if (int r = adaptive_args(c, "rt_adaptive_summarize", target, floor, min_samples, vote)) return r;
-    const uint64_t npix = (uint64_t)width * height;
-    if (npix >= (1ull << 31)) return fail(c, RT_E_INVALID, "rt_adaptive_summarize: the frame is too large");
+    const char* const who = "rt_adaptive_summarize";
+    if (!c) return fail(nullptr, RT_E_INVALID, std::string(who) + ": null context");
+    if (!out) return fail(c, RT_E_INVALID, std::string(who) + ": null summary");
+    if (int r = refuse(c, who, adaptive_fault(target, floor, min_samples, vote))) return r;
+    uint64_t npix;
+    if (int r = refuse(c, who, frame_fault(width, height, &npix))) return r;
     memset(out, 0, sizeof *out);
     out->pixels = npix;
     if (npix == 0) return RT_OK;
-    if (!state || !count) return fail(c, RT_E_INVALID, "rt_adaptive_summarize: null buffer");
-    if ((uintptr_t)state % 8 || (uintptr_t)count % 4)
-        return fail(c, RT_E_INVALID, "rt_adaptive_summarize: the state must be 8-byte and the counts 4-byte aligned");
+    const BufRange rg[] = {{state, npix * 8, 8, false, false, "state"}, {count, npix * 4, 4, false, false, "count"}};
+    if (int r = refuse(c, who, placement_fault(rg))) return r;
     if (int r = set_dev(c)) return r;
     rtk::DevLaunch L = region_launch(0, 0, width, height);
     L.u.resolution[0] = width;
@@ -181,7 +171,7 @@ int rt_adaptive_summarize(rt_ctx* c, const rt_noise_state* state, const uint32_t
     HIPCHK(c, stats.ensure(16 * sizeof(unsigned long long)));
     HIPCHK(c, hipMemsetAsync(stats.p, 0, 16 * sizeof(unsigned long long), c->stream));
     if (rtk::launch_adaptive_summary(L, state, count, P, stats.as<unsigned long long>(), c->stream))
-        return fail(c, RT_E_DEVICE, "rt_adaptive_summarize: launch failed");
+        return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed");
     unsigned long long h[9] = {};
     if (int r = read_back(c, h, stats.p, sizeof h)) return r;
     out->live_next = h[0];

@@ -148,6 +148,8 @@ inline uint32_t stream_blocks(uint64_t n, uint64_t cap)
     const uint64_t b = (n + 255) / 256;
     return (uint32_t)(b > cap ? cap : b ? b : 1);
 }
+// the status of the kernel launch just made, as a launcher returns it
+inline int launch_status() { return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE; }
 // Run-time values as template constants: f(std::bool_constant<b>), and
 // f(Int<mode>, std::bool_constant<detail>) for a mode in FIRST..LAST (false: outside).
 // A launcher instantiates its kernel from the arguments' types: k<decltype(M)::value, ..>.

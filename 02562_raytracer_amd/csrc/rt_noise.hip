@@ -11,30 +11,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rt_device_common.h"
+#include "rt_frame_common.h"
 
 namespace rtk {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-// one record into the state: it = the iteration's global index
-__device__ __forceinline__ void noise1(float& mean, float& m2, const v4f x, uint32_t it)
-{
-    const float y = (0.2126f * x.x + 0.7152f * x.y) + 0.0722f * x.z;
-    const float n = (float)(it + 1u);
-    const float d = y - mean;
-    mean = mean + d / n;
-    m2 = m2 + d * (y - mean);
-}
-
 // ------------------------------------------------------------------ state update
-// After k_fold, over the same records and with the same addressing (rt_stream_kernels.h
-// k_fold): one thread per output slot.  [pixel][iteration] records are the thread's own
-// contiguous run, loaded eight (128 B, one line) at a time; [iteration][pixel] records
-// are 1 KiB contiguous per wave and iteration.  The records are not read again after
-// this kernel, the state is: streaming loads for the chunk-major layout as in k_fold.
-// spp x 16 B read and 8 B written per pixel (8 B more read when first_iter > 0).
+// After k_fold, over the same records through the same walk (rt_frame_common.h
+// walk_records): one thread per output slot.  spp x 16 B read and 8 B written per pixel
+// (8 B more read when first_iter > 0).
 __global__ void __launch_bounds__(256) k_noise(DevLaunch L, const uint32_t* empty_mask, rt_noise_state* __restrict__ state)
 {
     const uint32_t nout = L.tileset ? L.nwork * 64u : L.w * L.h;
@@ -42,7 +26,7 @@ __global__ void __launch_bounds__(256) k_noise(DevLaunch L, const uint32_t* empt
         Pix px{0, 0, 0, true};
         if (L.tileset) px = map_pixel(L, o >> 6, o & 63u);
         if (!px.valid) continue;
-        // a flagged pixel (RT_OPT_EMPTY_PIXELS) has no records: the constant, as in k_fold
+        // a flagged pixel (RT_OPT_EMPTY_PIXELS) has no records: the constant
         const bool fl = out_flagged(L, empty_mask, o, px);
         const v4f cst = empty_record(L);
         v2f* const st = reinterpret_cast<v2f*>(state + o);
@@ -52,28 +36,16 @@ __global__ void __launch_bounds__(256) k_noise(DevLaunch L, const uint32_t* empt
             mean = s.x;
             m2 = s.y;
         }
-        uint32_t i = 0;
-        if (L.unit_order) {
-            const v4f* sp = reinterpret_cast<const v4f*>(L.samples + (size_t)o * L.spp);
-            for (; i + 8u <= L.spp; i += 8u) {
-                v4f q[8];
-                path_records(fl, cst, sp + i, q);
-#pragma unroll
-                for (int k = 0; k < 8; k++) noise1(mean, m2, q[k], L.first_iter + i + k);
-            }
-            for (; i < L.spp; i++) noise1(mean, m2, path_record(fl, cst, sp + i), L.first_iter + i);
-        } else {
-            const v4f* sp = reinterpret_cast<const v4f*>(L.samples + o);
-            for (; i < L.spp; i++)
-                noise1(mean, m2, path_record<true>(fl, cst, sp + (size_t)i * L.stride), L.first_iter + i);
-        }
+        walk_records(L, o, fl, cst, [&](const v4f x, uint32_t i) {
+            const uint32_t it = L.first_iter + i;
+            welford1(mean, m2, x, it);
+        });
         const v2f s = {mean, m2};
         *st = s;
     }
 }
 
 // ------------------------------------------------------------------ map and summary
-// (finitef and noise_rel: rt_device_common.h, shared with rt_adaptive.hip)
 __global__ void __launch_bounds__(256) k_noise_map(const rt_noise_state* __restrict__ state, uint32_t npix, float nf,
                                                    float floor, uint32_t* __restrict__ rel)
 {
@@ -81,7 +53,7 @@ __global__ void __launch_bounds__(256) k_noise_map(const rt_noise_state* __restr
     for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < npix; o += gridDim.x * blockDim.x) {
         const v2f s = *reinterpret_cast<const v2f*>(state + o);
         // a non-finite state: the canonical quiet NaN, whatever the state's payload
-        rel[o] = finitef(s.x) && finitef(s.y) ? __float_as_uint(noise_rel(s.x, s.y, denom, floor)) : 0x7FC00000u;
+        rel[o] = __float_as_uint(finitef(s.x) && finitef(s.y) ? noise_rel(s.x, s.y, denom, floor) : qnanf());
     }
 }
 
@@ -109,6 +81,8 @@ __global__ void __launch_bounds__(256) k_noise_summary(const rt_noise_state* __r
     }
     above = wave_sum(above);
     nonfinite = wave_sum(nonfinite);
+    // (the maximum stays written out here and in k_adaptive_live: inlined from a shared function
+    // the shuffles are scheduled differently and both kernels' assembly moves)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const uint32_t other = __shfl_xor(mx, off, 64);
@@ -127,7 +101,7 @@ int launch_noise(const DevLaunch& l, const uint32_t* empty_mask, rt_noise_state*
     // k_fold's grid (launch_fold): the two kernels stream the same records
     const uint64_t nout = l.tileset ? (uint64_t)l.nwork * 64u : (uint64_t)l.w * l.h;
     hipLaunchKernelGGL(k_noise, dim3(stream_blocks(nout, 16384)), dim3(256), 0, stream, l, empty_mask, state);
-    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
+    return launch_status();
 }
 
 int launch_noise_map(const rt_noise_state* state, uint32_t npix, uint32_t n, float floor, float* rel,
@@ -135,7 +109,7 @@ int launch_noise_map(const rt_noise_state* state, uint32_t npix, uint32_t n, flo
 {
     hipLaunchKernelGGL(k_noise_map, dim3(stream_blocks(npix, 2048)), dim3(256), 0, stream, state, npix, (float)n, floor,
                        reinterpret_cast<uint32_t*>(rel));
-    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
+    return launch_status();
 }
 
 int launch_noise_summary(const rt_noise_state* state, uint32_t npix, uint32_t n, float threshold, float floor,
@@ -143,7 +117,7 @@ int launch_noise_summary(const rt_noise_state* state, uint32_t npix, uint32_t n,
 {
     hipLaunchKernelGGL(k_noise_summary, dim3(stream_blocks(npix, 2048)), dim3(256), 0, stream, state, npix, (float)n,
                        threshold, floor, out);
-    return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE;
+    return launch_status();
 }
 
 }  // namespace rtk

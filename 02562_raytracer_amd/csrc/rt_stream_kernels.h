@@ -5,24 +5,20 @@
 #include <stdint.h>
 
 #include "../../include/rt_detmath.h"
-#include "rt_device_common.h"
+#include "rt_frame_common.h"
 #include "rt_internal.h"
-#include "rt_knobs.h"
 
 namespace rtk {
-
-typedef float v4f __attribute__((ext_vector_type(4)));   // a 16-B record (rt_device_common.h rec4)
 
 // ------------------------------------------------------------------ progressive fold
 // The accumulation of fs_main (w7e3.wgsl:261-271 / w9e1.wgsl:272-283), applied
 // for iterations first_iter .. first_iter+spp-1 in order to each output pixel:
 // accum = max(vec4((result + prev*it)/(it+1), 1), 0) with prev the stored
 // accumulation (read when first_iter > 0, as the RenderSource texture).  One
-// thread per pixel.  Chunk-major units write samples as [iteration][pixel] (a
-// wave reads 1 KiB contiguous per iteration); pixel-major units (the default)
-// as [pixel][iteration], so k_path's 16-B records land in whole lines and a
-// thread here streams its own pixel's records.  ids = primary hit of the last
-// iteration.
+// thread per pixel.  Chunk-major units write samples as [iteration][pixel];
+// pixel-major units (the default) as [pixel][iteration], so k_path's 16-B
+// records land in whole lines and a thread here streams its own pixel's records
+// (rt_frame_common.h walk_records).  ids = primary hit of the last iteration.
 __global__ void __launch_bounds__(256) k_fold(DevLaunch L, const uint32_t* empty_mask)
 {
     const uint32_t nout = L.tileset ? L.nwork * 64u : L.w * L.h;
@@ -40,37 +36,35 @@ __global__ void __launch_bounds__(256) k_fold(DevLaunch L, const uint32_t* empty
             a1 = pa.y;
             a2 = pa.z;
         }
+        // walk_records (rt_frame_common.h) written out, as flush_counters writes out wave_sum:
+        // through the function the accumulation's address stays live across the walk, two VGPRs
+        // more (47 -> 49), and the kernel's assembly moves; k_noise and k_adaptive_fold call the
+        // function.  Keep the two alike.  (The iteration is evaluated before fold1's references
+        // are bound: the other order commutes operands.)
         v4f r = {0.0f, 0.0f, 0.0f, 0.0f};
-        auto fold1 = [&](const v4f x, uint32_t i) {
+        auto step = [&](const v4f x, uint32_t i) {
             const uint32_t it = L.first_iter + i;
-            const float fi = (float)it, fi1 = (float)(it + 1u);
-            a0 = rt_max0f((x.x + a0 * fi) / fi1);
-            a1 = rt_max0f((x.y + a1 * fi) / fi1);
-            a2 = rt_max0f((x.z + a2 * fi) / fi1);
+            fold1(a0, a1, a2, x, it);
         };
         uint32_t i = 0;
         if (L.unit_order) {
-            // [pixel][iteration]: the thread's own records are contiguous; eight
-            // (128 B) are loaded together, so each line is fetched once while the
-            // wave's 64 threads stream 64 lines side by side
             const v4f* sp = reinterpret_cast<const v4f*>(L.samples + (size_t)o * L.spp);
             for (; i + RT_FOLD_BATCH <= L.spp; i += RT_FOLD_BATCH) {
                 v4f q[RT_FOLD_BATCH];
                 path_records(fl, cst, sp + i, q);
 #pragma unroll
-                for (int k = 0; k < RT_FOLD_BATCH; k++) fold1(q[k], i + k);
+                for (int k = 0; k < RT_FOLD_BATCH; k++) step(q[k], i + k);
                 r = q[RT_FOLD_BATCH - 1];
             }
             for (; i < L.spp; i++) {
                 r = path_record(fl, cst, sp + i);
-                fold1(r, i);
+                step(r, i);
             }
         } else {
-            // [iteration][pixel]: a wave reads 1 KiB contiguous per iteration
             const v4f* sp = reinterpret_cast<const v4f*>(L.samples + o);
             for (; i < L.spp; i++) {
                 r = path_record<true>(fl, cst, sp + (size_t)i * L.stride);
-                fold1(r, i);
+                step(r, i);
             }
         }
         L.accum[o] = make_float4(a0, a1, a2, 1.0f);

@@ -11,36 +11,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "rt_device_common.h"
+#include "rt_frame_common.h"
 
 namespace rtk {
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bool tp_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-__device__ __forceinline__ float tp_abs(float x) { return __uint_as_float(__float_as_uint(x) & 0x7FFFFFFFu); }
-__device__ __forceinline__ float tp_qnan() { return __uint_as_float(0x7FC00000u); }
-
-__device__ __forceinline__ Cam tp_cam(const float* cam)
-{
-    Cam c;
-    c.e = ld3(cam + 0);
-    c.v = ld3(cam + 3);
-    c.b1 = ld3(cam + 6);
-    c.b2 = ld3(cam + 9);
-    c.d = cam[12];
-    c.aspect = cam[13];
-    return c;
-}
-
-// the pixel-centre ray of (x, y), as rt.h "denoise / Guide" pins it
-__device__ __forceinline__ f3 tp_centre_dir(const Cam& c, uint32_t W, uint32_t H, uint32_t x, uint32_t y)
-{
-    const float ux = ((float)x + 0.5f) / (float)W - 0.5f;
-    const float uy = 0.5f - ((float)y + 0.5f) / (float)H;
-    return cam_dir(c, ux, uy, 0.0f, 0.0f);
-}
 
 // ------------------------------------------------------------------ accumulate
 // One thread per pixel, 16 x 16 blocks.  Both cameras' bases are kernel arguments (SGPRs); a
@@ -54,18 +27,18 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(TemporalArgs A)
     const uint32_t o = y * A.w + x;
     const v4f a4 = reinterpret_cast<const v4f*>(A.color)[o];
     const f3 cur = V(a4.x * A.color_scale, a4.y * A.color_scale, a4.z * A.color_scale);
-    const float l = (0.2126f * cur.x + 0.7152f * cur.y) + 0.0722f * cur.z;
+    const float l = lum709(cur.x, cur.y, cur.z);
     const float l2 = l * l;
     const v4f pn = reinterpret_cast<const v4f*>(A.nz)[o];
-    bool hist = A.hist_color != nullptr && pn.w > 0.0f && tp_finite(cur.x) && tp_finite(cur.y) && tp_finite(cur.z);
+    bool hist = A.hist_color != nullptr && pn.w > 0.0f && finitef(cur.x) && finitef(cur.y) && finitef(cur.z);
     float sw = 0.0f, sm1 = 0.0f, sm2 = 0.0f;
     f3 sc = V(0.0f, 0.0f, 0.0f);
     uint32_t nh = 0xFFFFFFFFu;
     if (hist) {
-        const Cam c = tp_cam(A.cam);
-        const Cam pc = tp_cam(A.pcam);
+        const Cam c = cam_from(A.cam);
+        const Cam pc = cam_from(A.pcam);
         const f3 N = V(pn.x, pn.y, pn.z);
-        const f3 P = add(c.e, muls(tp_centre_dir(c, A.w, A.h, x, y), pn.w));
+        const f3 P = add(c.e, muls(centre_dir(c, A.w, A.h, x, y), pn.w));
         int x0 = (int)x, y0 = (int)y;
         float tx = 0.0f, ty = 0.0f;
         if (!A.still) {
@@ -103,11 +76,11 @@ __global__ void __launch_bounds__(256) k_temporal_accumulate(TemporalArgs A)
                     if (!(dot(N, V(qn.x, qn.y, qn.z)) >= A.normal_min)) continue;
                     const v4f qc = reinterpret_cast<const v4f*>(A.hist_color)[qo];
                     const v2f qm = reinterpret_cast<const v2f*>(A.hist_mom)[qo];
-                    if (!(tp_finite(qc.x) && tp_finite(qc.y) && tp_finite(qc.z) && tp_finite(qm.x) && tp_finite(qm.y)))
+                    if (!(finitef(qc.x) && finitef(qc.y) && finitef(qc.z) && finitef(qm.x) && finitef(qm.y)))
                         continue;
-                    const f3 Pq = add(pc.e, muls(tp_centre_dir(pc, A.w, A.h, (uint32_t)qx, (uint32_t)qy), qn.w));
+                    const f3 Pq = add(pc.e, muls(centre_dir(pc, A.w, A.h, (uint32_t)qx, (uint32_t)qy), qn.w));
                     const float pd = dot(sub(Pq, P), N);
-                    if (!(tp_abs(pd) <= A.plane_tol * pn.w)) continue;
+                    if (!(rt_absf(pd) <= A.plane_tol * pn.w)) continue;
                     sw = sw + bw;
                     sc = add(sc, V(bw * qc.x, bw * qc.y, bw * qc.z));
                     sm1 = sm1 + bw * qm.x;
@@ -145,13 +118,13 @@ template <class Fetch>
 __device__ __forceinline__ float temporal_var_pixel(Fetch fetch, const v2f m, uint32_t len, const v4f pn, const v2f pdz,
                                                     uint32_t min_len, float normal_min, float plane_tol)
 {
-    if (!(tp_finite(m.x) && tp_finite(m.y))) return tp_qnan();
+    if (!(finitef(m.x) && finitef(m.y))) return qnanf();
     float M1 = m.x, M2 = m.y;
     if (len < min_len) {
         float s1 = 0.0f, s2 = 0.0f;
         uint32_t cnt = 0;
         const bool pbg = !(pn.w > 0.0f);
-        const float ztol = plane_tol * tp_abs(pn.w);
+        const float ztol = plane_tol * rt_absf(pn.w);
 #pragma unroll 1
         for (int dy = -3; dy <= 3; dy++) {
 #pragma unroll
@@ -160,15 +133,15 @@ __device__ __forceinline__ float temporal_var_pixel(Fetch fetch, const v2f m, ui
                 if (dy != 0 || dx != 0) {
                     v4f qn;
                     if (!fetch(dx, dy, qm, qn)) continue;
-                    if (!(tp_finite(qm.x) && tp_finite(qm.y))) continue;
+                    if (!(finitef(qm.x) && finitef(qm.y))) continue;
                     const bool qbg = !(qn.w > 0.0f);
                     if (qbg != pbg) continue;
                     if (!pbg) {
                         const float d = (pn.x * qn.x + pn.y * qn.y) + pn.z * qn.z;
                         if (!(d >= normal_min)) continue;
                         const float gr = pdz.x * (float)dx + pdz.y * (float)dy;
-                        const float lim = 2.0f * tp_abs(gr) + ztol;
-                        if (!(tp_abs(pn.w - qn.w) <= lim)) continue;
+                        const float lim = 2.0f * rt_absf(gr) + ztol;
+                        if (!(rt_absf(pn.w - qn.w) <= lim)) continue;
                     }
                 }
                 s1 = s1 + qm.x;
@@ -222,19 +195,16 @@ __global__ void __launch_bounds__(256) k_temporal_variance_lds(TemporalVarArgs A
     const bool any_short = __syncthreads_or(in && len < A.min_len) != 0;
     const int bx = (int)(blockIdx.x * 16u) - 3, by = (int)(blockIdx.y * 16u) - 3;
     if (any_short) {
-        for (int i = (int)threadIdx.x; i < T * T; i += 256) {
-            const int ty = i / T, tx = i - ty * T;
-            const int qx = bx + tx, qy = by + ty;
-            v2f qm = {tp_qnan(), tp_qnan()};
+        stage_tile(T, bx, by, 1, A.w, A.h, [&](int i, bool inside, uint32_t g) {
+            v2f qm = {qnanf(), qnanf()};
             v4f qn = {0.0f, 0.0f, 0.0f, -1.0f};
-            if (qx >= 0 && qy >= 0 && qx < A.w && qy < A.h) {
-                const uint32_t g = (uint32_t)qy * (uint32_t)A.w + (uint32_t)qx;
+            if (inside) {
                 qm = mom[g];
                 qn = nz[g];
             }
             tmom[i] = qm;
             tnz[i] = qn;
-        }
+        });
         __syncthreads();
     }
     if (!in) return;
@@ -251,12 +221,10 @@ __global__ void __launch_bounds__(256) k_temporal_variance_lds(TemporalVarArgs A
 }
 
 // ------------------------------------------------------------------ launchers
-static int tp_ok() { return hipGetLastError() == hipSuccess ? 0 : RT_E_DEVICE; }
-
 int launch_temporal_accumulate(const TemporalArgs& a, hipStream_t stream)
 {
     hipLaunchKernelGGL(k_temporal_accumulate, dim3((a.w + 15) / 16, (a.h + 15) / 16), dim3(256), 0, stream, a);
-    return tp_ok();
+    return launch_status();
 }
 
 int launch_temporal_variance(const TemporalVarArgs& a, bool lds, hipStream_t stream)
@@ -264,7 +232,7 @@ int launch_temporal_variance(const TemporalVarArgs& a, bool lds, hipStream_t str
     const dim3 grid(((uint32_t)a.w + 15) / 16, ((uint32_t)a.h + 15) / 16);
     if (lds) hipLaunchKernelGGL(k_temporal_variance_lds, grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(k_temporal_variance, grid, dim3(256), 0, stream, a);
-    return tp_ok();
+    return launch_status();
 }
 
 }  // namespace rtk

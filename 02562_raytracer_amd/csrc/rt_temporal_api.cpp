@@ -4,25 +4,6 @@
 
 namespace {
 
-struct TpRange {
-    const void* p;
-    uint64_t bytes;
-    bool out;
-};
-// an output that overlaps an input or another output
-bool tp_aliased(const TpRange* r, int n)
-{
-    for (int i = 0; i < n; i++) {
-        if (!r[i].out || !r[i].p) continue;
-        for (int j = 0; j < n; j++) {
-            if (j == i || !r[j].p || (r[j].out && j < i)) continue;
-            const uintptr_t a = (uintptr_t)r[i].p, b = (uintptr_t)r[j].p;
-            if (a < b + r[j].bytes && b < a + r[i].bytes) return true;
-        }
-    }
-    return false;
-}
-
 // the eleven camera floats of a uniform: camera_pos, camera_constant, camera_look_at,
 // aspect_ratio, camera_up (the head of the struct)
 bool same_camera_bits(const rt_uniform& a, const rt_uniform& b) { return memcmp(&a, &b, 11 * sizeof(float)) == 0; }
@@ -41,26 +22,25 @@ int rt_temporal_accumulate(rt_ctx* c, uint32_t width, uint32_t height, const flo
     if (max_history == 0) return fail(c, RT_E_INVALID, std::string(who) + ": max_history must be at least 1");
     if (color_scale != color_scale || normal_min != normal_min || !(plane_tol >= 0.0f))
         return fail(c, RT_E_INVALID, std::string(who) + ": color_scale and normal_min must not be NaN, plane_tol >= 0");
-    const uint64_t npix = (uint64_t)width * height;
-    if (npix >= (1ull << 31)) return fail(c, RT_E_INVALID, std::string(who) + ": the frame is too large");
+    uint64_t npix;
+    if (int r = refuse(c, who, frame_fault(width, height, &npix))) return r;
     const int nhist = (prev != nullptr) + (hist_color != nullptr) + (hist_mom != nullptr) + (hist_len != nullptr) +
                       (hist_nz != nullptr);
     if (nhist != 0 && nhist != 5)
         return fail(c, RT_E_INVALID, std::string(who) + ": a history is prev_uniform and four buffers, or none of them");
     if (npix == 0) return RT_OK;
-    if (!color || !nz || !out_color || !out_mom || !out_len) return fail(c, RT_E_INVALID, std::string(who) + ": null buffer");
-    if ((uintptr_t)color % 16 || (uintptr_t)nz % 16 || (uintptr_t)hist_color % 16 || (uintptr_t)hist_nz % 16 ||
-        (uintptr_t)out_color % 16 || (uintptr_t)hist_mom % 8 || (uintptr_t)out_mom % 8 || (uintptr_t)hist_len % 4 ||
-        (uintptr_t)out_len % 4)
-        return fail(c, RT_E_INVALID, std::string(who) + ": the float4 buffers must be 16-byte, the moments 8-byte and "
-                                                        "the lengths 4-byte aligned");
-    const TpRange rg[] = {{color, npix * 16, false},     {nz, npix * 16, false},      {hist_color, npix * 16, false},
-                          {hist_mom, npix * 8, false},   {hist_len, npix * 4, false}, {hist_nz, npix * 16, false},
-                          {out_color, npix * 16, true},  {out_mom, npix * 8, true},   {out_len, npix * 4, true}};
-    if (tp_aliased(rg, 9)) return fail(c, RT_E_INVALID, std::string(who) + ": an output overlaps another buffer");
+    const BufRange rg[] = {{color, npix * 16, 16, false, false, "color"},
+                           {nz, npix * 16, 16, false, false, "nz"},
+                           {hist_color, npix * 16, 16, false, true, "hist_color"},
+                           {hist_mom, npix * 8, 8, false, true, "hist_mom"},
+                           {hist_len, npix * 4, 4, false, true, "hist_len"},
+                           {hist_nz, npix * 16, 16, false, true, "hist_nz"},
+                           {out_color, npix * 16, 16, true, false, "out_color"},
+                           {out_mom, npix * 8, 8, true, false, "out_mom"},
+                           {out_len, npix * 4, 4, true, false, "out_len"}};
+    if (int r = refuse(c, who, buffers_fault(rg))) return r;
     if (!c->has_u) return fail(c, RT_E_NOT_READY, std::string(who) + ": needs rt_set_uniforms");
-    if (c->u.resolution[0] != width || c->u.resolution[1] != height)
-        return fail(c, RT_E_INVALID, std::string(who) + ": the uniforms' resolution is not width x height");
+    if (int r = refuse(c, who, resolution_fault(c->u.resolution, width, height))) return r;
     if (prev && (prev->resolution[0] != width || prev->resolution[1] != height ||
                  memcmp(&prev->aspect_ratio, &c->u.aspect_ratio, sizeof(float)) != 0))
         return fail(c, RT_E_INVALID, std::string(who) + ": the previous uniform's resolution or aspect differs");
@@ -86,19 +66,14 @@ int rt_temporal_accumulate(rt_ctx* c, uint32_t width, uint32_t height, const flo
     A.out_mom = out_mom;
     A.out_len = out_len;
     TemporalState& t = c->temporal;
-    const bool timed = c->ktime.on;
     t.acc_timed = false;
-    if (timed) {
-        HIPCHK(c, t.ev[0].ensure());
-        HIPCHK(c, t.ev[1].ensure());
-        HIPCHK(c, hipEventRecord(t.ev[0], c->stream));
-    }
-    if (rtk::launch_temporal_accumulate(A, c->stream))
-        return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed: " + hipGetErrorString(hipGetLastError()));
-    if (timed) {
-        HIPCHK(c, hipEventRecord(t.ev[1], c->stream));
-        t.acc_timed = true;
-    }
+    const int r = timed(c, &t.ev[0], t.ev[1], [&] {
+        if (rtk::launch_temporal_accumulate(A, c->stream))
+            return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed: " + hipGetErrorString(hipGetLastError()));
+        return (int)RT_OK;
+    });
+    if (r) return r;
+    t.acc_timed = c->ktime.on;
     return RT_OK;
 }
 
@@ -110,16 +85,13 @@ int rt_temporal_variance(rt_ctx* c, uint32_t width, uint32_t height, const float
     if (min_len == 0) return fail(c, RT_E_INVALID, std::string(who) + ": min_len must be at least 1");
     if (normal_min != normal_min || !(plane_tol >= 0.0f))
         return fail(c, RT_E_INVALID, std::string(who) + ": normal_min must not be NaN, plane_tol >= 0");
-    const uint64_t npix = (uint64_t)width * height;
-    if (npix >= (1ull << 31)) return fail(c, RT_E_INVALID, std::string(who) + ": the frame is too large");
+    uint64_t npix;
+    if (int r = refuse(c, who, frame_fault(width, height, &npix))) return r;
     if (npix == 0) return RT_OK;
-    if (!mom || !len || !nz || !dz || !var) return fail(c, RT_E_INVALID, std::string(who) + ": null buffer");
-    if ((uintptr_t)nz % 16 || (uintptr_t)mom % 8 || (uintptr_t)dz % 8 || (uintptr_t)len % 4 || (uintptr_t)var % 4)
-        return fail(c, RT_E_INVALID, std::string(who) + ": nz must be 16-byte, the moments and dz 8-byte, the lengths "
-                                                        "and the variance 4-byte aligned");
-    const TpRange rg[] = {{mom, npix * 8, false}, {len, npix * 4, false}, {nz, npix * 16, false}, {dz, npix * 8, false},
-                          {var, npix * 4, true}};
-    if (tp_aliased(rg, 5)) return fail(c, RT_E_INVALID, std::string(who) + ": the output overlaps an input");
+    const BufRange rg[] = {{mom, npix * 8, 8, false, false, "mom"}, {len, npix * 4, 4, false, false, "len"},
+                           {nz, npix * 16, 16, false, false, "nz"}, {dz, npix * 8, 8, false, false, "dz"},
+                           {var, npix * 4, 4, true, false, "var"}};
+    if (int r = refuse(c, who, buffers_fault(rg))) return r;
     if (int r = set_dev(c)) return r;
     rtk::TemporalVarArgs A;
     A.mom = mom;
@@ -133,20 +105,15 @@ int rt_temporal_variance(rt_ctx* c, uint32_t width, uint32_t height, const float
     A.normal_min = normal_min;
     A.plane_tol = plane_tol;
     TemporalState& t = c->temporal;
-    const bool timed = c->ktime.on;
     t.var_timed = false;
-    if (timed) {
-        HIPCHK(c, t.ev[2].ensure());
-        HIPCHK(c, t.ev[3].ensure());
-        HIPCHK(c, hipEventRecord(t.ev[2], c->stream));
-    }
-    if (rtk::launch_temporal_variance(A, t.var_lds, c->stream))
-        return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed: " + hipGetErrorString(hipGetLastError()));
-    t.var_form = t.var_lds ? 1u : 0u;
-    if (timed) {
-        HIPCHK(c, hipEventRecord(t.ev[3], c->stream));
-        t.var_timed = true;
-    }
+    const int r = timed(c, &t.ev[2], t.ev[3], [&] {
+        if (rtk::launch_temporal_variance(A, t.var_lds, c->stream))
+            return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed: " + hipGetErrorString(hipGetLastError()));
+        t.var_form = t.var_lds ? 1u : 0u;
+        return (int)RT_OK;
+    });
+    if (r) return r;
+    t.var_timed = c->ktime.on;
     return RT_OK;
 }
 

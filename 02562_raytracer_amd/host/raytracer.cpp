@@ -688,6 +688,30 @@ std::vector<uint8_t> RenderState::frame_rgba8() const
     return out;
 }
 
+// The float4 frame d on the device (freed here, whatever happens), downloaded as it is ...
+static std::vector<float> take_frame(const GpuHandles& gpu, void* d, size_t npx, const char* what)
+{
+    std::vector<float> out(npx * 4);
+    const int rc = rt_memcpy_to_host(gpu.ctx(), out.data(), d, out.size() * 4);
+    rt_device_free(gpu.ctx(), d);
+    gpu.check(rc, what);
+    return out;
+}
+// ... or as the sRGB surface would hold it (rt_frame_rgba8_mode)
+static std::vector<uint8_t> take_rgba8(const GpuHandles& gpu, rt_mode mode, void* d, size_t npx, const char* what)
+{
+    void* img = nullptr;
+    int rc = rt_device_alloc(gpu.ctx(), npx * 4, &img);
+    std::vector<uint8_t> out(npx * 4);
+    if (rc == RT_OK)
+        rc = rt_frame_rgba8_mode(gpu.ctx(), mode, static_cast<const float*>(d), (uint32_t)npx, static_cast<uint8_t*>(img));
+    if (rc == RT_OK) rc = rt_memcpy_to_host(gpu.ctx(), out.data(), img, out.size());
+    rt_device_free(gpu.ctx(), img);
+    rt_device_free(gpu.ctx(), d);
+    gpu.check(rc, what);
+    return out;
+}
+
 // the denoised frame on the device (the caller frees it)
 void* RenderState::denoise_device(uint32_t levels, float sigma_l, float sigma_z) const
 {
@@ -711,28 +735,12 @@ void* RenderState::denoise_device(uint32_t levels, float sigma_l, float sigma_z)
 
 std::vector<float> RenderState::denoise(uint32_t levels, float sigma_l, float sigma_z) const
 {
-    void* d = denoise_device(levels, sigma_l, sigma_z);
-    std::vector<float> out((size_t)width_ * height_ * 4);
-    const int rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), d, out.size() * 4);
-    rt_device_free(gpu_.ctx(), d);
-    gpu_.check(rc, "denoise");
-    return out;
+    return take_frame(gpu_, denoise_device(levels, sigma_l, sigma_z), (size_t)width_ * height_, "denoise");
 }
 
 std::vector<uint8_t> RenderState::denoised_rgba8(uint32_t levels, float sigma_l, float sigma_z) const
 {
-    void* d = denoise_device(levels, sigma_l, sigma_z);
-    const size_t npx = (size_t)width_ * height_;
-    void* img = nullptr;
-    int rc = rt_device_alloc(gpu_.ctx(), npx * 4, &img);
-    std::vector<uint8_t> out(npx * 4);
-    if (rc == RT_OK)
-        rc = rt_frame_rgba8_mode(gpu_.ctx(), mode(), static_cast<const float*>(d), (uint32_t)npx, static_cast<uint8_t*>(img));
-    if (rc == RT_OK) rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), img, out.size());
-    rt_device_free(gpu_.ctx(), img);
-    rt_device_free(gpu_.ctx(), d);
-    gpu_.check(rc, "denoised_rgba8");
-    return out;
+    return take_rgba8(gpu_, mode(), denoise_device(levels, sigma_l, sigma_z), (size_t)width_ * height_, "denoised_rgba8");
 }
 
 // ---- temporal accumulation (rt.h "temporal accumulation")
@@ -856,28 +864,12 @@ void* RenderState::temporal_device(uint32_t levels, float sigma_l, float sigma_z
 
 std::vector<float> RenderState::temporal_frame(uint32_t levels, float sigma_l, float sigma_z) const
 {
-    void* d = temporal_device(levels, sigma_l, sigma_z);
-    std::vector<float> out((size_t)width_ * height_ * 4);
-    const int rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), d, out.size() * 4);
-    rt_device_free(gpu_.ctx(), d);
-    gpu_.check(rc, "temporal_frame");
-    return out;
+    return take_frame(gpu_, temporal_device(levels, sigma_l, sigma_z), (size_t)width_ * height_, "temporal_frame");
 }
 
 std::vector<uint8_t> RenderState::temporal_rgba8(uint32_t levels, float sigma_l, float sigma_z) const
 {
-    void* d = temporal_device(levels, sigma_l, sigma_z);
-    const size_t npx = (size_t)width_ * height_;
-    void* img = nullptr;
-    int rc = rt_device_alloc(gpu_.ctx(), npx * 4, &img);
-    std::vector<uint8_t> out(npx * 4);
-    if (rc == RT_OK)
-        rc = rt_frame_rgba8_mode(gpu_.ctx(), mode(), static_cast<const float*>(d), (uint32_t)npx, static_cast<uint8_t*>(img));
-    if (rc == RT_OK) rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), img, out.size());
-    rt_device_free(gpu_.ctx(), img);
-    rt_device_free(gpu_.ctx(), d);
-    gpu_.check(rc, "temporal_rgba8");
-    return out;
+    return take_rgba8(gpu_, mode(), temporal_device(levels, sigma_l, sigma_z), (size_t)width_ * height_, "temporal_rgba8");
 }
 
 RenderState::TemporalCurrent RenderState::temporal_current() const

@@ -342,6 +342,25 @@ class RenderState:
                 break
         return self.iteration, summary
 
+    def _filtered_frame(self, fill, rgba8):
+        """What the four filtered-frame methods share: fill(out) writes a float4 frame into a device
+        buffer; returned as float32 [H, W, 4], or (rgba8) through rt_frame_rgba8_mode as uint8
+        [H, W, 4].  The buffers are freed whatever happens."""
+        npx = self.width * self.height
+        bufs = []
+        try:
+            bufs.append(self.ctx.alloc(npx * 16))
+            if rgba8:
+                bufs.append(self.ctx.alloc(npx * 4))
+            fill(bufs[0])
+            if not rgba8:
+                return bufs[0].to_numpy(np.float32, (self.height, self.width, 4))
+            self.ctx.frame_rgba8(bufs[0].ptr, npx, bufs[1].ptr, mode=self.mode)
+            return bufs[1].to_numpy(np.uint8, (self.height, self.width, 4))
+        finally:
+            for b in bufs:
+                b.free()
+
     # ---- the denoise filter (include/rt.h "denoise"; single process, no tiles)
     def _denoise_check(self, levels, sigma_l, sigma_z):
         """(no device: the checks come before any allocation)"""
@@ -367,27 +386,13 @@ class RenderState:
         sampling every pixel's variance uses its own sample count.  The accumulation, the ids and
         the noise state are not changed."""
         self._denoise_check(levels, sigma_l, sigma_z)
-        out = self.ctx.alloc(self.width * self.height * 16)
-        try:
-            self._denoise_into(out, levels, sigma_l, sigma_z)
-            return out.to_numpy(np.float32, (self.height, self.width, 4))
-        finally:
-            out.free()
+        return self._filtered_frame(lambda out: self._denoise_into(out, levels, sigma_l, sigma_z), rgba8=False)
 
     def denoised_rgba8(self, levels=5, sigma_l=4.0, sigma_z=1.0):
         """The denoised frame as the sRGB surface would hold it: uint8 [H, W, 4]
         (rt_frame_rgba8_mode of denoise())."""
         self._denoise_check(levels, sigma_l, sigma_z)
-        npx = self.width * self.height
-        out = self.ctx.alloc(npx * 16)
-        img = self.ctx.alloc(npx * 4)
-        try:
-            self._denoise_into(out, levels, sigma_l, sigma_z)
-            self.ctx.frame_rgba8(out.ptr, npx, img.ptr, mode=self.mode)
-            return img.to_numpy(np.uint8, (self.height, self.width, 4))
-        finally:
-            out.free()
-            img.free()
+        return self._filtered_frame(lambda out: self._denoise_into(out, levels, sigma_l, sigma_z), rgba8=True)
 
     # ---- temporal accumulation (include/rt.h "temporal accumulation"; single process, no tiles)
     def enable_temporal(self, max_history=32, normal_min=0.9, plane_tol=0.01, min_len=4):
@@ -513,26 +518,12 @@ class RenderState:
         """The latest integrated frame through rt_temporal_variance and rt_denoise_filter:
         float32 [H, W, 4], alpha 1."""
         self._temporal_check(levels, sigma_l, sigma_z)
-        out = self.ctx.alloc(self.width * self.height * 16)
-        try:
-            self._temporal_filter_into(out, levels, sigma_l, sigma_z)
-            return out.to_numpy(np.float32, (self.height, self.width, 4))
-        finally:
-            out.free()
+        return self._filtered_frame(lambda out: self._temporal_filter_into(out, levels, sigma_l, sigma_z), rgba8=False)
 
     def temporal_rgba8(self, levels=5, sigma_l=4.0, sigma_z=1.0):
         """temporal_frame() as the sRGB surface would hold it: uint8 [H, W, 4] (rt_frame_rgba8_mode)."""
         self._temporal_check(levels, sigma_l, sigma_z)
-        npx = self.width * self.height
-        out = self.ctx.alloc(npx * 16)
-        img = self.ctx.alloc(npx * 4)
-        try:
-            self._temporal_filter_into(out, levels, sigma_l, sigma_z)
-            self.ctx.frame_rgba8(out.ptr, npx, img.ptr, mode=self.mode)
-            return img.to_numpy(np.uint8, (self.height, self.width, 4))
-        finally:
-            out.free()
-            img.free()
+        return self._filtered_frame(lambda out: self._temporal_filter_into(out, levels, sigma_l, sigma_z), rgba8=True)
 
     def frame(self):
         """Linear accumulation [H, W, 4] float32 (the RenderDestination texture)."""

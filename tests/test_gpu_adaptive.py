@@ -171,6 +171,65 @@ def test_accumulate_count_is_written_by_the_last_pass_only(gpu):
     b.free()
 
 
+@pytest.mark.parametrize("first", [0, 3])
+@pytest.mark.parametrize("pixel_major", [1, 0])
+def test_noise_and_adaptive_accumulate_walk_the_same_records(gpu, pixel_major, first):
+    """rt_noise_accumulate and rt_adaptive_accumulate share one record walk: over the same
+    records, all slots live, they leave the same state bit for bit, and both restatements'.  65
+    slots (a wave and one); spp below, at and above the batch of eight, and two batches and a
+    tail.  A second set of records holds one NaN per slot, at its own iteration and channel: the
+    accumulation zeroes that channel there and goes on, the state stays NaN -- a walk that skipped
+    the record would show in both."""
+    npix, tail = 65, 64
+    live = np.ones(npix, bool)
+    lv = gpu.alloc(npix + 16)
+    lv.from_numpy(np.ones(npix + 16, np.uint8))
+    p = np.arange(npix)
+    for spp in (1, 7, 8, 9, 17):
+        for with_nan in (False, True):
+            what = (spp, pixel_major, first, with_nan)
+            rng = np.random.default_rng(1000 * spp + 10 * first + with_nan)
+            rec = rng.uniform(0.0, 4.0, (npix, first + spp, 4)).astype(f32)
+            rec[..., 3] = rng.integers(0, 1 << 32, (npix, first + spp), dtype=np.uint64).astype(np.uint32).view(f32)
+            if with_nan:
+                rec[p, first + p % spp, p % 3] = np.nan
+            init = (np.zeros((npix, 4), f32), np.zeros(npix, np.uint32), np.zeros((npix, 2), f32), np.zeros(npix, np.uint32))
+            if first:
+                init = AR.fold(rec[:, :first], 0, live, *init)
+            new = np.ascontiguousarray(rec[:, first:])
+            data = new if pixel_major else np.ascontiguousarray(new.transpose(1, 0, 2))
+            sb = gpu.alloc(data.nbytes)
+            sb.from_numpy(data)
+            st = gpu.alloc((npix + tail) * 8)
+            st.from_numpy(np.concatenate([u32(init[2]).ravel(), np.full(tail * 2, SENTINEL, np.uint32)]))
+            gpu.noise_accumulate(sb.ptr, npix, spp, pixel_major, first, st.ptr)
+            ns = st.to_numpy(np.uint32, (npix + tail, 2))
+            assert np.all(ns[npix:] == SENTINEL), what
+            ns = ns[:npix]
+            b = Bufs(gpu, npix)
+            b.put(*init)
+            gpu.adaptive_accumulate(sb.ptr, npix, spp, pixel_major, first, 1, lv.ptr, b.accum.ptr, b.ids.ptr, b.state.ptr,
+                                    b.count.ptr)
+            ga, gi, gs, gc = b.get()
+            ra, ri, rs, rc = AR.fold(new, first, live, *init)
+            fin = np.isfinite(rs)
+            assert np.array_equal(ns[fin], gs[fin]) and np.array_equal(np.isnan(ns.view(f32)), np.isnan(gs.view(f32))), what
+            if not with_nan:
+                assert fin.all() and np.array_equal(ns, gs), what
+            else:
+                assert np.isnan(gs.view(f32)).all(), what
+            assert_f32_matches(gs, rs, what)
+            assert_f32_matches(ns, rs, what)
+            assert_f32_matches(ns, NR.accumulate(new, first, init[2]), what)
+            assert np.isfinite(ra).all()
+            assert_f32_matches(ga, ra, what)
+            assert np.array_equal(gi, ri) and np.array_equal(gi, u32(new[:, -1, 3])) and np.all(gc == first + spp), what
+            for x in (sb, st):
+                x.free()
+            b.free()
+    lv.free()
+
+
 # ---- renders ----------------------------------------------------------------------------
 W, H = 70, 45          # 9 x 6 tiles, ragged right column and bottom row
 FULL = (0, 0, W, H)
