@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <sys/stat.h>
 
 namespace raytracer {
@@ -146,7 +147,7 @@ std::vector<SceneDescriptor> get_scenes()
     const Camera bunny = cam({-0.02f, 0.11f, 0.6f}, {-0.02f, 0.11f, 0.0f}, {0.0f, 1.0f, 0.0f}, 3.5f);
     const Camera dragon = bunny;   // scenes.rs:79-85 uses the bunny framing
     const std::string campus = "luxo_pxr_campus.jpg", campus_hdr = "luxo_pxr_campus.hdr.png";
-    const auto C = VertexType::Combined, Sp = VertexType::Split;
+    const auto C = VertexType::Combined;
     const auto BSP = TraverseType::Bsp, BVH = TraverseType::Bvh;
 
     std::vector<SceneDescriptor> v;
@@ -198,7 +199,6 @@ std::vector<SceneDescriptor> get_scenes()
     S("Project: Bunny BSP", "project.wgsl", "bunny.obj", bunny, 512, 512, C, BSP);
     S("Project: Dragon", "project.wgsl", "dragon.obj", dragon, 800, 450, C, BVH);
     S("Project: Dragon BSP", "project.wgsl", "dragon.obj", dragon, 800, 450, C, BSP);
-    (void)Sp;
     return v;
 }
 
@@ -344,19 +344,15 @@ RenderState::~RenderState() { release(); }
 
 void RenderState::release()
 {
-    if (accum_) rt_device_free(gpu_.ctx(), accum_);
-    if (ids_) rt_device_free(gpu_.ctx(), ids_);
-    if (tile_accum_) rt_device_free(gpu_.ctx(), tile_accum_);
-    if (tile_ids_) rt_device_free(gpu_.ctx(), tile_ids_);
-    if (counts_) {
-        rt_set_adaptive(gpu_.ctx(), nullptr, 0.0f, 0.0f, 0, 0);
-        rt_device_free(gpu_.ctx(), counts_);
-    }
-    if (noise_) {
-        rt_set_noise_buffer(gpu_.ctx(), nullptr);
-        rt_device_free(gpu_.ctx(), noise_);
-    }
-    accum_ = ids_ = tile_accum_ = tile_ids_ = noise_ = counts_ = nullptr;
+    // deregister before free: the context never keeps a pointer into a buffer that is gone
+    if (counts_) rt_set_adaptive(gpu_.ctx(), nullptr, 0.0f, 0.0f, 0, 0);
+    if (noise_) rt_set_noise_buffer(gpu_.ctx(), nullptr);
+    accum_.reset();
+    ids_.reset();
+    tile_accum_.reset();
+    tile_ids_.reset();
+    counts_.reset();
+    noise_.reset();
     disable_temporal();
 }
 
@@ -369,29 +365,21 @@ void RenderState::enable_noise()
     if (!writes_records(row_))
         throw Error(RT_E_UNSUPPORTED, "enable_noise: the mode writes no per-iteration records");
     if (iteration_) throw Error(RT_E_INVALID, "enable_noise: the estimate starts at iteration 0");
-    rt_ctx* c = gpu_.ctx();
-    if (!noise_) {
-        const size_t npx = (size_t)width_ * height_;
-        gpu_.check(rt_device_alloc(c, npx * sizeof(rt_noise_state), &noise_), "noise buffer");
-        gpu_.check(rt_memset_device(c, noise_, 0, npx * sizeof(rt_noise_state)), "clear noise buffer");
+    if (!noise_) {   // a member only once it is cleared: a failed clear leaves the estimate off
+        DeviceArray<rt_noise_state> fresh(gpu_, (size_t)width_ * height_, "noise buffer");
+        fresh.zero("clear noise buffer");
+        noise_ = std::move(fresh);
     }
-    gpu_.check(rt_set_noise_buffer(c, static_cast<rt_noise_state*>(noise_)), "set noise buffer");
+    gpu_.check(rt_set_noise_buffer(gpu_.ctx(), noise_.get()), "set noise buffer");
 }
 
 std::vector<float> RenderState::noise_map(float floor) const
 {
     if (!noise_) throw Error(RT_E_NOT_READY, "noise_map: enable_noise() first");
     if (tiled_) throw Error(RT_E_UNSUPPORTED, "noise_map is for an untiled state: a tiled render (set_tiling, any rank count) keeps its states packed per tile");
-    const size_t npx = (size_t)width_ * height_;
-    void* d = nullptr;
-    gpu_.check(rt_device_alloc(gpu_.ctx(), npx * 4, &d), "noise map buffer");
-    std::vector<float> out(npx);
-    int rc = rt_noise_map(gpu_.ctx(), static_cast<const rt_noise_state*>(noise_), (uint32_t)npx, iteration_, floor,
-                          static_cast<float*>(d));
-    if (rc == RT_OK) rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), d, npx * 4);
-    rt_device_free(gpu_.ctx(), d);
-    gpu_.check(rc, "noise_map");
-    return out;
+    const DeviceArray<float> d(gpu_, noise_.size(), "noise map buffer");
+    gpu_.check(rt_noise_map(gpu_.ctx(), noise_.get(), (uint32_t)noise_.size(), iteration_, floor, d.get()), "noise_map");
+    return d.download("noise_map");
 }
 
 rt_noise_summary RenderState::noise_summary(float threshold, float floor) const
@@ -399,8 +387,7 @@ rt_noise_summary RenderState::noise_summary(float threshold, float floor) const
     if (!noise_) throw Error(RT_E_NOT_READY, "noise_summary: enable_noise() first");
     if (tiled_) throw Error(RT_E_UNSUPPORTED, "noise_summary is for an untiled state: a tiled render (set_tiling, any rank count) keeps its states packed per tile");
     rt_noise_summary s;
-    gpu_.check(rt_noise_summarize(gpu_.ctx(), static_cast<const rt_noise_state*>(noise_),
-                                  (uint32_t)((size_t)width_ * height_), iteration_, threshold, floor, &s),
+    gpu_.check(rt_noise_summarize(gpu_.ctx(), noise_.get(), (uint32_t)noise_.size(), iteration_, threshold, floor, &s),
                "noise_summary");
     return s;
 }
@@ -436,26 +423,23 @@ void RenderState::enable_adaptive(float target, float floor, uint32_t min_sample
     if (min_samples < 2 || !(target >= 0.0f) || !(floor > 0.0f) || (vote != RT_ADAPT_PIXEL && vote != RT_ADAPT_TILE))
         throw Error(RT_E_INVALID, "enable_adaptive: min_samples >= 2, target >= 0, floor > 0, vote pixel or tile");
     if (!noise_) enable_noise();
-    rt_ctx* c = gpu_.ctx();
-    if (!counts_) {
-        const size_t npx = (size_t)width_ * height_;
-        gpu_.check(rt_device_alloc(c, npx * 4, &counts_), "sample count buffer");
-        gpu_.check(rt_memset_device(c, counts_, 0, npx * 4), "clear sample counts");
+    if (!counts_) {   // as the noise buffer: a member only once it is cleared
+        DeviceArray<uint32_t> fresh(gpu_, (size_t)width_ * height_, "sample count buffer");
+        fresh.zero("clear sample counts");
+        counts_ = std::move(fresh);
     }
     ad_target_ = target;
     ad_floor_ = floor;
     ad_min_ = min_samples;
     ad_vote_ = vote;
-    gpu_.check(rt_set_adaptive(c, static_cast<uint32_t*>(counts_), target, floor, min_samples, vote), "set adaptive");
+    gpu_.check(rt_set_adaptive(gpu_.ctx(), counts_.get(), target, floor, min_samples, vote), "set adaptive");
 }
 
 std::vector<uint32_t> RenderState::sample_counts() const
 {
     if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("sample_counts") + kAdaptiveUntiled);
     if (!counts_) throw Error(RT_E_NOT_READY, "sample_counts: enable_adaptive() first");
-    std::vector<uint32_t> out((size_t)width_ * height_);
-    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), out.data(), counts_, out.size() * 4), "sample_counts");
-    return out;
+    return counts_.download("sample_counts");
 }
 
 rt_adaptive_summary RenderState::adaptive_summary() const
@@ -463,8 +447,7 @@ rt_adaptive_summary RenderState::adaptive_summary() const
     if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("adaptive_summary") + kAdaptiveUntiled);
     if (!counts_) throw Error(RT_E_NOT_READY, "adaptive_summary: enable_adaptive() first");
     rt_adaptive_summary s;
-    gpu_.check(rt_adaptive_summarize(gpu_.ctx(), static_cast<const rt_noise_state*>(noise_),
-                                     static_cast<const uint32_t*>(counts_), width_, height_, iteration_, ad_target_,
+    gpu_.check(rt_adaptive_summarize(gpu_.ctx(), noise_.get(), counts_.get(), width_, height_, iteration_, ad_target_,
                                      ad_floor_, ad_min_, ad_vote_, &s),
                "adaptive_summary");
     return s;
@@ -486,6 +469,19 @@ uint32_t RenderState::render_adaptive(uint32_t max_samples, uint32_t batch, rt_a
     return iteration_;
 }
 
+// the packed tile buffers of one rank for a width x height frame (zeroed: the accumulation
+// of iteration 0 is not read), both or neither
+static void make_tiles(const GpuHandles& gpu, uint32_t width, uint32_t height, uint32_t nranks,
+                       DeviceArray<float>& accum, DeviceArray<uint32_t>& ids)
+{
+    const size_t px = (size_t)rt_tileset_local_tiles(width, height, nranks) * 64u;
+    DeviceArray<float> a(gpu, px * 4, "tile accumulation buffer");
+    DeviceArray<uint32_t> i(gpu, px, "tile id buffer");
+    a.zero("clear tile accumulation");
+    accum = std::move(a);
+    ids = std::move(i);
+}
+
 void RenderState::set_tiling(uint32_t nranks, uint32_t rank, const uint8_t comm_id[RT_COMM_ID_BYTES])
 {
     if (tiled_) throw Error(RT_E_INVALID, "set_tiling: already tiled");
@@ -494,25 +490,10 @@ void RenderState::set_tiling(uint32_t nranks, uint32_t rank, const uint8_t comm_
     if (noise_) throw Error(RT_E_UNSUPPORTED, "set_tiling: the noise estimate is enabled (it is for an untiled state)");
     if (temporal_) throw Error(RT_E_UNSUPPORTED, "set_tiling: temporal accumulation is enabled (it is for an untiled state)");
     gpu_.check(rt_comm_init(gpu_.ctx(), nranks, rank, comm_id), "communicator");
+    make_tiles(gpu_, width_, height_, nranks, tile_accum_, tile_ids_);   // (a throw leaves the state untiled)
     nranks_ = nranks;
     rank_ = rank;
     tiled_ = true;
-    alloc_tiles();
-}
-
-// the packed tile buffers of this rank for the current resolution (zeroed: the
-// accumulation of iteration 0 is not read)
-void RenderState::alloc_tiles()
-{
-    if (!tiled_) return;
-    rt_ctx* c = gpu_.ctx();
-    if (tile_accum_) rt_device_free(c, tile_accum_);
-    if (tile_ids_) rt_device_free(c, tile_ids_);
-    tile_accum_ = tile_ids_ = nullptr;
-    const size_t px = (size_t)rt_tileset_local_tiles(width_, height_, nranks_) * 64u;
-    gpu_.check(rt_device_alloc(c, px * 16, &tile_accum_), "tile accumulation buffer");
-    gpu_.check(rt_device_alloc(c, px * 4, &tile_ids_), "tile id buffer");
-    gpu_.check(rt_memset_device(c, tile_accum_, 0, px * 16), "clear tile accumulation");
 }
 
 void RenderState::setup_rendering(const SceneDescriptor& scene)
@@ -548,9 +529,8 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
             } else {   // Mesh::bsp_tree, mesh.rs:229-231 (depth 20, leaf 4)
                 rt_bsp_host* b = nullptr;
                 gpu_.check(rt_bsp_build(mesh.get(), 20, 4, 0, &b), "BSP build");
-                const int rc = rt_upload_bsp_host(c, b);
-                rt_bsp_free(b);
-                gpu_.check(rc, "upload BSP");
+                const std::unique_ptr<rt_bsp_host, decltype(&rt_bsp_free)> own(b, rt_bsp_free);
+                gpu_.check(rt_upload_bsp_host(c, b), "upload BSP");
             }
         } else if (trav_ == RT_TRAVERSE_BVH) {   // (NONE: the brute-force W5 scenes, the mesh alone)
             if (opts_.device_build) {
@@ -558,21 +538,20 @@ void RenderState::setup_rendering(const SceneDescriptor& scene)
             } else {   // Mesh::bvh, mesh.rs:233-239 (leaf 4)
                 rt_bvh_host* b = nullptr;
                 gpu_.check(rt_bvh_build(mesh.get(), 4, &b), "HLBVH build");
-                const int rc = rt_upload_bvh_host(c, b);
-                rt_bvh_free(b);
-                gpu_.check(rc, "upload BVH");
+                const std::unique_ptr<rt_bvh_host, decltype(&rt_bvh_free)> own(b, rt_bvh_free);
+                gpu_.check(rt_upload_bvh_host(c, b), "upload BVH");
             }
         }
     }
     gpu_.check(rt_set_environment(c, opts_.environment.data()), "environment");
     gpu_.check(rt_set_environment_map(c, nullptr, 0, 0), "environment map");
-    const bool had_noise = noise_ != nullptr, had_adaptive = counts_ != nullptr, had_temporal = temporal_;
-    release();
+    const bool had_noise = (bool)noise_, had_adaptive = (bool)counts_, had_temporal = temporal_;
+    release();   // free, then allocate: the old frame and the new need not fit side by side
     const size_t npx = (size_t)width_ * height_;
-    gpu_.check(rt_device_alloc(c, npx * 16, &accum_), "accumulation buffer");
-    gpu_.check(rt_device_alloc(c, npx * 4, &ids_), "id buffer");
-    gpu_.check(rt_memset_device(c, accum_, 0, npx * 16), "clear accumulation");
-    alloc_tiles();
+    accum_ = DeviceArray<float>(gpu_, npx * 4, "accumulation buffer");
+    ids_ = DeviceArray<uint32_t>(gpu_, npx, "id buffer");
+    accum_.zero("clear accumulation");
+    if (tiled_) make_tiles(gpu_, width_, height_, nranks_, tile_accum_, tile_ids_);
     iteration_ = 0;
     if (had_noise && writes_records(row_)) enable_noise();   // the buffer follows the scene
     if (had_adaptive && writes_records(row_)) enable_adaptive(ad_target_, ad_floor_, ad_min_, ad_vote_);
@@ -601,19 +580,15 @@ void RenderState::render(uint32_t spp)
     if (tiled_) {
         // this rank's tiles, then every rank's tiles into rank 0's frame
         const rt_tileset ts{rank_, nranks_};
-        gpu_.check(rt_render_tiles(gpu_.ctx(), mode(), trav_, &ts, iteration_, spp, static_cast<float*>(tile_accum_),
-                                   static_cast<uint32_t*>(tile_ids_), nullptr),
+        gpu_.check(rt_render_tiles(gpu_.ctx(), mode(), trav_, &ts, iteration_, spp, tile_accum_.get(), tile_ids_.get(), nullptr),
                    "render tiles");
         const bool root = rank_ == 0;
-        gpu_.check(rt_gather_tiles(gpu_.ctx(), width_, height_, static_cast<const float*>(tile_accum_),
-                                   static_cast<const uint32_t*>(tile_ids_), root ? static_cast<float*>(accum_) : nullptr,
-                                   root ? static_cast<uint32_t*>(ids_) : nullptr),
+        gpu_.check(rt_gather_tiles(gpu_.ctx(), width_, height_, tile_accum_.get(), tile_ids_.get(),
+                                   root ? accum_.get() : nullptr, root ? ids_.get() : nullptr),
                    "gather tiles");
     } else {
         const rt_tile region{0, 0, width_, height_};
-        gpu_.check(rt_render(gpu_.ctx(), mode(), trav_, &region, iteration_, spp, static_cast<float*>(accum_),
-                             static_cast<uint32_t*>(ids_), nullptr),
-                   "render");
+        gpu_.check(rt_render(gpu_.ctx(), mode(), trav_, &region, iteration_, spp, accum_.get(), ids_.get(), nullptr), "render");
     }
     if (progressive_ && (row_.flags & RT_MODEF_PROGRESSIVE)) iteration_ += spp;
     update();
@@ -660,60 +635,21 @@ void RenderState::reset_iteration()
     update();
 }
 
-std::vector<float> RenderState::frame() const
+std::vector<float> RenderState::frame() const { return accum_.download("download frame"); }
+std::vector<uint32_t> RenderState::hit_ids() const { return ids_.download("download ids"); }
+
+// a float4 frame on the device as the sRGB surface would hold it (rt_frame_rgba8_mode)
+static std::vector<uint8_t> rgba8_of(const GpuHandles& gpu, rt_mode mode, const DeviceArray<float>& frame, const char* what)
 {
-    std::vector<float> out((size_t)width_ * height_ * 4);
-    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), out.data(), accum_, out.size() * 4), "download frame");
-    return out;
+    const DeviceArray<uint8_t> img(gpu, frame.size(), what);
+    gpu.check(rt_frame_rgba8_mode(gpu.ctx(), mode, frame.get(), (uint32_t)(frame.size() / 4), img.get()), what);
+    return img.download(what);
 }
 
-std::vector<uint32_t> RenderState::hit_ids() const
-{
-    std::vector<uint32_t> out((size_t)width_ * height_);
-    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), out.data(), ids_, out.size() * 4), "download ids");
-    return out;
-}
+std::vector<uint8_t> RenderState::frame_rgba8() const { return rgba8_of(gpu_, mode(), accum_, "frame_rgba8"); }
 
-std::vector<uint8_t> RenderState::frame_rgba8() const
-{
-    const size_t npx = (size_t)width_ * height_;
-    void* d = nullptr;
-    gpu_.check(rt_device_alloc(gpu_.ctx(), npx * 4, &d), "frame buffer");
-    std::vector<uint8_t> out(npx * 4);
-    int rc = rt_frame_rgba8_mode(gpu_.ctx(), mode(), static_cast<const float*>(accum_), (uint32_t)npx,
-                                 static_cast<uint8_t*>(d));
-    if (rc == RT_OK) rc = rt_memcpy_to_host(gpu_.ctx(), out.data(), d, out.size());
-    rt_device_free(gpu_.ctx(), d);
-    gpu_.check(rc, "frame_rgba8");
-    return out;
-}
-
-// The float4 frame d on the device (freed here, whatever happens), downloaded as it is ...
-static std::vector<float> take_frame(const GpuHandles& gpu, void* d, size_t npx, const char* what)
-{
-    std::vector<float> out(npx * 4);
-    const int rc = rt_memcpy_to_host(gpu.ctx(), out.data(), d, out.size() * 4);
-    rt_device_free(gpu.ctx(), d);
-    gpu.check(rc, what);
-    return out;
-}
-// ... or as the sRGB surface would hold it (rt_frame_rgba8_mode)
-static std::vector<uint8_t> take_rgba8(const GpuHandles& gpu, rt_mode mode, void* d, size_t npx, const char* what)
-{
-    void* img = nullptr;
-    int rc = rt_device_alloc(gpu.ctx(), npx * 4, &img);
-    std::vector<uint8_t> out(npx * 4);
-    if (rc == RT_OK)
-        rc = rt_frame_rgba8_mode(gpu.ctx(), mode, static_cast<const float*>(d), (uint32_t)npx, static_cast<uint8_t*>(img));
-    if (rc == RT_OK) rc = rt_memcpy_to_host(gpu.ctx(), out.data(), img, out.size());
-    rt_device_free(gpu.ctx(), img);
-    rt_device_free(gpu.ctx(), d);
-    gpu.check(rc, what);
-    return out;
-}
-
-// the denoised frame on the device (the caller frees it)
-void* RenderState::denoise_device(uint32_t levels, float sigma_l, float sigma_z) const
+// the denoised frame on the device
+DeviceArray<float> RenderState::denoise_device(uint32_t levels, float sigma_l, float sigma_z) const
 {
     if (tiled_) throw Error(RT_E_UNSUPPORTED, "denoise is for an untiled state: the filter needs every pixel's neighbours, and a tiled render (set_tiling, any rank count) keeps its buffers packed per tile");
     if (!writes_records(row_)) throw Error(RT_E_UNSUPPORTED, "denoise: the mode keeps no noise state");
@@ -721,26 +657,21 @@ void* RenderState::denoise_device(uint32_t levels, float sigma_l, float sigma_z)
     if (iteration_ < 2) throw Error(RT_E_INVALID, "denoise: the variance needs at least 2 rendered iterations");
     if (levels < 1 || levels > 5 || !(sigma_l > 0.0f) || !(sigma_z > 0.0f))
         throw Error(RT_E_INVALID, "denoise: levels in 1..5, sigmas > 0");
-    const size_t npx = (size_t)width_ * height_;
-    void* d = nullptr;
-    gpu_.check(rt_device_alloc(gpu_.ctx(), npx * 16, &d), "denoise buffer");
-    const int rc = rt_denoise(gpu_.ctx(), width_, height_, static_cast<const float*>(accum_),
-                              static_cast<const uint32_t*>(ids_), static_cast<const rt_noise_state*>(noise_),
-                              static_cast<const uint32_t*>(counts_), iteration_, levels, sigma_l, sigma_z,
-                              static_cast<float*>(d));
-    if (rc != RT_OK) rt_device_free(gpu_.ctx(), d);
-    gpu_.check(rc, "denoise");
+    DeviceArray<float> d(gpu_, accum_.size(), "denoise buffer");
+    gpu_.check(rt_denoise(gpu_.ctx(), width_, height_, accum_.get(), ids_.get(), noise_.get(), counts_.get(), iteration_,
+                          levels, sigma_l, sigma_z, d.get()),
+               "denoise");
     return d;
 }
 
 std::vector<float> RenderState::denoise(uint32_t levels, float sigma_l, float sigma_z) const
 {
-    return take_frame(gpu_, denoise_device(levels, sigma_l, sigma_z), (size_t)width_ * height_, "denoise");
+    return denoise_device(levels, sigma_l, sigma_z).download("denoise");
 }
 
 std::vector<uint8_t> RenderState::denoised_rgba8(uint32_t levels, float sigma_l, float sigma_z) const
 {
-    return take_rgba8(gpu_, mode(), denoise_device(levels, sigma_l, sigma_z), (size_t)width_ * height_, "denoised_rgba8");
+    return rgba8_of(gpu_, mode(), denoise_device(levels, sigma_l, sigma_z), "denoised_rgba8");
 }
 
 // ---- temporal accumulation (rt.h "temporal accumulation")
@@ -756,22 +687,22 @@ void RenderState::enable_temporal(uint32_t max_history, float normal_min, float 
     if (max_history < 1 || min_len < 1 || !(plane_tol >= 0.0f) || normal_min != normal_min)
         throw Error(RT_E_INVALID, "enable_temporal: max_history and min_len >= 1, plane_tol >= 0, normal_min a number");
     disable_temporal();
-    rt_ctx* c = gpu_.ctx();
     const size_t npx = (size_t)width_ * height_;
-    try {
-        gpu_.check(rt_device_alloc(c, npx * 16, &tp_cur_), "temporal frame buffer");
-        gpu_.check(rt_device_alloc(c, npx * 4, &tp_ids_), "temporal id buffer");
-        gpu_.check(rt_device_alloc(c, npx * 8, &tp_dz_), "temporal guide buffer");
-        for (TemporalSet& s : tp_set_) {
-            gpu_.check(rt_device_alloc(c, npx * 16, &s.color), "temporal history colour");
-            gpu_.check(rt_device_alloc(c, npx * 8, &s.mom), "temporal history moments");
-            gpu_.check(rt_device_alloc(c, npx * 4, &s.len), "temporal history length");
-            gpu_.check(rt_device_alloc(c, npx * 16, &s.nz), "temporal history guide");
-        }
-    } catch (...) {
-        disable_temporal();   // a failed allocation leaves the state off, with nothing held
-        throw;
+    // into locals: a failed allocation leaves the state off, with nothing held
+    DeviceArray<float> cur(gpu_, npx * 4, "temporal frame buffer");
+    DeviceArray<uint32_t> ids(gpu_, npx, "temporal id buffer");
+    DeviceArray<float> dz(gpu_, npx * 2, "temporal guide buffer");
+    TemporalSet set[2];
+    for (TemporalSet& s : set) {
+        s.color = DeviceArray<float>(gpu_, npx * 4, "temporal history colour");
+        s.mom = DeviceArray<float>(gpu_, npx * 2, "temporal history moments");
+        s.len = DeviceArray<uint32_t>(gpu_, npx, "temporal history length");
+        s.nz = DeviceArray<float>(gpu_, npx * 4, "temporal history guide");
     }
+    tp_cur_ = std::move(cur);
+    tp_ids_ = std::move(ids);
+    tp_dz_ = std::move(dz);
+    for (int i = 0; i < 2; i++) tp_set_[i] = std::move(set[i]);
     temporal_ = true;
     tp_max_history_ = max_history;
     tp_normal_min_ = normal_min;
@@ -783,13 +714,10 @@ void RenderState::enable_temporal(uint32_t max_history, float normal_min, float 
 
 void RenderState::disable_temporal()
 {
-    rt_ctx* c = gpu_.ctx();
-    void** const bufs[] = {&tp_cur_,          &tp_ids_,        &tp_dz_,         &tp_set_[0].color, &tp_set_[0].mom, &tp_set_[0].len,
-                           &tp_set_[0].nz,    &tp_set_[1].color, &tp_set_[1].mom, &tp_set_[1].len,   &tp_set_[1].nz};
-    for (void** b : bufs) {
-        if (*b) rt_device_free(c, *b);
-        *b = nullptr;
-    }
+    tp_cur_.reset();
+    tp_ids_.reset();
+    tp_dz_.reset();
+    for (TemporalSet& s : tp_set_) s = TemporalSet{};
     temporal_ = false;
     tp_latest_ = -1;
 }
@@ -800,33 +728,28 @@ void RenderState::temporal_step(uint32_t spp)
     if (!temporal_) throw Error(RT_E_NOT_READY, "temporal_step: enable_temporal() first");
     if (spp < 1) throw Error(RT_E_INVALID, "temporal_step: spp must be at least 1");
     rt_ctx* c = gpu_.ctx();
-    const size_t npx = (size_t)width_ * height_;
-    gpu_.check(rt_memset_device(c, tp_cur_, 0, npx * 16), "clear temporal frame");
-    // the frame is not the progressive render's: its noise state and counts stay as they are
-    if (counts_) gpu_.check(rt_set_adaptive(c, nullptr, 0.0f, 0.0f, 0, 0), "set adaptive");
-    if (noise_) gpu_.check(rt_set_noise_buffer(c, nullptr), "set noise buffer");
+    tp_cur_.zero("clear temporal frame");
+    // the frame is not the progressive render's: its noise state and counts stay as they are.  Both
+    // registrations come back whatever happened, and the first failure is the one reported
+    int rc = RT_OK;
+    const auto then = [&rc](int r) { rc = rc == RT_OK ? r : rc; };
+    if (counts_) rc = rt_set_adaptive(c, nullptr, 0.0f, 0.0f, 0, 0);
+    if (noise_) then(rt_set_noise_buffer(c, nullptr));
     const rt_tile region{0, 0, width_, height_};
-    const int rc = rt_render(c, mode(), trav_, &region, tp_k_, spp, static_cast<float*>(tp_cur_),
-                             static_cast<uint32_t*>(tp_ids_), nullptr);
-    if (noise_) gpu_.check(rt_set_noise_buffer(c, static_cast<rt_noise_state*>(noise_)), "set noise buffer");
-    if (counts_)
-        gpu_.check(rt_set_adaptive(c, static_cast<uint32_t*>(counts_), ad_target_, ad_floor_, ad_min_, ad_vote_), "set adaptive");
+    if (rc == RT_OK) rc = rt_render(c, mode(), trav_, &region, tp_k_, spp, tp_cur_.get(), tp_ids_.get(), nullptr);
+    if (noise_) then(rt_set_noise_buffer(c, noise_.get()));
+    if (counts_) then(rt_set_adaptive(c, counts_.get(), ad_target_, ad_floor_, ad_min_, ad_vote_));
     gpu_.check(rc, "temporal render");
+    // an empty set's buffers are null: the first frame has no history
+    const TemporalSet none, &old = tp_latest_ < 0 ? none : tp_set_[tp_latest_];
     const TemporalSet& out = tp_set_[tp_latest_ < 0 ? 0 : 1 - tp_latest_];
     // the guide of the camera that rendered the frame: before update() moves it
-    gpu_.check(rt_denoise_guide(c, width_, height_, static_cast<const uint32_t*>(tp_ids_), static_cast<float*>(out.nz),
-                                static_cast<float*>(tp_dz_)),
-               "temporal guide");
-    const TemporalSet* old = tp_latest_ < 0 ? nullptr : &tp_set_[tp_latest_];
+    gpu_.check(rt_denoise_guide(c, width_, height_, tp_ids_.get(), out.nz.get(), tp_dz_.get()), "temporal guide");
     const float scale = (float)(tp_k_ + spp) / (float)spp;
-    gpu_.check(rt_temporal_accumulate(c, width_, height_, static_cast<const float*>(tp_cur_), scale,
-                                      static_cast<const float*>(out.nz), old ? &tp_uniform_ : nullptr,
-                                      old ? static_cast<const float*>(old->color) : nullptr,
-                                      old ? static_cast<const float*>(old->mom) : nullptr,
-                                      old ? static_cast<const uint32_t*>(old->len) : nullptr,
-                                      old ? static_cast<const float*>(old->nz) : nullptr, tp_max_history_, tp_normal_min_,
-                                      tp_plane_tol_, static_cast<float*>(out.color), static_cast<float*>(out.mom),
-                                      static_cast<uint32_t*>(out.len)),
+    gpu_.check(rt_temporal_accumulate(c, width_, height_, tp_cur_.get(), scale, out.nz.get(),
+                                      tp_latest_ < 0 ? nullptr : &tp_uniform_, old.color.get(), old.mom.get(), old.len.get(),
+                                      old.nz.get(), tp_max_history_, tp_normal_min_, tp_plane_tol_, out.color.get(),
+                                      out.mom.get(), out.len.get()),
                "temporal accumulate");
     tp_latest_ = tp_latest_ < 0 ? 0 : 1 - tp_latest_;
     tp_uniform_ = uniform_;
@@ -834,8 +757,8 @@ void RenderState::temporal_step(uint32_t spp)
     update();
 }
 
-// the filtered latest frame on the device (the caller frees it)
-void* RenderState::temporal_device(uint32_t levels, float sigma_l, float sigma_z) const
+// the filtered latest frame on the device
+DeviceArray<float> RenderState::temporal_device(uint32_t levels, float sigma_l, float sigma_z) const
 {
     if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("temporal_frame") + kTemporalUntiled);
     if (!temporal_ || tp_latest_ < 0) throw Error(RT_E_NOT_READY, "temporal_frame: enable_temporal() and temporal_step() first");
@@ -844,59 +767,46 @@ void* RenderState::temporal_device(uint32_t levels, float sigma_l, float sigma_z
     rt_ctx* c = gpu_.ctx();
     const size_t npx = (size_t)width_ * height_;
     const TemporalSet& s = tp_set_[tp_latest_];
-    void *var = nullptr, *d = nullptr;
-    gpu_.check(rt_device_alloc(c, npx * 4, &var), "temporal variance buffer");
-    int rc = rt_device_alloc(c, npx * 16, &d);
-    if (rc == RT_OK)
-        rc = rt_temporal_variance(c, width_, height_, static_cast<const float*>(s.mom), static_cast<const uint32_t*>(s.len),
-                                  static_cast<const float*>(s.nz), static_cast<const float*>(tp_dz_), tp_min_len_,
-                                  tp_normal_min_, tp_plane_tol_, static_cast<float*>(var));
-    if (rc == RT_OK)
-        rc = rt_denoise_filter(c, width_, height_, static_cast<const float*>(s.color), static_cast<const float*>(var),
-                               static_cast<const float*>(s.nz), static_cast<const float*>(tp_dz_), levels, sigma_l, sigma_z,
-                               static_cast<float*>(d), nullptr);
-    if (rc == RT_OK) rc = rt_synchronize(c);
-    rt_device_free(c, var);
-    if (rc != RT_OK && d) rt_device_free(c, d);
-    gpu_.check(rc, "temporal_frame");
+    const DeviceArray<float> var(gpu_, npx, "temporal variance buffer");
+    DeviceArray<float> d(gpu_, npx * 4, "temporal_frame");
+    gpu_.check(rt_temporal_variance(c, width_, height_, s.mom.get(), s.len.get(), s.nz.get(), tp_dz_.get(), tp_min_len_,
+                                    tp_normal_min_, tp_plane_tol_, var.get()),
+               "temporal_frame");
+    gpu_.check(rt_denoise_filter(c, width_, height_, s.color.get(), var.get(), s.nz.get(), tp_dz_.get(), levels, sigma_l,
+                                 sigma_z, d.get(), nullptr),
+               "temporal_frame");
+    gpu_.check(rt_synchronize(c), "temporal_frame");   // the filter reads var, which goes here
     return d;
 }
 
 std::vector<float> RenderState::temporal_frame(uint32_t levels, float sigma_l, float sigma_z) const
 {
-    return take_frame(gpu_, temporal_device(levels, sigma_l, sigma_z), (size_t)width_ * height_, "temporal_frame");
+    return temporal_device(levels, sigma_l, sigma_z).download("temporal_frame");
 }
 
 std::vector<uint8_t> RenderState::temporal_rgba8(uint32_t levels, float sigma_l, float sigma_z) const
 {
-    return take_rgba8(gpu_, mode(), temporal_device(levels, sigma_l, sigma_z), (size_t)width_ * height_, "temporal_rgba8");
+    return rgba8_of(gpu_, mode(), temporal_device(levels, sigma_l, sigma_z), "temporal_rgba8");
 }
 
 RenderState::TemporalCurrent RenderState::temporal_current() const
 {
     if (!temporal_ || tp_latest_ < 0) throw Error(RT_E_NOT_READY, "temporal_current: enable_temporal() and temporal_step() first");
-    const size_t npx = (size_t)width_ * height_;
     TemporalCurrent cur;
-    cur.accum.resize(npx * 4);
-    cur.ids.resize(npx);
+    cur.accum = tp_cur_.download("download temporal frame");
+    cur.ids = tp_ids_.download("download temporal ids");
     cur.uniform = tp_uniform_;
-    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), cur.accum.data(), tp_cur_, npx * 16), "download temporal frame");
-    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), cur.ids.data(), tp_ids_, npx * 4), "download temporal ids");
     return cur;
 }
 
 RenderState::TemporalHistory RenderState::temporal_history() const
 {
     if (!temporal_ || tp_latest_ < 0) throw Error(RT_E_NOT_READY, "temporal_history: enable_temporal() and temporal_step() first");
-    const size_t npx = (size_t)width_ * height_;
     const TemporalSet& s = tp_set_[tp_latest_];
     TemporalHistory h;
-    h.color.resize(npx * 4);
-    h.moments.resize(npx * 2);
-    h.length.resize(npx);
-    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), h.color.data(), s.color, npx * 16), "download temporal colour");
-    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), h.moments.data(), s.mom, npx * 8), "download temporal moments");
-    gpu_.check(rt_memcpy_to_host(gpu_.ctx(), h.length.data(), s.len, npx * 4), "download temporal length");
+    h.color = s.color.download("download temporal colour");
+    h.moments = s.mom.download("download temporal moments");
+    h.length = s.len.download("download temporal length");
     return h;
 }
 

@@ -76,6 +76,7 @@
 #include <sstream>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "raytracer.hpp"
@@ -169,21 +170,84 @@ static std::string default_models_dir(const char* argv0)
     return dir + "/../../assets/models";
 }
 
+// the command line: bare flags and `--name value` pairs; numbers as atoi / atof read them (garbage is 0)
+struct Args {
+    std::vector<std::string> words;
+    bool has(const std::string& name) const   // the flag is there
+    {
+        for (const auto& s : words)
+            if (s == name) return true;
+        return false;
+    }
+    const std::string* str(const std::string& name) const   // the word after `name`, null without one
+    {
+        for (size_t i = 0; i + 1 < words.size(); i++)
+            if (words[i] == name) return &words[i + 1];
+        return nullptr;
+    }
+    template <class T>
+    T num(const std::string& name, T otherwise) const
+    {
+        const std::string* s = str(name);
+        if (!s) return otherwise;
+        if constexpr (std::is_floating_point_v<T>) return (T)std::atof(s->c_str());
+        else return (T)std::atoi(s->c_str());
+    }
+    std::optional<std::pair<uint32_t, uint32_t>> size(const std::string& name) const   // `name WxH`
+    {
+        const std::string* s = str(name);
+        if (!s) return std::nullopt;
+        unsigned w = 0, h = 0;
+        if (std::sscanf(s->c_str(), "%ux%u", &w, &h) != 2) throw Error(RT_E_INVALID, name + " WxH");
+        return std::make_pair((uint32_t)w, (uint32_t)h);
+    }
+};
+
+// `file_option FILE` with `size_option WxH`: the file's raw RGBA8 texels to set(texels, width, height)
+template <class Set>
+static void read_rgba(const Args& args, const std::string& file_option, const std::string& size_option, Set set)
+{
+    const std::string* path = args.str(file_option);
+    if (!path) return;
+    const auto size = args.size(size_option);
+    if (!size) throw Error(RT_E_INVALID, file_option + " needs " + size_option + " WxH");
+    std::vector<uint8_t> texels((size_t)size->first * size->second * 4);
+    std::ifstream f(*path, std::ios::binary);
+    f.read(reinterpret_cast<char*>(texels.data()), (std::streamsize)texels.size());
+    if (!f) throw Error(RT_E_INVALID, "cannot read " + *path);
+    set(texels.data(), size->first, size->second);
+}
+
+// What is for an untiled state: the noise estimate and the counts are H x W maps, the filters need
+// every pixel's neighbours, and --comm-file tiles the render for any rank count (--nranks 1 too),
+// which packs the buffers per tile.  A row: the option, whether it is a bare flag, and who the
+// refusal names for it.  The estimates' rows are checked before the options' consistency, the
+// filters' rows after it.
+static const struct {
+    const char* option;
+    bool flag;
+    const char* who;
+} kUntiled[] = {{"--noise-target", false, "--noise-target does"},
+                {"--adaptive-target", false, "--adaptive-target / --adaptive-min / --adaptive-vote do"},
+                {"--adaptive-min", false, "--adaptive-target / --adaptive-min / --adaptive-vote do"},
+                {"--adaptive-vote", false, "--adaptive-target / --adaptive-min / --adaptive-vote do"},
+                {"--denoise", true, "--denoise does"},
+                {"--temporal-frames", false, "--temporal-frames does"}};
+enum { kUntiledEstimates = 0, kUntiledFilters = 4, kUntiledEnd = 6 };
+
+static void refuse_tiled(const Args& args, int from, int to)
+{
+    if (args.num<uint32_t>("--nranks", 1) <= 1 && !args.str("--comm-file")) return;
+    for (int i = from; i < to; i++)
+        if (kUntiled[i].flag ? args.has(kUntiled[i].option) : args.str(kUntiled[i].option) != nullptr)
+            throw Error(RT_E_UNSUPPORTED, std::string(kUntiled[i].who) + " not go with --comm-file / --nranks (a tiled render)");
+}
+
 int main(int argc, char** argv)
 {
     try {
-        std::vector<std::string> a(argv + 1, argv + argc);
-        auto arg = [&](const std::string& name) -> const std::string* {
-            for (size_t i = 0; i + 1 < a.size(); i++)
-                if (a[i] == name) return &a[i + 1];
-            return nullptr;
-        };
-        auto flag = [&](const std::string& name) {
-            for (const auto& s : a)
-                if (s == name) return true;
-            return false;
-        };
-        if (flag("--list-scenes")) {
+        const Args args{std::vector<std::string>(argv + 1, argv + argc)};
+        if (args.has("--list-scenes")) {
             for (const auto& s : get_scenes()) {
                 const char* m = mode_name(s.mode());
                 const char* rm = mode_name(s.render_mode());
@@ -205,7 +269,7 @@ int main(int argc, char** argv)
             }
             return 0;
         }
-        if (const std::string* k = arg("--camera-test")) {
+        if (const std::string* k = args.str("--camera-test")) {
             CameraController ctl;
             for (const auto& name : split(*k, ',')) ctl.handle_camera_commands(key_from_name(name), true);
             Camera c;
@@ -214,147 +278,110 @@ int main(int argc, char** argv)
             std::printf("%s\n", cam_json(c).c_str());
             return 0;
         }
-        if (const std::string* sd = arg("--jitter")) {
-            const uint32_t subdiv = (uint32_t)std::atoi(sd->c_str());
+        if (args.str("--jitter")) {
             const double h = argc > 3 ? std::atof(argv[3]) : 512.0;
-            for (const auto& j : compute_jitters(1.0 / h, subdiv)) std::printf("%s %s\n", hexf(j[0]).c_str(), hexf(j[1]).c_str());
+            for (const auto& j : compute_jitters(1.0 / h, args.num<uint32_t>("--jitter", 0)))
+                std::printf("%s %s\n", hexf(j[0]).c_str(), hexf(j[1]).c_str());
             return 0;
         }
-        const std::string* name = arg("--scene");
+        const std::string* name = args.str("--scene");
         if (!name) {
             std::fprintf(stderr, "usage: rt_render --list-scenes | --scene NAME [options] (see the source header)\n");
             return 2;
         }
         RenderOptions opt;
-        opt.models_dir = arg("--models") ? *arg("--models") : default_models_dir(argv[0]);
-        if (const std::string* r = arg("--res")) {
-            unsigned w = 0, h = 0;
-            if (std::sscanf(r->c_str(), "%ux%u", &w, &h) != 2) throw Error(RT_E_INVALID, "--res WxH");
-            opt.resolution = std::make_pair(w, h);
-        }
-        opt.device_build = flag("--device-build");
-        const uint32_t nranks = arg("--nranks") ? (uint32_t)std::atoi(arg("--nranks")->c_str()) : 1;
-        const uint32_t rank = arg("--rank") ? (uint32_t)std::atoi(arg("--rank")->c_str()) : 0;
+        opt.models_dir = args.str("--models") ? *args.str("--models") : default_models_dir(argv[0]);
+        opt.resolution = args.size("--res");
+        opt.device_build = args.has("--device-build");
+        const uint32_t nranks = args.num<uint32_t>("--nranks", 1), rank = args.num<uint32_t>("--rank", 0);
         if (nranks == 0 || rank >= nranks) throw Error(RT_E_INVALID, "--rank must be below --nranks");
-        if (nranks > 1 && !arg("--comm-file")) throw Error(RT_E_INVALID, "--nranks needs --comm-file PATH");
-        // the noise estimate is for an untiled state: --comm-file tiles the render for any rank count
-        // (--nranks 1 too), and its states would be packed per tile, not the H x W map
-        if (arg("--noise-target") && (nranks > 1 || arg("--comm-file")))
-            throw Error(RT_E_UNSUPPORTED, "--noise-target does not go with --comm-file / --nranks (a tiled render)");
-        const bool adaptive = arg("--adaptive-target") || arg("--adaptive-min") || arg("--adaptive-vote");
-        if (adaptive && (nranks > 1 || arg("--comm-file")))
-            throw Error(RT_E_UNSUPPORTED,
-                        "--adaptive-target / --adaptive-min / --adaptive-vote do not go with --comm-file / --nranks (a tiled render)");
-        if (adaptive && !arg("--adaptive-target")) throw Error(RT_E_INVALID, "--adaptive-min / --adaptive-vote need --adaptive-target T");
-        if (adaptive && arg("--noise-target")) throw Error(RT_E_INVALID, "--adaptive-target does not go with --noise-target");
-        // the denoise filter needs every pixel's neighbours and a noise state: an untiled render of a path mode
-        const bool denoise = flag("--denoise");
-        if (!denoise && (arg("--denoise-levels") || arg("--denoise-sigma-l") || arg("--denoise-sigma-z")))
+        if (nranks > 1 && !args.str("--comm-file")) throw Error(RT_E_INVALID, "--nranks needs --comm-file PATH");
+        const bool noise = args.str("--noise-target"), adaptive = args.str("--adaptive-target");
+        refuse_tiled(args, kUntiledEstimates, kUntiledFilters);
+        if (!adaptive && (args.str("--adaptive-min") || args.str("--adaptive-vote")))
+            throw Error(RT_E_INVALID, "--adaptive-min / --adaptive-vote need --adaptive-target T");
+        if (adaptive && noise) throw Error(RT_E_INVALID, "--adaptive-target does not go with --noise-target");
+        // the denoise filter needs a noise state: a path mode
+        const bool denoise = args.has("--denoise"), temporal = args.str("--temporal-frames");
+        if (!denoise && (args.str("--denoise-levels") || args.str("--denoise-sigma-l") || args.str("--denoise-sigma-z")))
             throw Error(RT_E_INVALID, "--denoise-levels / --denoise-sigma-l / --denoise-sigma-z need --denoise");
-        if (denoise && (nranks > 1 || arg("--comm-file")))
-            throw Error(RT_E_UNSUPPORTED, "--denoise does not go with --comm-file / --nranks (a tiled render)");
-        const uint32_t dn_levels = arg("--denoise-levels") ? (uint32_t)std::atoi(arg("--denoise-levels")->c_str()) : 5u;
-        const float dn_sigma_l = arg("--denoise-sigma-l") ? (float)std::atof(arg("--denoise-sigma-l")->c_str()) : 4.0f;
-        const float dn_sigma_z = arg("--denoise-sigma-z") ? (float)std::atof(arg("--denoise-sigma-z")->c_str()) : 1.0f;
+        refuse_tiled(args, kUntiledFilters, kUntiledEnd);
+        const auto path_scene = [&] {
+            const auto row = mode_of_shader(find_scene(*name).shader);
+            return row && row->family == RT_FAMILY_PATH;
+        };
+        const uint32_t dn_levels = args.num<uint32_t>("--denoise-levels", 5);
+        const float dn_sigma_l = args.num<float>("--denoise-sigma-l", 4.0f), dn_sigma_z = args.num<float>("--denoise-sigma-z", 1.0f);
         if (denoise) {
             if (dn_levels < 1 || dn_levels > 5 || !(dn_sigma_l > 0.0f) || !(dn_sigma_z > 0.0f))
                 throw Error(RT_E_INVALID, "--denoise-levels in 1..5, --denoise-sigma-l and --denoise-sigma-z > 0");
-            const auto row = mode_of_shader(find_scene(*name).shader);
-            if (!row || row->family != RT_FAMILY_PATH)
-                throw Error(RT_E_UNSUPPORTED, "--denoise: the scene's mode keeps no noise state (a path mode only)");
+            if (!path_scene()) throw Error(RT_E_UNSUPPORTED, "--denoise: the scene's mode keeps no noise state (a path mode only)");
         }
         // temporal accumulation reprojects between whole frames of a path mode, one camera move per frame
-        const bool temporal = arg("--temporal-frames") != nullptr;
-        if (!temporal && (arg("--temporal-history") || arg("--temporal-normal-min") || arg("--temporal-plane-tol")))
+        if (!temporal && (args.str("--temporal-history") || args.str("--temporal-normal-min") || args.str("--temporal-plane-tol")))
             throw Error(RT_E_INVALID, "--temporal-history / --temporal-normal-min / --temporal-plane-tol need --temporal-frames N");
-        if (temporal && (nranks > 1 || arg("--comm-file")))
-            throw Error(RT_E_UNSUPPORTED, "--temporal-frames does not go with --comm-file / --nranks (a tiled render)");
-        if (temporal && (arg("--noise-target") || arg("--adaptive-target") || arg("--samples")))
+        if (temporal && (noise || adaptive || args.str("--samples")))
             throw Error(RT_E_INVALID, "--temporal-frames does not go with --noise-target, --adaptive-target or --samples");
-        const int tp_frames = temporal ? std::atoi(arg("--temporal-frames")->c_str()) : 0;
-        const int tp_history = arg("--temporal-history") ? std::atoi(arg("--temporal-history")->c_str()) : 32;
-        const float tp_normal_min = arg("--temporal-normal-min") ? (float)std::atof(arg("--temporal-normal-min")->c_str()) : 0.9f;
-        const float tp_plane_tol = arg("--temporal-plane-tol") ? (float)std::atof(arg("--temporal-plane-tol")->c_str()) : 0.01f;
+        const int tp_frames = args.num<int>("--temporal-frames", 0), tp_history = args.num<int>("--temporal-history", 32);
+        const float tp_normal_min = args.num<float>("--temporal-normal-min", 0.9f);
+        const float tp_plane_tol = args.num<float>("--temporal-plane-tol", 0.01f);
         if (temporal) {
             if (tp_frames < 1 || tp_history < 1 || !(tp_plane_tol >= 0.0f) || tp_normal_min != tp_normal_min)
                 throw Error(RT_E_INVALID, "--temporal-frames and --temporal-history >= 1, --temporal-plane-tol >= 0");
-            if (arg("--spp") && std::atoi(arg("--spp")->c_str()) < 1) throw Error(RT_E_INVALID, "--temporal-frames: --spp >= 1");
-            const auto row = mode_of_shader(find_scene(*name).shader);
-            if (!row || row->family != RT_FAMILY_PATH)
+            if (args.num<int>("--spp", 1) < 1) throw Error(RT_E_INVALID, "--temporal-frames: --spp >= 1");
+            if (!path_scene())
                 throw Error(RT_E_UNSUPPORTED, "--temporal-frames: the scene's mode writes no per-iteration records (a path mode only)");
         }
         int vote = RT_ADAPT_TILE;
-        if (const std::string* v = arg("--adaptive-vote")) {
+        if (const std::string* v = args.str("--adaptive-vote")) {
             if (*v == "pixel") vote = RT_ADAPT_PIXEL;
             else if (*v != "tile") throw Error(RT_E_INVALID, "--adaptive-vote pixel|tile");
         }
-        GpuHandles gpu(arg("--device") ? std::atoi(arg("--device")->c_str()) : (int)rank);
+        GpuHandles gpu(args.num<int>("--device", (int)rank));
         RenderState rs(gpu, find_scene(*name), opt);
-        if (const std::string* cf = arg("--comm-file")) {
+        if (const std::string* cf = args.str("--comm-file")) {
             uint8_t id[RT_COMM_ID_BYTES];
             const char* et = std::getenv("RT_COMM_TOKEN");
-            const std::string token = arg("--comm-token") ? *arg("--comm-token") : (et ? et : "");
+            const std::string token = args.str("--comm-token") ? *args.str("--comm-token") : (et ? et : "");
             publish_comm_id(*cf, token, id, rank);
             rs.set_tiling(nranks, rank, id);
         }
-        std::vector<uint8_t> env;
-        if (const std::string* ef = arg("--env-rgba")) {
-            unsigned w = 0, h = 0;
-            if (!arg("--env-size") || std::sscanf(arg("--env-size")->c_str(), "%ux%u", &w, &h) != 2)
-                throw Error(RT_E_INVALID, "--env-rgba needs --env-size WxH");
-            std::ifstream f(*ef, std::ios::binary);
-            env.resize((size_t)w * h * 4);
-            f.read(reinterpret_cast<char*>(env.data()), (std::streamsize)env.size());
-            if (!f) throw Error(RT_E_INVALID, "cannot read " + *ef);
-            rs.set_environment_map(env.data(), w, h);
-        }
-        std::vector<uint8_t> tex;
-        if (const std::string* tf = arg("--tex-rgba")) {
-            unsigned w = 0, h = 0;
-            if (!arg("--tex-size") || std::sscanf(arg("--tex-size")->c_str(), "%ux%u", &w, &h) != 2)
-                throw Error(RT_E_INVALID, "--tex-rgba needs --tex-size WxH");
-            std::ifstream f(*tf, std::ios::binary);
-            tex.resize((size_t)w * h * 4);
-            f.read(reinterpret_cast<char*>(tex.data()), (std::streamsize)tex.size());
-            if (!f) throw Error(RT_E_INVALID, "cannot read " + *tf);
-            rs.set_texture_image(tex.data(), w, h);
-        }
-        if (const std::string* s = arg("--selection")) rs.set_selection1((uint32_t)std::atoi(s->c_str()));
-        if (const std::string* s = arg("--selection2")) rs.set_other_material((uint32_t)std::atoi(s->c_str()));
-        if (arg("--use-texture") || arg("--uv-scale")) {
+        read_rgba(args, "--env-rgba", "--env-size", [&](const uint8_t* p, uint32_t w, uint32_t h) { rs.set_environment_map(p, w, h); });
+        read_rgba(args, "--tex-rgba", "--tex-size", [&](const uint8_t* p, uint32_t w, uint32_t h) { rs.set_texture_image(p, w, h); });
+        if (args.str("--selection")) rs.set_selection1(args.num<uint32_t>("--selection", 0));
+        if (args.str("--selection2")) rs.set_other_material(args.num<uint32_t>("--selection2", 0));
+        if (args.str("--use-texture") || args.str("--uv-scale")) {
             float a = 1.0f, b = 1.0f;
-            if (const std::string* s = arg("--uv-scale"))
+            if (const std::string* s = args.str("--uv-scale"))
                 if (std::sscanf(s->c_str(), "%f,%f", &a, &b) != 2) throw Error(RT_E_INVALID, "--uv-scale A,B");
-            rs.set_texture(arg("--use-texture") ? (uint32_t)std::atoi(arg("--use-texture")->c_str()) : 0u, {a, b});
+            rs.set_texture(args.num<uint32_t>("--use-texture", 0), {a, b});
         }
-        if (const std::string* s = arg("--subdiv")) rs.set_subdivision_level((uint32_t)std::atoi(s->c_str()));
-        if (const std::string* s = arg("--camera-constant")) rs.update_camera_constant((float)std::atof(s->c_str()));
-        if (const std::string* k = arg("--keys")) {
+        if (args.str("--subdiv")) rs.set_subdivision_level(args.num<uint32_t>("--subdiv", 0));
+        if (args.str("--camera-constant")) rs.update_camera_constant(args.num<float>("--camera-constant", 0.0f));
+        if (const std::string* k = args.str("--keys")) {
             for (const auto& kn : split(*k, ',')) rs.input_alt(key_from_name(kn), true);
-            const int n = arg("--updates") ? std::atoi(arg("--updates")->c_str()) : 1;
+            const int n = args.num<int>("--updates", 1);
             for (int i = 0; i < n; i++) rs.update();
         } else {
             rs.update();
         }
         // --denoise: the noise estimate from iteration 0 on, unless --noise-target / --adaptive-target enable it
         // (with --temporal-frames it only carries the filter's parameters: no progressive frame is rendered)
-        if (denoise && !temporal && !arg("--noise-target") && !arg("--adaptive-target")) rs.enable_noise();
+        if (denoise && !temporal && !noise && !adaptive) rs.enable_noise();
         uint32_t frames = 0;
         std::string noise_json;
-        if (const std::string* t = arg("--noise-target")) {   // render until converged (render_until)
-            const uint32_t cap = arg("--samples") ? (uint32_t)std::atoi(arg("--samples")->c_str())
-                                 : arg("--spp")   ? (uint32_t)std::atoi(arg("--spp")->c_str())
-                                                  : 1024u;
-            const uint32_t batch = arg("--noise-batch") ? (uint32_t)std::atoi(arg("--noise-batch")->c_str()) : 16u;
-            const double allow = arg("--noise-allow") ? std::atof(arg("--noise-allow")->c_str()) : 0.0;
+        const std::string* const out = args.str("--out");
+        // --noise-target and --adaptive-target: at most `cap` iterations, `batch` at a time
+        const uint32_t cap = args.num<uint32_t>("--samples", args.num<uint32_t>("--spp", 1024)), spp = args.num<uint32_t>("--spp", 1);
+        const uint32_t batch = args.num<uint32_t>("--noise-batch", 16);
+        if (noise) {   // render until converged (render_until)
             rt_noise_summary ns;
-            const uint32_t its = rs.render_until((float)std::atof(t->c_str()), cap, batch, allow, 1e-3f, &ns);
+            const uint32_t its = rs.render_until(args.num<float>("--noise-target", 0.0f), cap, batch,
+                                                 args.num<double>("--noise-allow", 0.0), 1e-3f, &ns);
             frames = (its + batch - 1) / batch;
-            if (const std::string* out = arg("--out")) {
-                if (its >= 2) {
-                    const auto nm = rs.noise_map();
-                    write_file(*out + ".noise.f32", nm.data(), nm.size() * 4);
-                }
+            if (out && its >= 2) {
+                const auto nm = rs.noise_map();
+                write_file(*out + ".noise.f32", nm.data(), nm.size() * 4);
             }
             char b[256];
             std::snprintf(b, sizeof b,
@@ -363,17 +390,12 @@ int main(int argc, char** argv)
                           its, (unsigned long long)ns.pixels, (unsigned long long)ns.above,
                           (unsigned long long)ns.nonfinite, hexf(ns.max_rel_err).c_str());
             noise_json = b;
-        } else if (const std::string* t = arg("--adaptive-target")) {   // adaptive sampling (render_adaptive)
-            const uint32_t cap = arg("--samples") ? (uint32_t)std::atoi(arg("--samples")->c_str())
-                                 : arg("--spp")   ? (uint32_t)std::atoi(arg("--spp")->c_str())
-                                                  : 1024u;
-            const uint32_t batch = arg("--noise-batch") ? (uint32_t)std::atoi(arg("--noise-batch")->c_str()) : 16u;
-            const uint32_t amin = arg("--adaptive-min") ? (uint32_t)std::atoi(arg("--adaptive-min")->c_str()) : 16u;
-            rs.enable_adaptive((float)std::atof(t->c_str()), 1e-3f, amin, vote);
+        } else if (adaptive) {   // adaptive sampling (render_adaptive)
+            rs.enable_adaptive(args.num<float>("--adaptive-target", 0.0f), 1e-3f, args.num<uint32_t>("--adaptive-min", 16), vote);
             rt_adaptive_summary as;
             const uint32_t its = rs.render_adaptive(cap, batch, &as);
             frames = (its + batch - 1) / batch;
-            if (const std::string* out = arg("--out")) {
+            if (out) {
                 const auto cn = rs.sample_counts();
                 write_file(*out + ".count.u32", cn.data(), cn.size() * 4);
             }
@@ -386,21 +408,19 @@ int main(int argc, char** argv)
                           (unsigned long long)as.total_samples, as.min_count, as.max_count, hexf(as.max_rel_err).c_str());
             noise_json = b;
         } else if (temporal) {   // N frames with the keys held (temporal_step); the progressive frame stays as it is
-            const uint32_t spp = arg("--spp") ? (uint32_t)std::atoi(arg("--spp")->c_str()) : 1;
             rs.enable_temporal((uint32_t)tp_history, tp_normal_min, tp_plane_tol);
             for (int i = 0; i < tp_frames; i++) rs.temporal_step(spp);
             frames = (uint32_t)tp_frames;
-        } else if (const std::string* s = arg("--samples")) {   // the progressive loop, SetSamples
-            rs.set_samples((uint32_t)std::atoi(s->c_str()), true);
+        } else if (args.str("--samples")) {   // the progressive loop, SetSamples
+            rs.set_samples(args.num<uint32_t>("--samples", 0), true);
             while (rs.step()) frames++;
         } else {
-            const uint32_t spp = arg("--spp") ? (uint32_t)std::atoi(arg("--spp")->c_str()) : 1;
             rs.render(spp);
             frames = 1;
         }
         const rt_ray_counts c = rs.last_counts();
         if (rank != 0) return 0;   // the frame is rank 0's
-        if (const std::string* out = arg("--out")) {
+        if (out) {
             const auto f = rs.frame();
             const auto ids = rs.hit_ids();
             const auto rgba = rs.frame_rgba8();

@@ -156,6 +156,54 @@ private:
     rt_mesh_host* m_;
 };
 
+/* n elements of device memory and their owner: rt_device_alloc .. rt_device_free.  Move-only; the
+ * element type is the one the C ABI takes the buffer as.  Throws Error where the C ABI fails, but
+ * for the free, whose status nobody could act on. */
+template <class T>
+class DeviceArray {
+public:
+    DeviceArray() = default;
+    DeviceArray(const GpuHandles& gpu, size_t n, const char* what) : gpu_(&gpu), n_(n)
+    {
+        void* p = nullptr;
+        gpu.check(rt_device_alloc(gpu.ctx(), n * sizeof(T), &p), what);
+        p_ = static_cast<T*>(p);
+    }
+    DeviceArray(DeviceArray&& o) noexcept : gpu_(o.gpu_), p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+    DeviceArray& operator=(DeviceArray&& o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            gpu_ = o.gpu_;
+            p_ = std::exchange(o.p_, nullptr);
+            n_ = std::exchange(o.n_, 0);
+        }
+        return *this;
+    }
+    ~DeviceArray() { reset(); }
+    void reset()
+    {
+        if (p_) rt_device_free(gpu_->ctx(), p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    T* get() const { return p_; }
+    size_t size() const { return n_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    void zero(const char* what) { gpu_->check(rt_memset_device(gpu_->ctx(), p_, 0, n_ * sizeof(T)), what); }
+    std::vector<T> download(const char* what) const
+    {
+        std::vector<T> out(n_);
+        gpu_->check(rt_memcpy_to_host(gpu_->ctx(), out.data(), p_, n_ * sizeof(T)), what);
+        return out;
+    }
+
+private:
+    const GpuHandles* gpu_ = nullptr;
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+
 /* ---- src/render_state.rs + src/lib.rs rendering_thread */
 struct RenderOptions {
     std::string models_dir;                               // where scene models live
@@ -165,6 +213,11 @@ struct RenderOptions {
     Vec3 environment{1.0f, 1.0f, 1.0f};                   // W9 escape radiance without a texture
 };
 
+/* Every device buffer of a RenderState is a DeviceArray member, so whatever throws -- the
+ * constructor included -- leaves nothing allocated that the state does not still own.  A call that
+ * enables something allocates and clears into locals and commits when all of it succeeded: one that
+ * throws leaves the feature off.  A load_scene that throws leaves a state fit only for another
+ * load_scene or the destructor. */
 class RenderState {
 public:
     RenderState(GpuHandles& gpu, const SceneDescriptor& scene, RenderOptions opts);
@@ -197,7 +250,9 @@ public:
      * (rt_render_tiles, into a packed accumulation kept across iterations) and
      * gathers all ranks' tiles into rank 0's frame over RCCL (rt_comm_init with
      * the communicator id rank 0 made, rt_gather_tiles).  Collective: every rank
-     * calls it, then render()/step() in lockstep; frame()/hit_ids() are rank 0's. */
+     * calls it, then render()/step() in lockstep; frame()/hit_ids() are rank 0's.  When the
+     * tile buffers cannot be allocated it throws and the state stays untiled; the communicator
+     * rt_comm_init made stays in the context (rt_comm_destroy, or the context's end, removes it). */
     void set_tiling(uint32_t nranks, uint32_t rank, const uint8_t comm_id[RT_COMM_ID_BYTES]);
 
     /* The noise estimate of the path modes (rt.h "noise estimate"): from iteration 0 on, every
@@ -286,7 +341,8 @@ public:
 private:
     void setup_rendering(const SceneDescriptor& scene);   /* :161-265 */
     void release();
-    void* denoise_device(uint32_t levels, float sigma_l, float sigma_z) const;
+    DeviceArray<float> denoise_device(uint32_t levels, float sigma_l, float sigma_z) const;
+    DeviceArray<float> temporal_device(uint32_t levels, float sigma_l, float sigma_z) const;
 
     GpuHandles& gpu_;
     RenderOptions opts_;
@@ -300,31 +356,31 @@ private:
     uint32_t selection2_ = 0, use_texture_ = 0;
     std::array<float, 2> uv_scale_{1.0f, 1.0f};
     bool progressive_ = true;
-    void* accum_ = nullptr;
-    void* ids_ = nullptr;
-    void alloc_tiles();
+    DeviceArray<float> accum_;         // width x height RGBA32F
+    DeviceArray<uint32_t> ids_;
     uint32_t nranks_ = 1, rank_ = 0;   // set_tiling
     bool tiled_ = false;
-    void* tile_accum_ = nullptr;       // this rank's packed tiles (rt_render_tiles)
-    void* tile_ids_ = nullptr;
-    void* noise_ = nullptr;            // enable_noise: width x height rt_noise_state
-    void* counts_ = nullptr;           // enable_adaptive: width x height uint32 sample counts
+    DeviceArray<float> tile_accum_;    // this rank's packed tiles (rt_render_tiles)
+    DeviceArray<uint32_t> tile_ids_;
+    DeviceArray<rt_noise_state> noise_;   // enable_noise: width x height, registered with the context
+    DeviceArray<uint32_t> counts_;     // enable_adaptive: width x height sample counts, registered too
     float ad_target_ = 0.0f, ad_floor_ = 1e-3f;
     uint32_t ad_min_ = 16;
     int ad_vote_ = RT_ADAPT_TILE;
     rt_uniform uniform_{};             // what update() last set
     // enable_temporal: the current frame, the guide's dz and two history sets {colour, moments, length, nz}
     struct TemporalSet {
-        void *color = nullptr, *mom = nullptr, *len = nullptr, *nz = nullptr;
+        DeviceArray<float> color, mom, nz;
+        DeviceArray<uint32_t> len;
     };
     bool temporal_ = false;
-    void *tp_cur_ = nullptr, *tp_ids_ = nullptr, *tp_dz_ = nullptr;
+    DeviceArray<float> tp_cur_, tp_dz_;
+    DeviceArray<uint32_t> tp_ids_;
     TemporalSet tp_set_[2];
     int tp_latest_ = -1;               // the set of the latest frame; -1 before the first
     rt_uniform tp_uniform_{};          // the uniform that frame was rendered with
     uint32_t tp_k_ = 0, tp_max_history_ = 32, tp_min_len_ = 4;
     float tp_normal_min_ = 0.9f, tp_plane_tol_ = 0.01f;
-    void* temporal_device(uint32_t levels, float sigma_l, float sigma_z) const;
 };
 
 }  // namespace raytracer

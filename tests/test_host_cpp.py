@@ -5,6 +5,7 @@ controller and the jitter table must equal the Python mirror bit for bit
 import importlib
 import json
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -65,3 +66,49 @@ def test_jitter_table_equals_python(subdiv, h):
 def test_scene_errors():
     r = subprocess.run([BIN, "--scene", "W1 E1"], capture_output=True, text=True, timeout=60)
     assert r.returncode != 0
+
+
+def rt_codes():
+    text = open(os.path.join(ROOT, "include", "rt.h")).read()
+    return {k: int(v) for k, v in re.findall(r"#define\s+RT_E_(\w+)\s+\((-\d+)\)", text)}
+
+
+PATH_SCENE, TREE_SCENE = "W7 E3 Cornell Box", "W6 E1 Teapot"   # a path-family mode, and one that is not
+# what rt_render refuses before it opens a device: (options, the scene, the RT_E_* code)
+REFUSALS = [
+    ("--rank 2 --nranks 2", PATH_SCENE, "INVALID"),
+    ("--nranks 2", PATH_SCENE, "INVALID"),
+    ("--noise-target .1 --comm-file f", PATH_SCENE, "UNSUPPORTED"),
+    ("--adaptive-min 4", PATH_SCENE, "INVALID"),
+    ("--adaptive-target .1 --comm-file f", PATH_SCENE, "UNSUPPORTED"),
+    ("--adaptive-target .1 --noise-target .1", PATH_SCENE, "INVALID"),
+    ("--noise-target .1 --adaptive-target .1 --comm-file f", PATH_SCENE, "UNSUPPORTED"),   # the noise check is first
+    ("--adaptive-target .1 --adaptive-vote foo", PATH_SCENE, "INVALID"),
+    ("--denoise-levels 3", PATH_SCENE, "INVALID"),
+    ("--denoise --comm-file f", PATH_SCENE, "UNSUPPORTED"),
+    ("--denoise --denoise-levels 6", PATH_SCENE, "INVALID"),
+    ("--denoise --denoise-sigma-l 0", PATH_SCENE, "INVALID"),
+    ("--denoise", TREE_SCENE, "UNSUPPORTED"),
+    ("--denoise", "nope", "INVALID"),
+    ("--temporal-history 4", PATH_SCENE, "INVALID"),
+    ("--temporal-frames 2 --comm-file f", PATH_SCENE, "UNSUPPORTED"),
+    ("--temporal-frames 2 --samples 3", PATH_SCENE, "INVALID"),
+    ("--temporal-frames 0", PATH_SCENE, "INVALID"),
+    ("--temporal-frames 2 --spp 0", PATH_SCENE, "INVALID"),
+    ("--temporal-frames 2", TREE_SCENE, "UNSUPPORTED"),
+    ("--res 12", PATH_SCENE, "INVALID"),
+]
+
+
+@pytest.mark.parametrize("options,scene,code", REFUSALS, ids=[f"{o} [{s}]" for o, s, _ in REFUSALS])
+def test_refusals_before_a_device_is_opened(options, scene, code, tmp_path):
+    """Every option check of rt_render that comes before GpuHandles: exit status 1, nothing on stdout,
+    the RT_E_* value of include/rt.h on stderr.  (--env-rgba without --env-size is checked after
+    the device is opened, so it has no row here.)"""
+    r = subprocess.run([BIN, *options.split(), "--scene", scene], capture_output=True, text=True, timeout=60,
+                       cwd=tmp_path)
+    assert r.returncode == 1 and r.stdout == "", (r.returncode, r.stdout, r.stderr)
+    assert r.stderr.startswith(f"rt_render: error {rt_codes()[code]}: "), r.stderr
+    # the text names what it refuses: the row's first option, but for the two rows that refuse a later word
+    named = {"--adaptive-target .1 --adaptive-vote foo": "--adaptive-vote"}.get(options, options.split()[0])
+    assert ("nope" if scene == "nope" else named) in r.stderr, r.stderr
