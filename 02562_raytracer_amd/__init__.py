@@ -10,13 +10,13 @@ The package directory name starts with a digit; import it with
 """
 from . import _ffi
 from ._ffi import MODES, TRAVERSALS, RtError, lib
-from .core import (BspTree, Bvh, Context, DeviceBuffer, Mesh, empty_mask_host, load_texture_rgba8, local_tiles,
-                   make_uniform, pixel_depth_host)
+from .core import (BspTree, Bvh, Context, DeviceBuffer, Mesh, empty_mask_host, guide_objects_of, load_texture_rgba8,
+                   local_tiles, make_uniform, pixel_depth_host)
 from .render_state import ASSETS, RenderState
 from .camera import CameraController
 from .scenes import Camera, SceneDescriptor, find_scene, get_scenes
 
 __all__ = ["BspTree", "Bvh", "Camera", "CameraController", "Context", "DeviceBuffer", "Mesh", "RenderState", "RtError",
-           "SceneDescriptor", "ASSETS", "MODES", "TRAVERSALS", "find_scene", "get_scenes", "lib", "local_tiles",
+           "SceneDescriptor", "ASSETS", "MODES", "TRAVERSALS", "find_scene", "get_scenes", "guide_objects_of", "lib", "local_tiles",
            "load_texture_rgba8",
            "make_uniform", "_ffi"]

@@ -223,6 +223,8 @@ class ModeDesc(C.Structure):          # include/rt.h rt_mode_desc
 
 
 RT_ADAPT_PIXEL, RT_ADAPT_TILE = 0, 1
+# rt_guide_objects' bits: the analytic objects a guide can put under the pixels without a primary id
+RT_GUIDE_BALLS, RT_GUIDE_PLANE = 1, 2
 ADAPT_VOTES = {"pixel": RT_ADAPT_PIXEL, "tile": RT_ADAPT_TILE}
 
 # name -> (restype, argtypes); mirrors include/rt.h one to one
@@ -290,6 +292,10 @@ SIGNATURES = {
     "rt_temporal_variance": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_float, C.c_float,
                                        vp]),
     "rt_temporal_times": (C.c_int, [vp, f32p, f32p, u32p]),
+    "rt_guide_objects": (C.c_int, [C.c_int, u32p]),
+    "rt_denoise_guide_objects": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp]),
+    "rt_denoise_objects": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp, C.c_uint32, C.c_uint32,
+                                     C.c_float, C.c_float, vp]),
     "rt_unpack_tiles": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "rt_comm_unique_id": (C.c_int, [vp]),
     "rt_comm_init": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),

@@ -495,9 +495,14 @@ class Context:
         return {"live": int(live.value), "dealt": int(dealt.value), "list": bool(took.value)}
 
     # ---- the denoise filter (include/rt.h "denoise"; device pointers, asynchronous)
-    def denoise_guide(self, width, height, ids_ptr, nz_ptr, dz_ptr):
+    def denoise_guide(self, width, height, ids_ptr, nz_ptr, dz_ptr, objects=0):
         """rt_denoise_guide: {N, z} (float4) and {dzx, dzy} (float2) per pixel from the primary ids,
-        the uploaded mesh and the current uniforms."""
+        the uploaded mesh and the current uniforms; with objects (a mask of RT_GUIDE_*, see
+        guide_objects_of()) rt_denoise_guide_objects: those analytic objects under the pixels without an id."""
+        if objects:
+            self._chk(F.lib().rt_denoise_guide_objects(self._h, int(objects), width, height, C.c_void_p(ids_ptr),
+                                                       C.c_void_p(nz_ptr), C.c_void_p(dz_ptr)))
+            return
         self._chk(F.lib().rt_denoise_guide(self._h, width, height, C.c_void_p(ids_ptr), C.c_void_p(nz_ptr),
                                            C.c_void_p(dz_ptr)))
 
@@ -516,8 +521,14 @@ class Context:
                                             _vp(out_var_ptr)))
 
     def denoise(self, width, height, accum_ptr, ids_ptr, state_ptr, count_ptr, n, out_ptr, levels=5, sigma_l=4.0,
-                sigma_z=1.0):
-        """rt_denoise: guide, variance and filter of a rendered frame on the context's scratch."""
+                sigma_z=1.0, objects=0):
+        """rt_denoise: guide, variance and filter of a rendered frame on the context's scratch; with
+        objects (a mask of RT_GUIDE_*) rt_denoise_objects: the same with the guide of those objects."""
+        if objects:
+            self._chk(F.lib().rt_denoise_objects(self._h, int(objects), width, height, C.c_void_p(accum_ptr),
+                                                 C.c_void_p(ids_ptr), C.c_void_p(state_ptr), _vp(count_ptr), int(n),
+                                                 int(levels), float(sigma_l), float(sigma_z), C.c_void_p(out_ptr)))
+            return
         self._chk(F.lib().rt_denoise(self._h, width, height, C.c_void_p(accum_ptr), C.c_void_p(ids_ptr),
                                      C.c_void_p(state_ptr), _vp(count_ptr), int(n),
                                      int(levels), float(sigma_l), float(sigma_z), C.c_void_p(out_ptr)))
@@ -702,6 +713,14 @@ class Context:
         bad = C.c_uint32()
         self._chk(F.lib().rt_selftest_math(self._h, n, lo, hi, C.byref(bad)))
         return bad.value
+
+
+def guide_objects_of(mode):
+    """rt_guide_objects: the mask (RT_GUIDE_*) of the analytic objects a mode's shader tests
+    beside the mesh and that leave no primary id; mode: a name or an rt_mode value."""
+    out = C.c_uint32(0)
+    F.check(F.lib().rt_guide_objects(F.MODES[mode] if isinstance(mode, str) else int(mode), C.byref(out)))
+    return int(out.value)
 
 
 def _mask_bits(words, width, height):

@@ -82,6 +82,11 @@ inline std::string resolution_fault(const uint32_t resolution[2], uint32_t width
 {
     return resolution[0] != width || resolution[1] != height ? "the uniforms' resolution is not width x height" : "";
 }
+// a mask of the analytic objects a guide knows (rt.h RT_GUIDE_*)
+inline std::string guide_objects_fault(uint32_t objects)
+{
+    return objects & ~(RT_GUIDE_BALLS | RT_GUIDE_PLANE) ? "objects has a bit outside RT_GUIDE_BALLS | RT_GUIDE_PLANE" : "";
+}
 inline std::string filter_fault(uint32_t levels, float sigma_l, float sigma_z)
 {
     if (levels < 1 || levels > 5) return "levels must be in 1..5";

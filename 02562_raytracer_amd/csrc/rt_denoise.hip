@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "rt_frame_common.h"
+#include "rt_scene3.h"
 
 namespace rtk {
 
@@ -48,6 +49,96 @@ __global__ void __launch_bounds__(256) k_denoise_guide(DenoiseCam G, const float
                 onz = v4f{g.x, g.y, g.z, z};
                 odz = v2f{finitef(dzx) ? dzx : 0.0f, finitef(dzy) ? dzy : 0.0f};
             }
+        }
+        nz[o] = onz;
+        dz[o] = odz;
+    }
+}
+
+// ------------------------------------------------------------------ guide with objects
+// (rt.h "denoise / Guide with objects").  A pixel with a primary id is k_denoise_guide's, line
+// for line; a pixel without one (0xFFFFFFFF: k_path sets the id on a mesh hit alone) tests the
+// analytic objects of `objects` on its centre ray as k_path's closest-hit ray does: the tests
+// are the shader's (rt_scene3.h), in its order, each accept lowering tmax.  tmin is the path
+// kernels' ETA of the modes that hold the object: 0.01 for the W8 balls, 0.0001 for the W9
+// plane.  `objects` is uniform over the launch: a wave takes or skips each test as one.
+constexpr float GUIDE_ETA_BALLS = 0.01f;
+constexpr float GUIDE_ETA_PLANE = 0.0001f;
+
+__global__ void __launch_bounds__(256) k_denoise_guide_objects(DenoiseCam G, uint32_t objects,
+                                                               const float4* __restrict__ pos,
+                                                               const uint4* __restrict__ tri_idx, uint32_t ntris,
+                                                               const uint32_t* __restrict__ ids, v4f* __restrict__ nz,
+                                                               v2f* __restrict__ dz)
+{
+    const uint32_t npix = G.w * G.h;
+    const Cam c = cam_from(G.cam);
+    for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < npix; o += gridDim.x * blockDim.x) {
+        const uint32_t y = o / G.w, x = o - y * G.w;
+        const uint32_t id = ids[o];
+        v4f onz = {0.0f, 0.0f, 0.0f, -1.0f};
+        v2f odz = {0.0f, 0.0f};
+        const f3 w = centre_dir(c, G.w, G.h, x, y);
+        f3 g = V(0.0f, 0.0f, 0.0f);
+        float z = -1.0f, num = 0.0f;
+        bool surface = false;
+        if (id != 0xFFFFFFFFu) {
+            if (id < ntris) {
+                const uint4 t = tri_idx[id];
+                const f3 v0 = ld3(pos[t.x]);
+                const f3 e0 = sub(ld3(pos[t.y]), v0);
+                const f3 e1 = sub(ld3(pos[t.z]), v0);
+                g = normalize(cross(e0, e1));
+                if (dot(g, w) > 0.0f) g = neg(g);
+                const float den = dot(w, g);
+                num = dot(sub(v0, c.e), g);
+                z = num / den;
+                surface = den != 0.0f && finitef(z) && z > 0.0f;
+            }
+        } else {
+            float tmax = SCENE3_TMAX;
+            int hit = 0;   // 1: a ball (centre `bc`), 2: the plane
+            f3 bc = V(0.0f, 0.0f, 0.0f);
+            if (objects & RT_GUIDE_BALLS) {
+                if (scene3_sphere(c.e, w, GUIDE_ETA_BALLS, tmax, w8_mirror_center(), W8_BALL_RADIUS, tmax)) {
+                    hit = 1;
+                    bc = w8_mirror_center();
+                }
+                if (scene3_sphere(c.e, w, GUIDE_ETA_BALLS, tmax, w8_glass_center(), W8_BALL_RADIUS, tmax)) {
+                    hit = 1;
+                    bc = w8_glass_center();
+                }
+            }
+            if (objects & RT_GUIDE_PLANE) {
+                float t;
+                // scene3_plane accepts a NaN distance; the guide makes no surface of it
+                if (scene3_plane(c.e, w, GUIDE_ETA_PLANE, tmax, t) && finitef(t) && t > 0.0f &&
+                    dot(w, scene3_plane_normal()) != 0.0f) {
+                    hit = 2;
+                    tmax = t;
+                }
+            }
+            if (hit) {
+                z = tmax;
+                g = scene3_plane_normal();
+                if (hit == 1) {
+                    const f3 P = add(c.e, muls(w, z));
+                    g = normalize(sub(P, bc));
+                }
+                if (dot(g, w) > 0.0f) g = neg(g);
+                const float den = dot(w, g);
+                num = z * den;
+                surface = true;
+            }
+        }
+        if (surface) {
+            // the tangent plane under the two neighbours' rays, a triangle's and an object's alike
+            const float zx = num / dot(centre_dir(c, G.w, G.h, x + 1u, y), g);
+            const float zy = num / dot(centre_dir(c, G.w, G.h, x, y + 1u), g);
+            const float dzx = zx - z;
+            const float dzy = zy - z;
+            onz = v4f{g.x, g.y, g.z, z};
+            odz = v2f{finitef(dzx) ? dzx : 0.0f, finitef(dzy) ? dzy : 0.0f};
         }
         nz[o] = onz;
         dz[o] = odz;
@@ -320,6 +411,14 @@ int launch_denoise_guide(const DenoiseCam& g, const float4* pos, const uint4* tr
 {
     hipLaunchKernelGGL(k_denoise_guide, dim3(stream_blocks((uint64_t)g.w * g.h, 4096)), dim3(256), 0, stream, g, pos,
                        tri_idx, ntris, ids, reinterpret_cast<v4f*>(nz), reinterpret_cast<v2f*>(dz));
+    return launch_status();
+}
+
+int launch_denoise_guide_objects(const DenoiseCam& g, uint32_t objects, const float4* pos, const uint4* tri_idx,
+                                 uint32_t ntris, const uint32_t* ids, float* nz, float* dz, hipStream_t stream)
+{
+    hipLaunchKernelGGL(k_denoise_guide_objects, dim3(stream_blocks((uint64_t)g.w * g.h, 4096)), dim3(256), 0, stream, g,
+                       objects, pos, tri_idx, ntris, ids, reinterpret_cast<v4f*>(nz), reinterpret_cast<v2f*>(dz));
     return launch_status();
 }
 

@@ -38,25 +38,27 @@ int dn_run_levels(rt_ctx* c, const char* who, uint32_t width, uint32_t height, c
     return RT_OK;
 }
 
-// the guide of the uniforms' camera for the ids of a width x height frame
-int dn_guide(rt_ctx* c, uint32_t width, uint32_t height, const uint32_t* ids, float* nz, float* dz)
+// the guide of the uniforms' camera for the ids of a width x height frame; objects (RT_GUIDE_*):
+// the analytic objects under the pixels without an id (0: rt_denoise_guide's own kernel)
+int dn_guide(rt_ctx* c, uint32_t objects, uint32_t width, uint32_t height, const uint32_t* ids, float* nz, float* dz)
 {
     rtk::DenoiseCam g;
     rtk::camera_basis(c->u, g.cam);
     g.w = width;
     g.h = height;
+    if (objects)
+        return rtk::launch_denoise_guide_objects(g, objects, c->scene.pos.as<float4>(), c->scene.idx.as<uint4>(),
+                                                 c->scene.ntris, ids, nz, dz, c->stream);
     return rtk::launch_denoise_guide(g, c->scene.pos.as<float4>(), c->scene.idx.as<uint4>(), c->scene.ntris, ids, nz, dz,
                                      c->stream);
 }
 
-}  // namespace
-
-extern "C" {
-
-int rt_denoise_guide(rt_ctx* c, uint32_t width, uint32_t height, const uint32_t* ids, float* nz, float* dz)
+// rt_denoise_guide and rt_denoise_guide_objects
+int dn_guide_call(rt_ctx* c, const char* who, uint32_t objects, uint32_t width, uint32_t height, const uint32_t* ids,
+                  float* nz, float* dz)
 {
-    const char* const who = "rt_denoise_guide";
     if (!c) return fail(nullptr, RT_E_INVALID, std::string(who) + ": null context");
+    if (int r = refuse(c, who, guide_objects_fault(objects))) return r;
     uint64_t npix;
     if (int r = refuse(c, who, frame_fault(width, height, &npix))) return r;
     if (npix == 0) return RT_OK;
@@ -67,8 +69,54 @@ int rt_denoise_guide(rt_ctx* c, uint32_t width, uint32_t height, const uint32_t*
         return fail(c, RT_E_NOT_READY, std::string(who) + ": needs rt_upload_mesh and rt_set_uniforms");
     if (int r = refuse(c, who, resolution_fault(c->u.resolution, width, height))) return r;
     if (int r = set_dev(c)) return r;
-    if (dn_guide(c, width, height, ids, nz, dz)) return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed");
+    if (dn_guide(c, objects, width, height, ids, nz, dz)) return fail(c, RT_E_DEVICE, std::string(who) + ": launch failed");
     return RT_OK;
+}
+
+// rt_denoise and rt_denoise_objects
+int dn_denoise_call(rt_ctx* c, const char* who, uint32_t objects, uint32_t width, uint32_t height, const float* accum,
+                    const uint32_t* ids, const rt_noise_state* state, const uint32_t* count, uint32_t n, uint32_t levels,
+                    float sigma_l, float sigma_z, float* out)
+{
+    if (!c) return fail(nullptr, RT_E_INVALID, std::string(who) + ": null context");
+    if (int r = refuse(c, who, guide_objects_fault(objects))) return r;
+    if (int r = refuse(c, who, filter_fault(levels, sigma_l, sigma_z))) return r;
+    if (!count && n < 2) return fail(c, RT_E_INVALID, std::string(who) + ": the variance needs n >= 2 iterations (or counts)");
+    uint64_t npix;
+    if (int r = refuse(c, who, frame_fault(width, height, &npix))) return r;
+    if (npix == 0) return RT_OK;
+    const BufRange rg[] = {{accum, npix * 16, 16, false, false, "accum"}, {ids, npix * 4, 4, false, false, "ids"},
+                           {state, npix * 8, 8, false, false, "state"},   {count, npix * 4, 4, false, true, "count"},
+                           {out, npix * 16, 16, true, false, "out"}};
+    if (int r = refuse(c, who, buffers_fault(rg))) return r;
+    if (!c->scene.has_mesh || !c->has_u) return fail(c, RT_E_NOT_READY, std::string(who) + ": needs rt_upload_mesh and rt_set_uniforms");
+    if (int r = refuse(c, who, resolution_fault(c->u.resolution, width, height))) return r;
+    if (int r = set_dev(c)) return r;
+    DenoiseState& d = c->denoise;
+    HIPCHK(c, d.var.ensure(npix * 4));
+    HIPCHK(c, d.nz.ensure(npix * 16));
+    HIPCHK(c, d.dz.ensure(npix * 8));
+    if (dn_guide(c, objects, width, height, ids, d.nz.as<float>(), d.dz.as<float>()))
+        return fail(c, RT_E_DEVICE, std::string(who) + ": guide launch failed");
+    if (rtk::launch_denoise_variance(state, count, (uint32_t)npix, n, d.var.as<float>(), c->stream))
+        return fail(c, RT_E_DEVICE, std::string(who) + ": variance launch failed");
+    return dn_run_levels(c, who, width, height, accum, d.var.as<float>(), d.nz.as<float>(), d.dz.as<float>(),
+                         levels, sigma_l, sigma_z, out, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_denoise_guide(rt_ctx* c, uint32_t width, uint32_t height, const uint32_t* ids, float* nz, float* dz)
+{
+    return dn_guide_call(c, "rt_denoise_guide", 0, width, height, ids, nz, dz);
+}
+
+int rt_denoise_guide_objects(rt_ctx* c, uint32_t objects, uint32_t width, uint32_t height, const uint32_t* ids, float* nz,
+                             float* dz)
+{
+    return dn_guide_call(c, "rt_denoise_guide_objects", objects, width, height, ids, nz, dz);
 }
 
 int rt_denoise_variance(rt_ctx* c, const rt_noise_state* state, const uint32_t* count, uint32_t npix, uint32_t n,
@@ -111,30 +159,15 @@ int rt_denoise(rt_ctx* c, uint32_t width, uint32_t height, const float* accum, c
                const rt_noise_state* state, const uint32_t* count, uint32_t n, uint32_t levels, float sigma_l,
                float sigma_z, float* out)
 {
-    const char* const who = "rt_denoise";
-    if (!c) return fail(nullptr, RT_E_INVALID, std::string(who) + ": null context");
-    if (int r = refuse(c, who, filter_fault(levels, sigma_l, sigma_z))) return r;
-    if (!count && n < 2) return fail(c, RT_E_INVALID, std::string(who) + ": the variance needs n >= 2 iterations (or counts)");
-    uint64_t npix;
-    if (int r = refuse(c, who, frame_fault(width, height, &npix))) return r;
-    if (npix == 0) return RT_OK;
-    const BufRange rg[] = {{accum, npix * 16, 16, false, false, "accum"}, {ids, npix * 4, 4, false, false, "ids"},
-                           {state, npix * 8, 8, false, false, "state"},   {count, npix * 4, 4, false, true, "count"},
-                           {out, npix * 16, 16, true, false, "out"}};
-    if (int r = refuse(c, who, buffers_fault(rg))) return r;
-    if (!c->scene.has_mesh || !c->has_u) return fail(c, RT_E_NOT_READY, std::string(who) + ": needs rt_upload_mesh and rt_set_uniforms");
-    if (int r = refuse(c, who, resolution_fault(c->u.resolution, width, height))) return r;
-    if (int r = set_dev(c)) return r;
-    DenoiseState& d = c->denoise;
-    HIPCHK(c, d.var.ensure(npix * 4));
-    HIPCHK(c, d.nz.ensure(npix * 16));
-    HIPCHK(c, d.dz.ensure(npix * 8));
-    if (dn_guide(c, width, height, ids, d.nz.as<float>(), d.dz.as<float>()))
-        return fail(c, RT_E_DEVICE, std::string(who) + ": guide launch failed");
-    if (rtk::launch_denoise_variance(state, count, (uint32_t)npix, n, d.var.as<float>(), c->stream))
-        return fail(c, RT_E_DEVICE, std::string(who) + ": variance launch failed");
-    return dn_run_levels(c, who, width, height, accum, d.var.as<float>(), d.nz.as<float>(), d.dz.as<float>(),
-                         levels, sigma_l, sigma_z, out, nullptr);
+    return dn_denoise_call(c, "rt_denoise", 0, width, height, accum, ids, state, count, n, levels, sigma_l, sigma_z, out);
+}
+
+int rt_denoise_objects(rt_ctx* c, uint32_t objects, uint32_t width, uint32_t height, const float* accum,
+                       const uint32_t* ids, const rt_noise_state* state, const uint32_t* count, uint32_t n, uint32_t levels,
+                       float sigma_l, float sigma_z, float* out)
+{
+    return dn_denoise_call(c, "rt_denoise_objects", objects, width, height, accum, ids, state, count, n, levels, sigma_l,
+                           sigma_z, out);
 }
 
 int rt_denoise_level_times(rt_ctx* c, float* level_ms, uint32_t* lds_form)

@@ -276,6 +276,9 @@ struct DenoiseCam {
 // nz: w x h float4 {N, z}, dz: w x h float2 {dzx, dzy}, from the primary ids and the mesh
 int launch_denoise_guide(const DenoiseCam& g, const float4* pos, const uint4* tri_idx, uint32_t ntris,
                          const uint32_t* ids, float* nz, float* dz, hipStream_t stream);
+// the same with the analytic objects of `objects` (RT_GUIDE_*, not 0) under the pixels that have no id
+int launch_denoise_guide_objects(const DenoiseCam& g, uint32_t objects, const float4* pos, const uint4* tri_idx,
+                                 uint32_t ntris, const uint32_t* ids, float* nz, float* dz, hipStream_t stream);
 // var[i] = the variance of state[i]'s mean after count[i] (or, count null, n) iterations; 0x7FC00000: unfilterable
 int launch_denoise_variance(const rt_noise_state* state, const uint32_t* count, uint32_t npix, uint32_t n, float* var,
                             hipStream_t stream);

@@ -71,3 +71,14 @@ extern "C" int rt_mode_describe(int mode, rt_mode_desc* out)
     *out = *d;
     return RT_OK;
 }
+
+// the analytic objects a path mode's shader tests beside the mesh and that leave no primary id
+// (rt.h "denoise / Guide with objects"); W6E3 renders the balls too but is no path mode
+extern "C" int rt_guide_objects(int mode, uint32_t* objects)
+{
+    if (!mode_desc((rt_mode)mode) || !objects) return RT_E_INVALID;
+    *objects = mode == RT_MODE_W8E1 || mode == RT_MODE_W8E2 || mode == RT_MODE_W8E3 ? RT_GUIDE_BALLS
+               : mode == RT_MODE_W9E2 || mode == RT_MODE_W9E3                      ? RT_GUIDE_PLANE
+                                                                                   : 0u;
+    return RT_OK;
+}

@@ -26,6 +26,13 @@ __device__ __forceinline__ f3 scene3_sphere_color() { return V(0.0f, 0.0f, 0.0f)
 __device__ __forceinline__ f3 scene3_plane_color() { return V(0.1f, 0.7f, 0.0f); }
 __device__ __forceinline__ f3 scene3_background() { return V(0.1f, 0.3f, 0.6f); }
 
+// The two balls of W8E1..W8E3 (w8e1.wgsl:244-262: the mirror ball, then the glass ball), tested
+// with scene3_sphere below: one definition for the path kernel (rt_shade.h w8_balls) and the
+// object guide (rt_denoise.hip)
+constexpr float W8_BALL_RADIUS = 90.0f;
+__device__ __forceinline__ f3 w8_mirror_center() { return V(420.0f, 90.0f, 370.0f); }
+__device__ __forceinline__ f3 w8_glass_center() { return V(130.0f, 90.0f, 250.0f); }
+
 struct Scene3Tri {
     f3 v0, e0, e1, normal;   // normal = cross(e0, e1), not normalised
 };

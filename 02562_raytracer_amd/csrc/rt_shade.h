@@ -82,7 +82,7 @@ struct W8Ball {
 // intersect_sphere (w8e1.wgsl:352-376) is the three-object scene's: the closest root in [tmin, b.t]
 __device__ __forceinline__ void w8_ball(f3 o, f3 w, float tmin, f3 center, uint32_t id, W8Ball& b)
 {
-    if (!scene3_sphere(o, w, tmin, b.t, center, 90.0f, b.t)) return;
+    if (!scene3_sphere(o, w, tmin, b.t, center, W8_BALL_RADIUS, b.t)) return;
     b.id = id;
     b.pos = add(o, muls(w, b.t));
     b.nrm = normalize(sub(b.pos, center));
@@ -93,8 +93,8 @@ __device__ __forceinline__ W8Ball w8_balls(f3 o, f3 w, float tmin, float tmax)
     b.id = 0;
     b.t = tmax;
     b.pos = b.nrm = V(0, 0, 0);
-    w8_ball(o, w, tmin, V(420.0f, 90.0f, 370.0f), 1, b);
-    w8_ball(o, w, tmin, V(130.0f, 90.0f, 250.0f), 2, b);
+    w8_ball(o, w, tmin, w8_mirror_center(), 1, b);
+    w8_ball(o, w, tmin, w8_glass_center(), 2, b);
     return b;
 }
 

@@ -648,6 +648,38 @@ static std::vector<uint8_t> rgba8_of(const GpuHandles& gpu, rt_mode mode, const 
 
 std::vector<uint8_t> RenderState::frame_rgba8() const { return rgba8_of(gpu_, mode(), accum_, "frame_rgba8"); }
 
+// ---- the guide with objects (rt.h "denoise / Guide with objects")
+// Its entry points are referenced weakly, so that this file also links against a library from
+// before they existed (and against a test's stub of the ABI): absent, the flag's first use throws
+// RT_E_UNSUPPORTED and everything else works as before.
+extern "C" {
+int rt_guide_objects(int mode, uint32_t* objects) __attribute__((weak));
+int rt_denoise_guide_objects(rt_ctx* ctx, uint32_t objects, uint32_t width, uint32_t height, const uint32_t* ids_dev,
+                             float* nz_dev, float* dz_dev) __attribute__((weak));
+int rt_denoise_objects(rt_ctx* ctx, uint32_t objects, uint32_t width, uint32_t height, const float* accum_dev,
+                       const uint32_t* ids_dev, const rt_noise_state* state_dev, const uint32_t* count_dev, uint32_t n,
+                       uint32_t levels, float sigma_l, float sigma_z, float* out_rgba_dev) __attribute__((weak));
+}
+
+void RenderState::set_guide_objects(bool on)
+{
+    if (temporal_)
+        throw Error(RT_E_UNSUPPORTED, "set_guide_objects: temporal accumulation is enabled and its history holds the guide it "
+                                      "was made with (set_guide_objects before enable_temporal)");
+    guide_objects_ = on;
+}
+
+// the objects mask of the guides this state makes; 0: rt_denoise_guide and rt_denoise themselves
+uint32_t RenderState::guide_mask(const char* who) const
+{
+    if (!guide_objects_) return 0;
+    if (!rt_guide_objects || !rt_denoise_guide_objects || !rt_denoise_objects)
+        throw Error(RT_E_UNSUPPORTED, std::string(who) + ": set_guide_objects is on, and the library has no rt_denoise_guide_objects");
+    uint32_t objects = 0;
+    gpu_.check(rt_guide_objects(mode(), &objects), who);
+    return objects;
+}
+
 // the denoised frame on the device
 DeviceArray<float> RenderState::denoise_device(uint32_t levels, float sigma_l, float sigma_z) const
 {
@@ -657,9 +689,12 @@ DeviceArray<float> RenderState::denoise_device(uint32_t levels, float sigma_l, f
     if (iteration_ < 2) throw Error(RT_E_INVALID, "denoise: the variance needs at least 2 rendered iterations");
     if (levels < 1 || levels > 5 || !(sigma_l > 0.0f) || !(sigma_z > 0.0f))
         throw Error(RT_E_INVALID, "denoise: levels in 1..5, sigmas > 0");
+    const uint32_t objects = guide_mask("denoise");
     DeviceArray<float> d(gpu_, accum_.size(), "denoise buffer");
-    gpu_.check(rt_denoise(gpu_.ctx(), width_, height_, accum_.get(), ids_.get(), noise_.get(), counts_.get(), iteration_,
-                          levels, sigma_l, sigma_z, d.get()),
+    gpu_.check(objects ? rt_denoise_objects(gpu_.ctx(), objects, width_, height_, accum_.get(), ids_.get(), noise_.get(),
+                                            counts_.get(), iteration_, levels, sigma_l, sigma_z, d.get())
+                       : rt_denoise(gpu_.ctx(), width_, height_, accum_.get(), ids_.get(), noise_.get(), counts_.get(),
+                                    iteration_, levels, sigma_l, sigma_z, d.get()),
                "denoise");
     return d;
 }
@@ -727,6 +762,7 @@ void RenderState::temporal_step(uint32_t spp)
     if (tiled_) throw Error(RT_E_UNSUPPORTED, std::string("temporal_step") + kTemporalUntiled);
     if (!temporal_) throw Error(RT_E_NOT_READY, "temporal_step: enable_temporal() first");
     if (spp < 1) throw Error(RT_E_INVALID, "temporal_step: spp must be at least 1");
+    const uint32_t objects = guide_mask("temporal_step");
     rt_ctx* c = gpu_.ctx();
     tp_cur_.zero("clear temporal frame");
     // the frame is not the progressive render's: its noise state and counts stay as they are.  Both
@@ -744,7 +780,9 @@ void RenderState::temporal_step(uint32_t spp)
     const TemporalSet none, &old = tp_latest_ < 0 ? none : tp_set_[tp_latest_];
     const TemporalSet& out = tp_set_[tp_latest_ < 0 ? 0 : 1 - tp_latest_];
     // the guide of the camera that rendered the frame: before update() moves it
-    gpu_.check(rt_denoise_guide(c, width_, height_, tp_ids_.get(), out.nz.get(), tp_dz_.get()), "temporal guide");
+    gpu_.check(objects ? rt_denoise_guide_objects(c, objects, width_, height_, tp_ids_.get(), out.nz.get(), tp_dz_.get())
+                       : rt_denoise_guide(c, width_, height_, tp_ids_.get(), out.nz.get(), tp_dz_.get()),
+               "temporal guide");
     const float scale = (float)(tp_k_ + spp) / (float)spp;
     gpu_.check(rt_temporal_accumulate(c, width_, height_, tp_cur_.get(), scale, out.nz.get(),
                                       tp_latest_ < 0 ? nullptr : &tp_uniform_, old.color.get(), old.mom.get(), old.len.get(),

@@ -52,6 +52,12 @@
 //                                        PREFIX.denoised.* is not written) beside the progressive frame's
 //                                        files; refused with --comm-file / --nranks, --noise-target,
 //                                        --adaptive-target and --samples)
+//             [--guide-objects]          (with --denoise or --temporal-frames: their guide also holds
+//                                        the analytic objects of the scene's mode -- the two balls of
+//                                        W8E1..W8E3, the holdout plane of W9E2 / W9E3 --, which the
+//                                        primary ids do not name: set_guide_objects,
+//                                        rt_denoise_guide_objects; a mode without them is not changed;
+//                                        refused without one of the two flags)
 //   rt_render ... --nranks N --rank R --comm-file PATH [--comm-token T] [--device D]
 //                                        (one process per GPU: rank R renders its
 //                                        interleaved tiles, rank 0 gathers the frame
@@ -332,6 +338,10 @@ int main(int argc, char** argv)
             if (!path_scene())
                 throw Error(RT_E_UNSUPPORTED, "--temporal-frames: the scene's mode writes no per-iteration records (a path mode only)");
         }
+        // the guide with objects is the filters' guide: there is none to change without one of them
+        const bool guide_objects = args.has("--guide-objects");
+        if (guide_objects && !denoise && !temporal)
+            throw Error(RT_E_INVALID, "--guide-objects needs --denoise or --temporal-frames N (it changes their guide)");
         int vote = RT_ADAPT_TILE;
         if (const std::string* v = args.str("--adaptive-vote")) {
             if (*v == "pixel") vote = RT_ADAPT_PIXEL;
@@ -368,6 +378,7 @@ int main(int argc, char** argv)
         // --denoise: the noise estimate from iteration 0 on, unless --noise-target / --adaptive-target enable it
         // (with --temporal-frames it only carries the filter's parameters: no progressive frame is rendered)
         if (denoise && !temporal && !noise && !adaptive) rs.enable_noise();
+        if (guide_objects) rs.set_guide_objects(true);   // (before enable_temporal below)
         uint32_t frames = 0;
         std::string noise_json;
         const std::string* const out = args.str("--out");

@@ -23,13 +23,15 @@ import numpy as np
 from . import _ffi as F
 from .camera import Camera, CameraController
 from .jitter import MAX_SUBDIVISION, jitters_for
-from .core import BspTree, Bvh, Context, Mesh, make_uniform, synth_texture
+from .core import BspTree, Bvh, Context, Mesh, guide_objects_of, make_uniform, synth_texture
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASSETS = os.path.join(REPO, "assets", "models")
 
 
 class RenderState:
+    guide_objects = False   # set_guide_objects(): the guide also sees the mode's analytic objects
+
     def __init__(self, scene, device=0, ctx=None, models_dir=ASSETS, bunny_standin=True, selection1=0,
                  env=(1.0, 1.0, 1.0), resolution=None, device_build=False):
         self.ctx = ctx if ctx is not None else Context(device)
@@ -361,6 +363,23 @@ class RenderState:
             for b in bufs:
                 b.free()
 
+    # ---- the guide with objects (include/rt.h "denoise / Guide with objects")
+    def set_guide_objects(self, on):
+        """Off (the default): the guide of denoise(), denoised_rgba8(), temporal_step(),
+        temporal_frame() and temporal_rgba8() is rt_denoise_guide's, for which the W8 balls and
+        the W9E2 / W9E3 holdout plane are background.  On: it is rt_denoise_guide_objects' with
+        rt_guide_objects(mode), which gives those pixels the object's normal and depth -- and a
+        history; a mode without such objects is not changed.  A history's guide must come from
+        one definition: set it before enable_temporal().  load_scene keeps it."""
+        if getattr(self, "temporal", None) is not None:
+            raise ValueError("set_guide_objects: temporal accumulation is enabled and its history holds the guide "
+                             "it was made with (set_guide_objects before enable_temporal)")
+        self.guide_objects = bool(on)
+
+    def _guide_mask(self):
+        """the objects mask of the guides this state makes (0: rt_denoise_guide and rt_denoise themselves)"""
+        return guide_objects_of(self.mode) if self.guide_objects else 0
+
     # ---- the denoise filter (include/rt.h "denoise"; single process, no tiles)
     def _denoise_check(self, levels, sigma_l, sigma_z):
         """(no device: the checks come before any allocation)"""
@@ -378,7 +397,7 @@ class RenderState:
         state = self._noise_or_raise()
         counts = self.counts.ptr if self.counts is not None else None
         self.ctx.denoise(self.width, self.height, self.accum.ptr, self.ids.ptr, state, counts, self.iteration, out.ptr,
-                         levels=levels, sigma_l=sigma_l, sigma_z=sigma_z)
+                         levels=levels, sigma_l=sigma_l, sigma_z=sigma_z, objects=self._guide_mask())
 
     def denoise(self, levels=5, sigma_l=4.0, sigma_z=1.0):
         """The frame through the variance-guided a-trous filter (rt_denoise): float32 [H, W, 4],
@@ -464,7 +483,8 @@ class RenderState:
                 self.ctx.set_adaptive(self.counts.ptr, **self.adaptive)
         new = 0 if t["latest"] is None else 1 - t["latest"]
         out = t["sets"][new]
-        self.ctx.denoise_guide(w, h, t["ids"].ptr, out["nz"].ptr, t["dz"].ptr)   # before update() moves the camera
+        # (before update() moves the camera)
+        self.ctx.denoise_guide(w, h, t["ids"].ptr, out["nz"].ptr, t["dz"].ptr, objects=self._guide_mask())
         hist = None
         if t["latest"] is not None:
             old = t["sets"][t["latest"]]

@@ -287,6 +287,17 @@ public:
      * *summary (if given) receives the last summary (zeroed when nothing was rendered). */
     uint32_t render_adaptive(uint32_t max_samples, uint32_t batch = 16, rt_adaptive_summary* summary = nullptr);
 
+    /* The guide with objects (rt.h "denoise / Guide with objects").  Off (the default): the guide
+     * of denoise, denoised_rgba8, temporal_step, temporal_frame and temporal_rgba8 is
+     * rt_denoise_guide's, for which the W8 balls and the W9E2 / W9E3 holdout plane are background.
+     * On: it is rt_denoise_guide_objects' with rt_guide_objects(mode()): those pixels get the
+     * object's normal and depth, and a history; a mode without such objects is not changed.
+     * Throws once temporal accumulation is enabled (a history's guide comes from one definition:
+     * set it before enable_temporal); load_scene keeps it.  With a library that lacks the entry
+     * points the first use throws RT_E_UNSUPPORTED. */
+    void set_guide_objects(bool on);
+    bool guide_objects() const { return guide_objects_; }
+
     /* The frame through the variance-guided a-trous filter (rt.h "denoise", rt_denoise): linear
      * RGBA32F, H x W x 4, alpha 1.  Needs enable_noise() and iteration() >= 2; under adaptive
      * sampling every pixel's variance uses its own sample count.  The accumulation, the ids and
@@ -343,6 +354,7 @@ private:
     void release();
     DeviceArray<float> denoise_device(uint32_t levels, float sigma_l, float sigma_z) const;
     DeviceArray<float> temporal_device(uint32_t levels, float sigma_l, float sigma_z) const;
+    uint32_t guide_mask(const char* who) const;
 
     GpuHandles& gpu_;
     RenderOptions opts_;
@@ -373,6 +385,7 @@ private:
         DeviceArray<float> color, mom, nz;
         DeviceArray<uint32_t> len;
     };
+    bool guide_objects_ = false;       // set_guide_objects
     bool temporal_ = false;
     DeviceArray<float> tp_cur_, tp_dz_;
     DeviceArray<uint32_t> tp_ids_;

@@ -926,9 +926,11 @@ int rt_denoise_level_times(rt_ctx* ctx, float* level_ms, uint32_t* lds_form);
  * A fresh or disoccluded pixel so borrows its neighbours' spread (one sample has none of its
  * own) and is blurred more.  Default min_len = 4.
  *
- * Limits: reprojection follows the primary hit, so what a mirror or glass surface shows (the
- * W8 and W9E1 balls) lags behind the camera, as in SVGF; background pixels keep no history;
- * the scene is static.
+ * Limits: reprojection follows the primary hit, so what a mirror or glass surface shows lags
+ * behind the camera, as in SVGF; background pixels keep no history; the scene is static.  With
+ * rt_denoise_guide the analytic W8 balls and the W9E2 / W9E3 holdout plane are background: they
+ * keep no history at all, even under a still camera.  With the guide of "denoise / Guide with
+ * objects" below they keep one, and what a ball shows lags.
  *
  * Both calls are asynchronous on the context stream, take DEVICE pointers (prev_uniform: host)
  * and follow rt_denoise_filter's argument rules: RT_E_INVALID for a null context or buffer,
@@ -952,6 +954,72 @@ int rt_temporal_variance(rt_ctx* ctx, uint32_t width, uint32_t height, const flo
  * rt_temporal_accumulate and rt_temporal_variance (0 when that call was not timed), and the form
  * the latter ran (or NULL: 0 every neighbour from global memory, 1 the LDS tile).  Synchronizes. */
 int rt_temporal_times(rt_ctx* ctx, float* accumulate_ms, float* variance_ms, uint32_t* variance_lds_form);
+
+/* ---- denoise / Guide with objects (DESIGN.md section 4 "Guide with objects") ----
+ * rt_render's primary id is set on a mesh hit alone: the two analytic balls of W8E1..W8E3 and
+ * the holdout plane y = 0 of W9E2 / W9E3 leave it at 0xFFFFFFFF, and rt_denoise_guide classes
+ * their pixels as background.  This guide gives those pixels the object's {N, z} and {dzx, dzy}
+ * instead, so that the filter separates them from the environment and temporal accumulation
+ * keeps their history.  A new entry point: rt_denoise_guide and rt_denoise are as they were, and
+ * the hosts use this guide only when asked (set_guide_objects, --guide-objects).  Pinned f32
+ * arithmetic as "denoise": no contraction, correctly rounded / and sqrt, every line one
+ * operation, the same dot, normalize, |a| and max; a vector line is that operation per component.
+ *
+ * The camera and the pixel-centre ray (e, w(x, y)) are exactly those of "denoise / Guide".
+ * `objects` is a mask of the RT_GUIDE_* bits below.
+ *
+ * A pixel whose id is not 0xFFFFFFFF is rt_denoise_guide's, its lines and its bits: a valid id,
+ * an id >= ntris (background), and every way such a pixel becomes background there.
+ *
+ * A pixel whose id is 0xFFFFFFFF tests the objects of the mask on (e, w), w = w(x, y), with the
+ * shader's own tests in the shader's order, on the interval [tmin, tmax], tmax = 5000.0f at the
+ * start, every accept lowering tmax to its distance; tmin is the path kernels' ETA of the modes
+ * that hold the object: 0.01f for the balls, 0.0001f for the plane.
+ *   RT_GUIDE_BALLS: the mirror ball C = (420, 90, 370), then the glass ball C = (130, 90, 250),
+ *   both of radius r = 90.0f (intersect_sphere, w8e1.wgsl:352-376):
+ *       oc = e - C;  a = dot(w, w);  b2 = dot(oc, w);  c = dot(oc, oc) - r * r
+ *       D = b2 * b2 - a * c;  no hit when D < 0;  sq = sqrtf(D)
+ *       t = (-b2 - sq) / a;  if (t < tmin || t > tmax) t = (-b2 + sq) / a
+ *       no hit when that t < tmin || t > tmax;  else accepted: tmax = t
+ *   RT_GUIDE_PLANE, after the balls: the plane y = 0, n = (0, 1, 0) (intersect_plane,
+ *   w9e2.wgsl:388-404):
+ *       pn = ((0.0f - e.x) * 0.0f + (0.0f - e.y) * 1.0f) + (0.0f - e.z) * 0.0f
+ *       pd = (w.x * 0.0f + w.y * 1.0f) + w.z * 0.0f
+ *       t = pn / pd;  accepted iff !(t < tmin) && !(t > tmax) && t is finite && t > 0 && pd != 0
+ *       then tmax = t
+ *   (the shader accepts a NaN distance; the guide makes no surface of it: such a test accepts
+ *   nothing and an earlier ball stays).
+ * With no accept the pixel is BACKGROUND, as in rt_denoise_guide: N = 0, z = -1, dz = 0.  Else,
+ * for the last accepted object at distance t = tmax:
+ *       a ball:  P = e + w * t;  N = normalize(P - C)           the plane:  N = (0, 1, 0)
+ *       if (dot(N, w) > 0) N = -N                     (an eye inside a ball or below the plane)
+ *       z = t;  den = dot(w, N);  num = z * den
+ *       dzx = num / dot(w(x+1, y), N) - z;  dzy = num / dot(w(x, y+1), N) - z
+ * the tangent plane at P under the neighbours' rays, as the triangles' lines; a dzx or dzy that
+ * is not finite becomes 0.
+ *
+ * rt_guide_objects names the mask of a mode: RT_GUIDE_BALLS for W8E1..W8E3, RT_GUIDE_PLANE for
+ * W9E2 and W9E3, 0 for every other rt_mode (W6E3 has the balls but no primary-id guide: it is no
+ * path mode); RT_E_INVALID for a value that is no rt_mode or a null pointer.
+ *
+ * Limits: the centre ray decides the object, the last iteration's jittered ray the id: at an
+ * object's silhouette the two may disagree by a pixel.  What a mirror or glass ball shows lags
+ * behind the camera, as any reflection does under "temporal accumulation". */
+#define RT_GUIDE_BALLS 1u /* the mirror and the glass ball of W8E1..W8E3 */
+#define RT_GUIDE_PLANE 2u /* the holdout plane y = 0 of W9E2 and W9E3 */
+
+int rt_guide_objects(int mode, uint32_t* objects);
+
+/* rt_denoise_guide with the objects of the mask under the pixels that have no id.  Arguments,
+ * alignment, overlap and readiness rules are rt_denoise_guide's; RT_E_INVALID also for a bit
+ * outside RT_GUIDE_BALLS | RT_GUIDE_PLANE.  objects == 0 gives rt_denoise_guide's bytes. */
+int rt_denoise_guide_objects(rt_ctx* ctx, uint32_t objects, uint32_t width, uint32_t height, const uint32_t* ids_dev,
+                             float* nz_dev, float* dz_dev);
+
+/* rt_denoise with that guide; every other argument and rule is rt_denoise's. */
+int rt_denoise_objects(rt_ctx* ctx, uint32_t objects, uint32_t width, uint32_t height, const float* accum_dev,
+                       const uint32_t* ids_dev, const rt_noise_state* state_dev, const uint32_t* count_dev, uint32_t n,
+                       uint32_t levels, float sigma_l, float sigma_z, float* out_rgba_dev);
 
 /* ---- multi-GPU: the tile gather over RCCL -----------------
  * One process per GPU, each with its own context: every rank renders its

@@ -1,0 +1,383 @@
+"""The guide with objects without a GPU: the numpy float32 restatement (tests/guide_objects_ref.py)
+on hand-made cameras, its effect on the oracle's W8E1 and W9E2 frames through the filter and
+through temporal accumulation, the entry points at the ABI boundary (include/rt.h "denoise /
+Guide with objects") and the hosts' refusals."""
+import ctypes as C
+import os
+import subprocess
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+import denoise_ref as DR
+import guide_objects_ref as GR
+import noise_ref as NR
+import temporal_ref as TR
+from conftest import ROOT, model
+from parity_util import CORNELL_CAM, TEAPOT_CAM
+
+f32 = np.float32
+NONE = 0xFFFFFFFF
+BALLS, PLANE = GR.RT_GUIDE_BALLS, GR.RT_GUIDE_PLANE
+# one triangle far from every camera below, so that "a valid id" exists
+VERTS = np.array([[1000.0, 1000.0, 1000.0], [1001.0, 1000.0, 1000.0], [1000.0, 1001.0, 1000.0]], f32)
+TRIS = np.array([[0, 1, 2, 0]], np.uint32)
+
+
+def u32(a):
+    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
+
+
+def uniform(eye, at, up=(0.0, 1.0, 0.0), cc=1.0, aspect=1.0):
+    return SimpleNamespace(camera_pos=eye, camera_look_at=at, camera_up=up, camera_constant=cc, aspect_ratio=aspect)
+
+
+def rays(u, w, h):
+    cam = TR.camera(u)
+    y, x = np.meshgrid(np.arange(h, dtype=np.uint32), np.arange(w, dtype=np.uint32), indexing="ij")
+    return cam[0], TR.ray(cam, w, h, x, y)
+
+
+def none_ids(h, w):
+    return np.full((h, w), NONE, np.uint32)
+
+
+def rms(a, b, mask=None):
+    d = (a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)) ** 2
+    return float(np.sqrt(np.mean(d if mask is None else d[mask])))
+
+
+# ---- the restatement on hand-made cameras ------------------------------------------
+def test_no_objects_and_every_pixel_with_an_id_are_the_plain_guide():
+    rng = np.random.default_rng(1)
+    h, w = 23, 37
+    u = uniform(*CORNELL_CAM[:2], aspect=w / h)
+    # ids that mix no id, the valid id and ids past the mesh; a triangle the camera does see
+    verts = np.array([[0.0, 0.0, 0.0], [556.0, 0.0, 0.0], [0.0, 548.0, 559.0], [556.0, 548.0, 559.0]], f32)
+    tris = np.array([[0, 1, 2, 0], [1, 3, 2, 0]], np.uint32)
+    ids = rng.choice(np.array([NONE, 0, 1, 2, 7, 0xFFFFFFFE], np.uint32), (h, w))
+    want = DR.guide(u, w, h, ids, verts, tris)
+    got0 = GR.guide(u, w, h, ids, verts, tris, 0)
+    assert np.array_equal(u32(got0[0]), u32(want[0])) and np.array_equal(u32(got0[1]), u32(want[1]))
+    assert (want[0][..., 3] > 0).sum() > 0
+    for objects in (BALLS, PLANE, BALLS | PLANE):
+        nz, dz = GR.guide(u, w, h, ids, verts, tris, objects)
+        has_id = ids != NONE
+        assert np.array_equal(u32(nz)[has_id], u32(want[0])[has_id]), objects
+        assert np.array_equal(u32(dz)[has_id], u32(want[1])[has_id]), objects
+        assert (nz[..., 3][~has_id] > 0).sum() > 0, objects      # ... and the others do change
+
+
+def test_eye_inside_the_glass_ball_sees_its_far_side_everywhere():
+    h, w = 9, 11
+    eye = (130.0, 90.0, 250.0 - 30.0)
+    u = uniform(eye, (130.0, 90.0, 400.0), aspect=w / h)
+    nz, dz = GR.guide(u, w, h, none_ids(h, w), VERTS, TRIS, BALLS)
+    e, d = rays(u, w, h)
+    assert np.all(nz[..., 3] > 0)
+    # N faces the eye: it points inwards, against the ray
+    assert np.all(TR._dot([nz[..., k] for k in range(3)], d) < 0)
+    # z is the far root: the point lies on the sphere, beyond the centre plane
+    P = np.stack([e[k] + d[k].astype(np.float64) * nz[..., 3] for k in range(3)], axis=-1)
+    r = np.linalg.norm(P - np.array(GR.GLASS, np.float64), axis=-1)
+    assert np.allclose(r, 90.0, rtol=1e-5)
+    assert np.all(nz[..., 3] >= 60.0 - 1e-3) and nz[h // 2, w // 2, 3] > 119.0
+    assert np.all(np.isfinite(dz))
+
+
+def test_mirror_ball_wins_on_the_line_through_both_centres():
+    h, w = 7, 7
+    g, m = np.array(GR.GLASS, np.float64), np.array(GR.MIRROR, np.float64)
+    axis = (m - g) / np.linalg.norm(m - g)
+    eye = m + axis * 300.0          # beyond the mirror ball, looking back through both
+    u = uniform(tuple(eye), tuple(g), cc=4.0)
+    nz, _ = GR.guide(u, w, h, none_ids(h, w), VERTS, TRIS, BALLS)
+    c = nz[h // 2, w // 2]
+    assert abs(c[3] - 210.0) < 0.5          # the mirror ball's near side, not the glass ball's (300 + 314 - 90)
+    assert np.allclose(c[:3], axis, atol=2e-2)
+    # ... and with the mirror ball out of the interval's reach the glass ball would answer: the
+    # accept really lowered tmax (the second test ran on [0.01, 210])
+    e, d = rays(u, w, h)
+    hit, t = GR._sphere(e, d, GR.ETA_BALLS, GR.TMAX, GR.GLASS, GR.RADIUS)
+    assert hit[h // 2, w // 2] and t[h // 2, w // 2] > 500.0
+
+
+def test_a_ray_that_misses_by_a_pixel_is_background():
+    h, w = 5, 64
+    eye = (420.0, 90.0, 370.0 - 1000.0)
+    # a wide frame across the mirror ball's silhouette: the ball spans atan(90 / 1000) of it
+    u = uniform(eye, (420.0, 90.0, 370.0), cc=8.0, aspect=w / h)
+    nz, dz = GR.guide(u, w, h, none_ids(h, w), VERTS, TRIS, BALLS)
+    row = nz[h // 2, :, 3] > 0
+    # the run of pixels around the centre (the glass ball shows further along the row)
+    assert row[w // 2 - 1] and row[w // 2]
+    first = w // 2 - 1 - int(np.argmin(row[w // 2 - 1::-1]))  + 1
+    last = w // 2 + int(np.argmin(row[w // 2:])) - 1
+    assert 0 < first <= last < w - 1 and np.all(row[first:last + 1]) and not row[first - 1] and not row[last + 1]
+    for x in (first - 1, last + 1):
+        assert np.array_equal(nz[h // 2, x], np.array([0, 0, 0, -1], f32)) and np.all(dz[h // 2, x] == 0)
+    # the discriminant decides it: positive on the last pixel inside, negative on the first outside
+    e, d = rays(u, w, h)
+    oc = [e[k] - GR.MIRROR[k] for k in range(3)]
+    D = TR._dot(oc, d) ** 2 - TR._dot(d, d) * (TR._dot(oc, oc) - f32(8100.0))
+    assert D[h // 2, last] >= 0 > D[h // 2, last + 1]
+
+
+def test_eye_below_the_plane_sees_its_underside():
+    h, w = 9, 12
+    u = uniform((0.0, -2.0, 5.0), (0.0, 0.0, 0.0), aspect=w / h)
+    nz, dz = GR.guide(u, w, h, none_ids(h, w), VERTS, TRIS, PLANE)
+    surf = nz[..., 3] > 0
+    assert surf.sum() > 0 and not surf.all()
+    assert np.all(nz[surf][:, :3] == np.array([0.0, -1.0, 0.0], f32))
+    above = GR.guide(uniform((0.0, 2.0, 5.0), (0.0, 0.0, 0.0), aspect=w / h), w, h, none_ids(h, w), VERTS, TRIS, PLANE)[0]
+    assert np.all(above[above[..., 3] > 0][:, :3] == np.array([0.0, 1.0, 0.0], f32))
+    # the balls' bit alone leaves a plane scene as background
+    assert not np.any(GR.guide(u, w, h, none_ids(h, w), VERTS, TRIS, BALLS)[0][..., 3] > 0)
+
+
+def test_horizontal_view_with_an_odd_height_has_a_background_middle_row():
+    h, w = 9, 8
+    u = uniform((0.0, 1.0, 0.0), (0.0, 1.0, 10.0), aspect=w / h)
+    nz, dz = GR.guide(u, w, h, none_ids(h, w), VERTS, TRIS, PLANE)
+    _, d = rays(u, w, h)
+    assert np.all(d[1][h // 2] == 0)                    # dot(w, n) == 0: 1 / 0 is infinite
+    assert np.all(nz[h // 2] == np.array([0, 0, 0, -1], f32)) and np.all(dz[h // 2] == 0)
+    assert np.all(nz[:h // 2, :, 3] == -1)              # the rows above look up
+    assert np.all(nz[h // 2 + 1:, :, 3] > 0)            # the rows below see the plane
+    assert np.all(np.isfinite(dz))
+
+
+def test_a_plane_hit_beyond_5000_is_background():
+    h, w = 1, 4
+    # looking down by 1 in 6000 from height 1: the hit lies 6000 away; by 1 in 4000: 4000 away
+    far = GR.guide(uniform((0.0, 1.0, 0.0), (0.0, 0.0, 6000.0), cc=50.0), w, h, none_ids(h, w), VERTS, TRIS, PLANE)[0]
+    near = GR.guide(uniform((0.0, 1.0, 0.0), (0.0, 0.0, 4000.0), cc=50.0), w, h, none_ids(h, w), VERTS, TRIS, PLANE)[0]
+    assert np.all(far[..., 3] == -1)
+    assert np.all((near[..., 3] > 3900) & (near[..., 3] < 4100))
+
+
+def test_plane_dz_is_the_difference_of_neighbouring_z():
+    h, w = 12, 16
+    u = uniform(*TEAPOT_CAM[:2], cc=TEAPOT_CAM[3], aspect=w / h)
+    nz, dz = GR.guide(u, w, h, none_ids(h, w), VERTS, TRIS, PLANE)
+    z = nz[..., 3]
+    both_x = (z[:, :-1] > 0) & (z[:, 1:] > 0)
+    both_y = (z[:-1] > 0) & (z[1:] > 0)
+    assert both_x.sum() > 20 and both_y.sum() > 20
+    # z' - z against num / dot(w', N) - z: two roundings of values near z, a few ulp of z
+    ulp = np.spacing(np.maximum(z[:, :-1], z[:, 1:]))
+    assert np.all(np.abs((z[:, 1:] - z[:, :-1]) - dz[:, :-1, 0])[both_x] <= 4 * ulp[both_x])
+    ulp = np.spacing(np.maximum(z[:-1], z[1:]))
+    assert np.all(np.abs((z[1:] - z[:-1]) - dz[:-1, :, 1])[both_y] <= 4 * ulp[both_y])
+
+
+# ---- the oracle's frames: the filter -------------------------------------------------
+def _spatial_case(O, obj, cam, W, H, mode, env, objects):
+    m = O.load_obj(model(obj))
+    sc = O.SceneRef(m, O.build_bsp(m), None, env)
+    u = O.make_uniform(*cam, W, H)
+    region = (0, 0, W, H)
+    ref = O.render(sc, u, mode, "BSP", region, 0, 512)[0]
+    noisy, ids, _ = O.render(sc, u, mode, "BSP", region, 0, 16)
+    rec = np.zeros((W * H, 16, 4), f32)
+    zero = np.zeros((H, W, 4), f32)
+    for i in range(16):
+        a = O.render(sc, u, mode, "BSP", region, i, 1, accum=zero.copy())[0]
+        rec[:, i, :3] = (a[..., :3] * f32(i + 1)).reshape(-1, 3)
+    state = NR.accumulate(rec)
+    parent = GR.denoise(noisy, ids, state, u, m.pos, m.idx, 0, n=16)
+    ours = GR.denoise(noisy, ids, state, u, m.pos, m.idx, objects, n=16)
+    assert np.array_equal(u32(parent), u32(DR.denoise(noisy, ids, state, u, m.pos, m.idx, n=16)))
+    obj_px = GR.object_mask(u, W, H, ids, m.pos, m.idx, objects)
+    mesh_px = DR.guide(u, W, H, ids, m.pos, m.idx)[0][..., 3] > 0
+    return SimpleNamespace(ref=ref, noisy=noisy, parent=parent, ours=ours, obj=obj_px, mesh=mesh_px)
+
+
+@pytest.fixture(scope="module")
+def w9e2_16spp(oracle):
+    return _spatial_case(oracle, "teapot.obj", TEAPOT_CAM, 96, 54, "W9E2", (1.0, 1.0, 1.0), PLANE)
+
+
+@pytest.fixture(scope="module")
+def w8e1_16spp(oracle):
+    return _spatial_case(oracle, "CornellBox.obj", CORNELL_CAM, 64, 64, "W8E1", (0.1, 0.3, 0.6), BALLS)
+
+
+def halfway(ratio):
+    """the bound of an RMS inequality: halfway between the ratio the restatement measured and 1, so
+    that half the measured gain is what passes -- not a near tie"""
+    return 0.5 * (1.0 + ratio)
+
+
+def _report(name, c):
+    r = SimpleNamespace(raw_o=rms(c.noisy, c.ref, c.obj), par_o=rms(c.parent, c.ref, c.obj), our_o=rms(c.ours, c.ref, c.obj),
+                        par_m=rms(c.parent, c.ref, c.mesh), our_m=rms(c.ours, c.ref, c.mesh),
+                        raw_f=rms(c.noisy, c.ref), par_f=rms(c.parent, c.ref), our_f=rms(c.ours, c.ref))
+    print(f"{name}: objects {c.obj.mean():.4f} of the frame; object px raw {r.raw_o:.4g} parent {r.par_o:.4g} "
+          f"ours {r.our_o:.4g} (ratio {r.our_o / r.par_o:.4g}); mesh px parent {r.par_m:.4g} ours {r.our_m:.4g} "
+          f"(ratio {r.our_m / r.par_m:.6g}); frame raw {r.raw_f:.4g} parent {r.par_f:.4g} ours {r.our_f:.4g} "
+          f"(ours / raw {r.our_f / r.raw_f:.4g})")
+    return r
+
+
+def test_w9e2_plane_16spp_filters_better_with_the_object_guide(w9e2_16spp):
+    """teapot.obj, W9E2, BSP, TEAPOT_CAM, white environment, 96 x 54, 16 spp through five levels
+    against 512 spp; RMS over rgb.  The plane is 25.68 % of the frame.  The restatement measures on
+    the plane's pixels 0.08982 unfiltered, 0.06805 with the parent's guide (objects 0) and 0.04657
+    with the plane in the guide: ratio 0.6844, asserted at halfway to 1.  The mesh pixels: 0.1817
+    both ways (ratio 0.99995)."""
+    c = w9e2_16spp
+    r = _report("W9E2 16 spp", c)
+    assert c.obj.mean() >= 0.20
+    assert r.our_o < r.par_o
+    assert r.our_o <= halfway(0.6844) * r.par_o
+    assert abs(r.our_m / r.par_m - 1.0) <= 0.01
+
+
+def test_w8e1_balls_16spp_filter_better_with_the_object_guide(w8e1_16spp):
+    """CornellBox.obj, W8E1, BSP, CORNELL_CAM, environment (0.1, 0.3, 0.6), 64 x 64, 16 spp through
+    five levels against 512 spp.  The balls are 6.49 % of the frame.  On their pixels the
+    restatement measures 0.2205 unfiltered, 0.5289 with the parent's guide -- 2.4 x worse than not
+    filtering -- and 0.2108 with the balls in the guide: ratio 0.3985.  The whole frame: 0.194
+    unfiltered, 0.226 with the parent's guide (it fails the second assertion), 0.1892 with the
+    balls: ratio to unfiltered 0.9753.  Both asserted at halfway to 1.  The mesh pixels: 0.1945
+    against 0.1946 (ratio 1.00005)."""
+    c = w8e1_16spp
+    r = _report("W8E1 16 spp", c)
+    assert c.obj.mean() >= 0.05
+    assert r.our_o < r.par_o
+    assert r.our_o <= halfway(0.3985) * r.par_o
+    assert r.our_f < r.raw_f
+    assert r.our_f <= halfway(0.9753) * r.raw_f
+    assert not r.par_f < r.raw_f            # what the parent's guide does to this frame
+    assert abs(r.our_m / r.par_m - 1.0) <= 0.01
+
+
+# ---- the oracle's frames: temporal accumulation --------------------------------------
+def _temporal_case(O, obj, cam, W, H, mode, env, objects, eye_step, at_step):
+    """16 frames of 1 spp, frame t at eye + t eye_step, look-at + t at_step (along x), integrated
+    and filtered, with the parent's guide and with the objects, against 512 spp at the last camera"""
+    m = O.load_obj(model(obj))
+    sc = O.SceneRef(m, O.build_bsp(m), None, env)
+    eye, tgt, up, cc = cam
+    region = (0, 0, W, H)
+    zero = np.zeros((H, W, 4), f32)
+
+    def uni(t):
+        return O.make_uniform((eye[0] + eye_step * t, eye[1], eye[2]), (tgt[0] + at_step * t, tgt[1], tgt[2]), up, cc, W, H)
+
+    par = our = None
+    for t in range(16):
+        a, ids, _ = O.render(sc, uni(t), mode, "BSP", region, t, 1, accum=zero.copy())
+        par = GR.step(par, a, ids, t, 1, uni(t), m.pos, m.idx, 0)
+        our = GR.step(our, a, ids, t, 1, uni(t), m.pos, m.idx, objects)
+    ref = O.render(sc, uni(15), mode, "BSP", region, 0, 512)[0]
+    obj_px = GR.object_mask(uni(15), W, H, ids, m.pos, m.idx, objects)
+    r = SimpleNamespace(share=float(obj_px.mean()), par_len=float(par["len"][obj_px].mean()),
+                        our_len=float(our["len"][obj_px].mean()), par=rms(TR.filtered(par), ref, obj_px),
+                        our=rms(TR.filtered(our), ref, obj_px))
+    print(f"{mode} eye {eye_step:+g} look-at {at_step:+g} per frame: objects {r.share:.4f} of the frame; mean history "
+          f"parent {r.par_len:.4g} ours {r.our_len:.4g}; object px parent {r.par:.4g} ours {r.our:.4g} "
+          f"(ratio {r.our / r.par:.4g})")
+    return r
+
+
+# (mode, model, camera, W, H, environment, objects, eye step, look-at step) and what the restatement
+# measures: the mean history length on the object pixels with the objects (the parent's is 1.0 in
+# every row), the object pixels' RMS with the parent's guide and with the objects, their ratio
+TEMPORAL = {"W9E2-moving": (("W9E2", "teapot.obj", TEAPOT_CAM, 96, 54, (1.0, 1.0, 1.0), PLANE, 0.1, 0.05),
+                            (11.94, 0.1100, 0.0643, 0.5844)),
+            "W9E2-still": (("W9E2", "teapot.obj", TEAPOT_CAM, 96, 54, (1.0, 1.0, 1.0), PLANE, 0.0, 0.0),
+                           (15.46, 0.1076, 0.06006, 0.5580)),
+            "W8E1-moving": (("W8E1", "CornellBox.obj", CORNELL_CAM, 64, 64, (0.1, 0.3, 0.6), BALLS, 6.0, 3.0),
+                            (12.72, 0.5628, 0.3800, 0.6752)),
+            "W8E1-still": (("W8E1", "CornellBox.obj", CORNELL_CAM, 64, 64, (0.1, 0.3, 0.6), BALLS, 0.0, 0.0),
+                           (14.83, 0.6959, 0.2109, 0.3031))}
+
+
+@pytest.mark.parametrize("case", sorted(TEMPORAL))
+def test_16_frames_of_1spp_keep_a_history_on_the_objects(oracle, case):
+    """16 frames of 1 spp (frame t renders iteration t), integrated and filtered, against 512 spp at
+    the last camera, on the object pixels.  Moving: the eye +0.1 (W9E2) or +6 (W8E1) per frame along
+    x, the look-at half that.  Measured by the restatement (TEMPORAL above): with the parent's guide
+    every object pixel has history length 1; with the objects the mean is 11.94 / 15.46 (W9E2 moving /
+    still) and 12.72 / 14.83 (W8E1), and the RMS falls from 0.1100 to 0.0643, 0.1076 to 0.0601, 0.5628
+    to 0.3800 and 0.6959 to 0.2109.  Each ratio is asserted at halfway to 1."""
+    (mode, obj, cam, W, H, env, objects, eye_step, at_step), (_, _, _, ratio) = TEMPORAL[case]
+    r = _temporal_case(oracle, obj, cam, W, H, mode, env, objects, eye_step, at_step)
+    assert r.share >= (0.20 if objects == PLANE else 0.05)
+    assert r.par_len == 1.0
+    assert r.our_len > 8.0
+    assert r.our < r.par
+    assert r.our <= halfway(ratio) * r.par
+
+
+# ---- the ABI ------------------------------------------------------------------------
+NAMES = ("rt_guide_objects", "rt_denoise_guide_objects", "rt_denoise_objects")
+
+
+def test_symbols_exported(rt):
+    so = os.path.join(ROOT, "02562_raytracer_amd", "lib02562rt.so")
+    out = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
+    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    assert set(NAMES) <= exported, set(NAMES) - exported
+    assert set(NAMES) <= set(rt._ffi.SIGNATURES)
+    assert (rt._ffi.RT_GUIDE_BALLS, rt._ffi.RT_GUIDE_PLANE) == (1, 2)
+
+
+def test_null_context_is_invalid(rt):
+    L, F = rt.lib(), rt._ffi
+    calls = [lambda: L.rt_denoise_guide_objects(None, 1, 4, 4, None, None, None),
+             lambda: L.rt_denoise_objects(None, 1, 4, 4, None, None, None, None, 2, 5, 4.0, 1.0, None)]
+    for name, call in zip(NAMES[1:], calls):
+        assert call() == F.RT_E_INVALID, name
+        assert name.encode() in L.rt_last_error(None), name
+
+
+def test_guide_objects_of_every_mode(rt):
+    L, F = rt.lib(), rt._ffi
+    assert F.RT_MODE_COUNT == 31
+    want = {"W8E1": F.RT_GUIDE_BALLS, "W8E2": F.RT_GUIDE_BALLS, "W8E3": F.RT_GUIDE_BALLS,
+            "W9E2": F.RT_GUIDE_PLANE, "W9E3": F.RT_GUIDE_PLANE}
+    for mode in range(F.RT_MODE_COUNT):
+        out = C.c_uint32(0xDEAD)
+        assert L.rt_guide_objects(mode, C.byref(out)) == F.RT_OK, mode
+        assert out.value == want.get(F.MODE_TABLE[mode].name, 0), F.MODE_TABLE[mode].name
+        assert rt.guide_objects_of(F.MODE_TABLE[mode].name) == out.value
+    assert want.keys() <= set(F.NOISE_MODES) and "W6E3" not in F.NOISE_MODES
+    for bad in (31, -1):
+        out = C.c_uint32(0xDEAD)
+        assert L.rt_guide_objects(bad, C.byref(out)) == F.RT_E_INVALID and out.value == 0xDEAD
+    assert L.rt_guide_objects(F.RT_MODE_W8E1, None) == F.RT_E_INVALID
+
+
+# ---- the hosts' refusals ------------------------------------------------------------
+@pytest.mark.parametrize("flags", [[], ["--spp", "4"], ["--noise-target", "0.05"], ["--denoise-levels", "3"]])
+def test_rt_render_refuses_guide_objects_without_a_filter(tmp_path, flags):
+    # before it touches a device or a file
+    exe = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
+    r = subprocess.run([exe, "--scene", "W8 E1 Cornell Box Balls", "--res", "36x20", "--guide-objects", *flags,
+                        "--out", str(tmp_path / "frame")], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 1 and ("--guide-objects" in r.stderr or "--denoise" in r.stderr), r.stderr
+    if flags != ["--denoise-levels", "3"]:
+        assert "--guide-objects" in r.stderr, r.stderr
+    assert r.stdout == "" and os.listdir(tmp_path) == []
+
+
+def test_render_state_set_guide_objects(rt):
+    # (no device: the flag is host state)
+    rs = rt.RenderState.__new__(rt.RenderState)
+    rs.temporal, rs.mode = None, "W8E1"
+    assert rs.guide_objects is False and rs._guide_mask() == 0
+    rs.set_guide_objects(True)
+    assert rs.guide_objects is True and rs._guide_mask() == rt._ffi.RT_GUIDE_BALLS
+    rs.mode = "W7E3"
+    assert rs._guide_mask() == 0                  # a mode without objects: the plain guide
+    rs.set_guide_objects(False)
+    rs.temporal = {"latest": None}                # as enable_temporal() leaves it
+    for on in (True, False):
+        with pytest.raises(ValueError, match="before enable_temporal"):
+            rs.set_guide_objects(on)
+    assert rs.guide_objects is False
