@@ -3,9 +3,11 @@ analytic W2 / W3 modes (test infrastructure; shares no code with the kernel),
 and the inputs the CPU and GPU tests of those modes share."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import native_build
+from parity_util import COUNT_KEYS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "analytic_ref.c")
@@ -32,10 +34,7 @@ def texture_6x4():
 
 def build(out_dir):
     """Compile analytic_ref.c into out_dir and load it."""
-    so = os.path.join(str(out_dir), "libanalytic_ref.so")
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, SRC, "-lm"], check=True,
-                   timeout=120)
-    lib = C.CDLL(so)
+    lib = native_build.shared_lib(SRC, out_dir, ["-O2", "-ffp-contract=off"], libs=["-lm"], timeout=120)
     vp = C.c_void_p
     lib.analytic_ref_render.restype = C.c_int
     lib.analytic_ref_render.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -58,7 +57,7 @@ def render(lib, uniform, jitter, region, mode, texture=None, only_sample=-1):
                                  0 if T is None else T.shape[0], x0, y0, w, h, MODES[mode], only_sample,
                                  acc.ctypes.data, ids.ctypes.data, cnt.ctypes.data)
     assert rc == 0, f"analytic_ref_render failed ({rc})"
-    return acc, ids, {n: int(c) for n, c in zip(("samples", "primary", "shadow", "bounce"), cnt)}
+    return acc, ids, {n: int(c) for n, c in zip(COUNT_KEYS, cnt)}
 
 
 def tex_sample(lib, texture, u, v, nearest):

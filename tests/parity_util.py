@@ -1,4 +1,7 @@
-"""Shared helpers for GPU-vs-oracle parity tests (test infrastructure)."""
+"""Shared helpers for GPU-vs-oracle parity tests (test infrastructure): the cameras,
+the Scene that holds one mesh on both sides, and the assertions that compare two
+renders (a render is the tuple (accum float32[h, w, 4], ids uint32[h, w], counts)).
+The assertions state their own messages: pytest rewrites asserts in test modules only."""
 import numpy as np
 
 import oracle_ffi as O
@@ -7,8 +10,19 @@ CORNELL_CAM = ((277.0, 275.0, -570.0), (277.0, 275.0, 0.0), (0.0, 1.0, 0.0), 1.0
 BUNNY_CAM = ((-0.02, 0.11, 0.6), (-0.02, 0.11, 0.0), (0.0, 1.0, 0.0), 3.5)
 TEAPOT_CAM = ((0.15, 1.5, 10.0), (0.15, 1.5, 0.0), (0.0, 1.0, 0.0), 2.5)
 BASIC_CAM = ((2.0, 1.5, 2.0), (0.0, 0.5, 0.0), (0.0, 1.0, 0.0), 1.0)
+CAM3 = ((-0.02, 0.11, 0.6), (-0.02, 0.11, 0.0), (0.0, 1.0, 0.0), 3.5)   # configs.py config 3
 
 RADIANCE_TOL = 1e-4   # north_star: image L-infinity < 1e-4 vs the reference path
+COUNT_KEYS = ("samples", "primary", "shadow", "bounce")   # the ray counts every render returns
+
+
+def frame_camera(mesh, back=2.5, constant=1.5):
+    """A camera on the +z side of the mesh's bounding box that frames the whole of it."""
+    V = mesh.arrays()[0][:, :3]
+    lo, hi = V.min(0), V.max(0)
+    c = 0.5 * (lo + hi)
+    r = float(np.abs(hi - lo).max())
+    return (tuple(c + np.array([0.0, 0.0, back * r])), tuple(c), (0.0, 1.0, 0.0), constant)
 
 
 class Scene:
@@ -85,3 +99,46 @@ def compare(gpu, ora, what=""):
     bits = int(((ga.view(np.uint32) != oa.view(np.uint32)) & ~both_nan).sum())
     idm = int((gi != oi).sum())
     return linf + (np.inf if nan_mismatch or inf_mismatch else 0.0), bits, idm
+
+
+def check(gpu, ora, exact=True, counts=True):
+    """GPU render against the oracle's: ids equal, radiance within RADIANCE_TOL and
+    (exact) bit for bit, the four ray counts equal."""
+    linf, bits, idm = compare(gpu, ora)
+    assert idm == 0, f"{idm} primary-hit ids differ"
+    assert linf <= RADIANCE_TOL, f"L-inf {linf}"
+    if exact:
+        assert bits == 0, f"{bits} radiance words differ bitwise (L-inf {linf})"
+    if counts:
+        for k in COUNT_KEYS:
+            assert gpu[2][k] == ora[2][k], (k, gpu[2][k], ora[2][k])
+
+
+def assert_same_render(a, b, counts=COUNT_KEYS):
+    """Two renders of the same thing: radiance bits, ids and the listed counts equal."""
+    wa, wb = np.ascontiguousarray(a[0]).view(np.uint32), np.ascontiguousarray(b[0]).view(np.uint32)
+    assert np.array_equal(wa, wb), (f"radiance differs in {int((wa != wb).sum())} words, "
+                                    f"first at {np.argwhere(wa != wb)[:4].tolist()}")
+    assert np.array_equal(a[1], b[1]), f"primary-hit ids differ at {int((a[1] != b[1]).sum())} pixels"
+    for k in counts:
+        assert a[2][k] == b[2][k], (k, a[2][k], b[2][k])
+
+
+# ---- rt_frame_rgba8's pinned definition ---------------------------------------------
+MIDPOINT_REACH = 1e-10   # |255 * oetf(v) - (k + 0.5)| under which two float64 pow may round a code differently
+
+
+def oetf(v):
+    return np.where(v <= 0.0031308, 12.92 * v, 1.055 * np.power(v, 1.0 / 2.4) - 0.055)
+
+
+def frame_reference(c):
+    """The pinned definition (k_frame's comment) in float64: (code u8, near a rounding midpoint)."""
+    c = np.asarray(c, np.float32)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        x = np.where(c > 0, c, np.float32(0))           # NaN, negatives, -0: 0
+        v = (x * np.sqrt(x)).astype(np.float32)         # pow(x, 1.5) = x * sqrt(x), both rounded to float32
+        v = np.where(v < 1, v, np.float32(1))
+    e = 255.0 * oetf(v.astype(np.float64))
+    near = np.abs(e - np.floor(e) - 0.5) < MIDPOINT_REACH
+    return np.floor(e + 0.5).astype(np.uint8), near

@@ -2,9 +2,10 @@
 brute-force W5 modes (test infrastructure; shares no code with the kernel)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import native_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "sweep_ref.c")
@@ -13,10 +14,7 @@ MODES = {"W5E2": 14, "W5E3": 15, "W5E4": 16, "W5E5": 17}
 
 def build(out_dir):
     """Compile sweep_ref.c into out_dir and load it."""
-    so = os.path.join(str(out_dir), "libsweep_ref.so")
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, SRC, "-lm"], check=True,
-                   timeout=120)
-    lib = C.CDLL(so)
+    lib = native_build.shared_lib(SRC, out_dir, ["-O2", "-ffp-contract=off"], libs=["-lm"], timeout=120)
     vp = C.c_void_p
     lib.sweep_ref_render.restype = C.c_int
     lib.sweep_ref_render.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp,

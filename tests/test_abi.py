@@ -3,10 +3,10 @@ declares, and reports errors as codes (no GPU needed)."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
+import abi_util
 from conftest import ROOT
 
 
@@ -20,9 +20,7 @@ def declared_functions():
 def test_library_exports_every_declared_symbol(rt):
     names = declared_functions()
     assert len(names) >= 40
-    so = os.path.join(ROOT, "02562_raytracer_amd", "lib02562rt.so")
-    out = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
+    exported = abi_util.exported_symbols()
     missing = [n for n in names if n not in exported]
     assert not missing, missing
     # and the Python binding declares a signature for each
@@ -30,8 +28,7 @@ def test_library_exports_every_declared_symbol(rt):
 
 
 def test_library_contains_gfx950_code_object():
-    so = os.path.join(ROOT, "02562_raytracer_amd", "lib02562rt.so")
-    data = open(so, "rb").read()
+    data = open(abi_util.LIB, "rb").read()
     assert b"gfx950" in data
 
 

@@ -4,22 +4,18 @@ restatement tests/adaptive_ref.py against a scalar per-pixel loop, the rule's ed
 min_samples boundaries, rel == target), the ABI's symbols and struct, and the hosts'
 argument checks and tiling refusals."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_util
 import adaptive_ref as AR
+import driver
 import noise_ref as NR
-from conftest import ROOT
+from array_util import u32
 
 f32 = np.float32
 PARAMS = dict(target=0.05, floor=1e-3, min_samples=4)
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def records(npix, n, seed=3):
@@ -155,23 +151,15 @@ NAMES = ("rt_set_adaptive", "rt_adaptive_accumulate", "rt_adaptive_map", "rt_ada
 
 
 def test_symbols_exported(rt):
-    so = os.path.join(ROOT, "02562_raytracer_amd", "lib02562rt.so")
-    out = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    assert set(NAMES) <= exported, set(NAMES) - exported
-    assert set(NAMES) <= set(rt._ffi.SIGNATURES)
+    abi_util.assert_exported(rt, NAMES)
 
 
 def test_struct_size(rt, tmp_path):
     assert C.sizeof(rt._ffi.AdaptiveSummary) == 56
-    src = tmp_path / "sizes.c"
-    src.write_text('#include "rt.h"\n'
-                   "_Static_assert(sizeof(rt_adaptive_summary) == 56, \"rt_adaptive_summary\");\n"
-                   "_Static_assert(__builtin_offsetof(rt_adaptive_summary, max_rel_err) == 40, \"max_rel_err\");\n"
-                   "_Static_assert(RT_ADAPT_PIXEL == 0 && RT_ADAPT_TILE == 1, \"votes\");\n")
-    r = subprocess.run(["cc", "-std=c11", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    abi_util.assert_header_compiles(tmp_path, [
+        '_Static_assert(sizeof(rt_adaptive_summary) == 56, "rt_adaptive_summary");',
+        '_Static_assert(__builtin_offsetof(rt_adaptive_summary, max_rel_err) == 40, "max_rel_err");',
+        '_Static_assert(RT_ADAPT_PIXEL == 0 && RT_ADAPT_TILE == 1, "votes");'])
 
 
 def test_null_context_is_invalid(rt):
@@ -182,12 +170,8 @@ def test_null_context_is_invalid(rt):
               lambda: L.rt_adaptive_map(None, None, None, 4, 1e-3, None),
               lambda: L.rt_adaptive_summarize(None, None, None, 2, 2, 4, 0.1, 1e-3, 16, 1, C.byref(s)),
               lambda: L.rt_adaptive_in_use(None, None, None, None)]
-    for name, call in zip(NAMES, calls_):
-        assert call() == F.RT_E_INVALID, name
-    for name in NAMES[:4]:
-        pass   # (rt_adaptive_in_use sets no message, as rt_empty_pixels_in_use)
-    assert L.rt_adaptive_summarize(None, None, None, 2, 2, 4, 0.1, 1e-3, 16, 1, C.byref(s)) == F.RT_E_INVALID
-    assert b"rt_adaptive_summarize" in L.rt_last_error(None)
+    abi_util.assert_null_context_invalid(rt, dict(zip(NAMES[:4], calls_)))
+    assert calls_[4]() == F.RT_E_INVALID   # (rt_adaptive_in_use sets no message, as rt_empty_pixels_in_use)
 
 
 # ---- the hosts -----------------------------------------------------------------------
@@ -218,17 +202,10 @@ def test_render_state_checks_its_arguments(rt):
 def test_rt_render_refuses_adaptive_on_a_tiled_render(tmp_path, extra, flags):
     # --comm-file tiles the render for any rank count: the C++ RenderState refuses every
     # adaptive call on a tiled state, and the driver before it touches a device or a file
-    exe = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
-    extra = [str(tmp_path / a) if a == "ID" else a for a in extra]
-    r = subprocess.run([exe, "--scene", "W7 E3 Cornell Box", "--res", "36x20", *flags, "--out", str(tmp_path / "frame"),
-                        *extra], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 1 and "--adaptive-target" in r.stderr and "--comm-file" in r.stderr, r.stderr
-    assert r.stdout == "" and os.listdir(tmp_path) == []
+    r = driver.refused(tmp_path, "W7 E3 Cornell Box", [*flags, *extra])
+    assert "--adaptive-target" in r.stderr and "--comm-file" in r.stderr, r.stderr
 
 
 def test_rt_render_refuses_adaptive_with_noise_target(tmp_path):
-    exe = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
-    r = subprocess.run([exe, "--scene", "W7 E3 Cornell Box", "--res", "36x20", "--adaptive-target", "0.05",
-                        "--noise-target", "0.05", "--out", str(tmp_path / "frame")], capture_output=True, text=True,
-                       timeout=60)
-    assert r.returncode == 1 and "--noise-target" in r.stderr and os.listdir(tmp_path) == []
+    r = driver.refused(tmp_path, "W7 E3 Cornell Box", ["--adaptive-target", "0.05", "--noise-target", "0.05"])
+    assert "--noise-target" in r.stderr, r.stderr

@@ -7,18 +7,17 @@ compares two reference renders which must differ in a stated way, so that a
 restatement missing the trap fails.  The inputs are shown not to be vacuous, the
 pinned texture lookup is checked on a 6x4 texture, and the scene tables, the
 ctypes binding, the header and the C++ driver must agree on the nine modes."""
-import json
 import os
-import subprocess
 from importlib import import_module
 
 import numpy as np
 import pytest
 
 import analytic_ffi as A
+import driver
+from array_util import u32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 f32 = np.float32
 W = H = 64
 FRAME = (0, 0, W, H)
@@ -33,17 +32,13 @@ def ref(tmp_path_factory):
     return A.build(tmp_path_factory.mktemp("analytic_ref"))
 
 
-def bits(a):
-    return np.ascontiguousarray(a, f32).view(np.uint32)
-
-
 def same(a, b):
-    return np.array_equal(bits(a), bits(b))
+    return np.array_equal(u32(a), u32(b))
 
 
 def px_differ(a, b):
     """[H, W] bool: pixels whose colour bits differ."""
-    return (bits(a[..., :3]) != bits(b[..., :3])).any(axis=-1)
+    return (u32(a[..., :3]) != u32(b[..., :3])).any(axis=-1)
 
 
 # ------------------------------------------------------------------ numpy float32 second opinion
@@ -394,8 +389,7 @@ def test_make_uniform_keeps_the_reference_defaults(rt):
 
 
 def test_cpp_list_scenes_agrees_on_analytic_mode(rt):
-    out = subprocess.run([BIN, "--list-scenes"], capture_output=True, text=True, timeout=60, check=True).stdout
-    cpp = [json.loads(l) for l in out.splitlines()]
+    cpp = driver.list_scenes()
     py = rt.get_scenes()
     assert len(cpp) == len(py) == 44
     for c, p in zip(cpp, py):

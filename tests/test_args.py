@@ -1,8 +1,8 @@
 """The argument checks the post-process entry points share (csrc/rt_args.h), on the host alone (no GPU)."""
 import os
 import re
-import subprocess
 
+import native_build
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "02562_raytracer_amd", "csrc")
@@ -14,12 +14,9 @@ def test_args_check_native(tmp_path):
     skipped by every test, each alignment is refused at half a step and accepted at a whole one,
     inputs may overlap but an output may share no byte with anything, a range that ends at the
     top of the address space does not wrap into a false verdict, and the value checks."""
-    exe = str(tmp_path / "args_check")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-I", CSRC,
-                    "-o", exe, os.path.join(ROOT, "tests", "native", "args_check.cpp")], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "args_check: 0 mismatches" in out.stdout
+    out = native_build.run_checker(tmp_path, [os.path.join(ROOT, "tests", "native", "args_check.cpp")], [CSRC],
+                                   ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined"])
+    assert "args_check: 0 mismatches" in out
 
 
 def test_ranges_and_aliasing_are_defined_once():

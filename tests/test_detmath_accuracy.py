@@ -15,11 +15,11 @@ results are implementation-defined at the bit level; the build pins one accurate
 choice and uses it on both sides."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import native_build
 from conftest import ROOT
 
 FUNCS1 = ["sinf", "cosf", "acosf", "expf", "exp2f", "log2f", "sqrtf", "atanf"]
@@ -28,7 +28,7 @@ FUNCS1 = ["sinf", "cosf", "acosf", "expf", "exp2f", "log2f", "sqrtf", "atanf"]
 @pytest.fixture(scope="module")
 def lib(tmp_path_factory):
     d = tmp_path_factory.mktemp("detmath")
-    src, so = d / "shim.c", d / "shim.so"
+    src = d / "shim.c"
     body = ['#include "%s"' % os.path.join(ROOT, "include", "rt_detmath.h")]
     for f in FUNCS1:
         body.append(f"void v_{f}(const float* x, float* y, long n) {{ for (long i = 0; i < n; i++) "
@@ -39,9 +39,7 @@ def lib(tmp_path_factory):
                 "y[i] = rt_det_atan2f(a[i], b[i]); }")
     src.write_text("\n".join(body) + "\n")
     # the oracle's flags: no contraction, IEEE
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-o", str(so), str(src),
-                    "-lm"], check=True)
-    return C.CDLL(str(so))
+    return native_build.shared_lib(src, d, ["-O2", "-ffp-contract=off", "-fno-fast-math"], libs=["-lm"])
 
 
 def _f32p(a):

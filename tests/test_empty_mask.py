@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 
 from conftest import model
+from parity_util import CAM3, frame_camera
 
 ENV = (0.7, 0.8, 0.9)
-CAM3 = ((-0.02, 0.11, 0.6), (-0.02, 0.11, 0.0), (0.0, 1.0, 0.0), 3.5)   # configs.py config 3
 
 
 def _oracle_scene(O, mesh):
@@ -76,23 +76,15 @@ def test_standin_69451(rt, oracle):
     assert mask.sum() >= 0.5 * hitless.sum()
 
 
-def _frame_camera(mesh, back=2.5, constant=1.5):
-    V = mesh.arrays()[0][:, :3]
-    lo, hi = V.min(0), V.max(0)
-    c = 0.5 * (lo + hi)
-    r = float(np.abs(hi - lo).max())
-    return (tuple(c + np.array([0.0, 0.0, back * r])), tuple(c), (0.0, 1.0, 0.0), constant)
-
-
 def test_teapot(rt, oracle):
     mesh = rt.Mesh.from_obj(model("teapot.obj"))
-    mask, hitless = _check_sound(rt, oracle, mesh, _frame_camera(mesh), 96, 64, np.random.default_rng(3))
+    mask, hitless = _check_sound(rt, oracle, mesh, frame_camera(mesh), 96, 64, np.random.default_rng(3))
     assert mask.any()
 
 
 def test_elephant(rt, oracle):
     mesh = rt.Mesh.from_obj(model("justElephant.obj"))
-    mask, _ = _check_sound(rt, oracle, mesh, _frame_camera(mesh), 96, 64, np.random.default_rng(4))
+    mask, _ = _check_sound(rt, oracle, mesh, frame_camera(mesh), 96, 64, np.random.default_rng(4))
     assert mask.any()
 
 

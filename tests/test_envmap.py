@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import native_build
 from conftest import ROOT, model
 
 
@@ -20,8 +21,8 @@ def _detmath():
                     'float shim_atan2(float y, float x) { return rt_det_atan2f(y, x); }\n'
                     'void shim_env(const unsigned int* t, unsigned int w, unsigned int h, float x, float y, float z,'
                     ' float* o) { rt_det_env_sample(t, w, h, x, y, z, o); }\n')
-        os.system(f"cc -O2 -ffp-contract=off -fno-fast-math -shared -fPIC -o {so} {src} -lm")
-    lib = C.CDLL(so)
+    lib = native_build.shared_lib(src, os.path.dirname(src), ["-O2", "-ffp-contract=off", "-fno-fast-math"], libs=["-lm"],
+                                  cc="cc")
     lib.shim_atan2.restype = C.c_float
     lib.shim_atan2.argtypes = [C.c_float, C.c_float]
     lib.shim_env.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_float, C.c_float, C.c_float,

@@ -10,6 +10,7 @@ import pytest
 import adaptive_ref as AR
 import noise_ref as NR
 import tile_layout as TL
+from array_util import u32
 from conftest import model
 from parity_util import CORNELL_CAM, TEAPOT_CAM, Scene
 
@@ -17,10 +18,6 @@ pytestmark = pytest.mark.gpu
 
 SENTINEL = TL.SENTINEL
 f32 = np.float32
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def assert_f32_matches(g_bits, r, what=""):

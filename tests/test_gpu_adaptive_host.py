@@ -1,17 +1,12 @@
 """Adaptive sampling through the hosts: the C++ RenderState behind rt_render
 --adaptive-target and the Python RenderState give the same counts, frame and summary."""
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from conftest import ROOT
+import driver
 
 pytestmark = pytest.mark.gpu
 
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 SCENE = "W7 E3 Cornell Box"
 W, H = 36, 20
 
@@ -34,19 +29,13 @@ def test_rt_render_adaptive_equals_python_render_adaptive(rt, tmp_path, vote):
         assert len(np.unique(counts)) >= 2 and counts.max() == its
     finally:
         rs.ctx.close()
-    out = str(tmp_path / "frame")
-    r = subprocess.run([BIN, "--scene", SCENE, "--res", f"{W}x{H}", "--out", out, "--adaptive-target", f"{target:.9g}",
-                        "--adaptive-min", "4", "--adaptive-vote", vote, "--noise-batch", "4", "--samples", "20"],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == 1
-    info = json.loads(lines[0])
+    out, info = driver.render(tmp_path, SCENE, W, H, "--adaptive-target", f"{target:.9g}", "--adaptive-min", "4",
+                              "--adaptive-vote", vote, "--noise-batch", "4", "--samples", "20", stdout_lines=1)
     a = info["adaptive"]
     assert info["iteration"] == its == a["iterations"]
     for k in ("pixels", "live_next", "above", "nonfinite", "total_samples", "min_count", "max_count"):
         assert a[k] == s[k], k
     assert np.float32(float.fromhex(a["max_rel_err"])) == np.float32(s["max_rel_err"])
-    assert np.array_equal(np.fromfile(out + ".count.u32", np.uint32).reshape(H, W), counts)
-    assert np.array_equal(np.fromfile(out + ".accum.f32", np.uint32).reshape(H, W, 4), frame)
+    assert np.array_equal(driver.read_file(out, ".count.u32", np.uint32, H, W), counts)
+    assert np.array_equal(driver.read_file(out, ".accum.f32", np.uint32, H, W, 4), frame)
     assert a["total_samples"] == int(counts.sum())

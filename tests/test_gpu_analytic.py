@@ -4,20 +4,19 @@ accumulation and first-accepted object ids compared as uint32, the four ray
 counts equal.  tests/test_analytic_ref.py shows that the inputs used here reach
 every object, blocked and unblocked shadow rays, every bounce target and (the
 behind camera) pixels whose first-accepted object is not the closest."""
-import json
 import os
-import subprocess
 from importlib import import_module
 
 import numpy as np
 import pytest
 
 import analytic_ffi as A
+import driver
+from parity_util import COUNT_KEYS
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 MODES = list(A.MODES)
 W3 = ["W3E1", "W3E2", "W3E3", "W3E4"]
 SELECTIONS = [(0, 0), (1, 0), (2, 2), (3, 0), (4, 6), (5, 1), (9, 0)]
@@ -60,7 +59,7 @@ def compare(got, want):
     assert np.array_equal(gi, wi), f"{int((gi != wi).sum())} first-accepted ids differ"
     assert np.array_equal(ga.view(np.uint32), wa.view(np.uint32)), \
         f"{int((ga.view(np.uint32) != wa.view(np.uint32)).any(axis=-1).sum())} pixels differ"
-    for k in ("samples", "primary", "shadow", "bounce"):
+    for k in COUNT_KEYS:
         assert gc[k] == wc[k], (k, gc[k], wc[k])
 
 
@@ -220,14 +219,9 @@ def test_render_state_follows_the_control_panel(rt, ref):
 
 def test_cpp_driver_writes_the_same_frame(rt, ref, tmp_path):
     W = H = 64
-    out = str(tmp_path / "frame")
-    r = subprocess.run([BIN, "--scene", "W2 E5", "--selection", "4", "--res", f"{W}x{H}", "--out", out],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    info = json.loads(r.stdout.strip().splitlines()[-1])
+    out, info = driver.render(tmp_path, "W2 E5", W, H, "--selection", "4")
     assert info["mode"] == "W2E5"
-    acc = np.fromfile(out + ".accum.f32", np.float32).reshape(H, W, 4)
-    ids = np.fromfile(out + ".ids.u32", np.uint32).reshape(H, W)
+    acc, ids, _ = driver.read_frame(out, W, H)
     rs = rt.RenderState(rt.find_scene("W2 E5"), resolution=(W, H), selection1=4)
     try:
         rs.render(1)
@@ -242,11 +236,8 @@ def test_cpp_driver_writes_the_same_frame(rt, ref, tmp_path):
 
 def test_cpp_driver_textures_a_w3_scene_like_the_python_host(rt, tmp_path):
     W = H = 64
-    out = str(tmp_path / "frame")
-    r = subprocess.run([BIN, "--scene", "W3 E2", "--selection2", "0", "--use-texture", "1", "--uv-scale", "0.2,0.2",
-                        "--res", f"{W}x{H}", "--out", out], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    acc = np.fromfile(out + ".accum.f32", np.float32).reshape(H, W, 4)
+    out, _ = driver.render(tmp_path, "W3 E2", W, H, "--selection2", "0", "--use-texture", "1", "--uv-scale", "0.2,0.2")
+    acc = driver.read_frame(out, W, H)[0]
     rs = rt.RenderState(rt.find_scene("W3 E2"), resolution=(W, H))
     try:
         rs.set_texture(1, (0.2, 0.2))

@@ -7,51 +7,32 @@ device-built tree equal renders through the uploaded host build."""
 import numpy as np
 import pytest
 
+from accel_cases import check_bsp_build
 from conftest import model
 from parity_util import BUNNY_CAM, CORNELL_CAM
 
 pytestmark = pytest.mark.gpu
 
 
-def _check(rt, mesh, max_depth=20, max_leaf=4):
-    ctx = rt.Context(0)
-    try:
-        ctx.upload_mesh(mesh)
-        t = ctx.build_bsp_device(max_depth, max_leaf)
-        gt, gp, gi, ga = ctx.download_bsp()
-    finally:
-        ctx.close()
-    ht, hp, hi, ha, _ = mesh.bsp_tree(max_depth, max_leaf).arrays()
-    assert gt.shape == ht.shape
-    bad = np.nonzero((gt != ht).any(axis=1))[0]
-    assert bad.size == 0, f"{bad.size} nodes differ, first {bad[:4]}: gpu {gt[bad[:1]]} host {ht[bad[:1]]}"
-    badp = np.nonzero(gp.view(np.uint32) != hp.view(np.uint32))[0]
-    assert badp.size == 0, f"{badp.size} planes differ, first {badp[:4]}: gpu {gp[badp[:2]]} host {hp[badp[:2]]}"
-    assert np.array_equal(gi, hi), (gi.size, hi.size)
-    assert np.array_equal(ga.view(np.uint32), ha.view(np.uint32))
-    assert t["nids"] == hi.size
-    return t
-
-
 @pytest.mark.parametrize("name", ["test_object.obj", "plane.obj", "CornellBox.obj", "CornellBoxWithBlocks.obj",
                                   "teapot.obj"])
 @pytest.mark.parametrize("depth,leaf", [(20, 4), (8, 1), (12, 2), (3, 4)])
 def test_assets(rt, name, depth, leaf):
-    _check(rt, rt.Mesh.from_obj(model(name)), depth, leaf)
+    check_bsp_build(rt, rt.Mesh.from_obj(model(name)), depth, leaf)
 
 
 def test_bunny_standin(rt):
-    t = _check(rt, rt.Mesh.synth_bunny())
+    t = check_bsp_build(rt, rt.Mesh.synth_bunny())
     assert t["levels"] == 21
 
 
 def test_soup(rt):
-    _check(rt, rt.Mesh.synth_soup(300_000))
+    check_bsp_build(rt, rt.Mesh.synth_soup(300_000))
 
 
 def test_grid_of_copies(rt):
     # translated copies: many coincident candidate planes and shared extents
-    _check(rt, rt.Mesh.grid(rt.Mesh.synth_bunny(2000), 4, 3, 0.2))
+    check_bsp_build(rt, rt.Mesh.grid(rt.Mesh.synth_bunny(2000), 4, 3, 0.2))
 
 
 def test_duplicates_empty_sides(rt):
@@ -62,13 +43,13 @@ def test_duplicates_empty_sides(rt):
     idx = np.array([[3 * i, 3 * i + 1, 3 * i + 2, 0] for i in range(40)], np.uint32)
     mesh = rt.Mesh.from_arrays(verts, idx)
     for depth, leaf in ((20, 4), (6, 1)):
-        _check(rt, mesh, depth, leaf)
+        check_bsp_build(rt, mesh, depth, leaf)
 
 
 def test_single_triangle(rt):
     mesh = rt.Mesh.from_arrays(np.array([[0, 0, 0, 1], [1, 0, 0, 1], [0, 1, 0, 1]], np.float32),
                                np.array([[0, 1, 2, 0]], np.uint32))
-    _check(rt, mesh)
+    check_bsp_build(rt, mesh)
 
 
 def test_render_with_device_bsp(rt):

@@ -1,7 +1,7 @@
 """rt_build_bsp_device (csrc/rt_bsp_build.hip) at the sizes, depths and leaf
 counts where its kernels change behaviour, against the host builder under the
-contract of tests/test_gpu_bsp_build.py (_check: bsp_array, plane bits,
-primitive_ids, root box, times["nids"]); the host builder equals the oracle on
+contract of tests/test_gpu_bsp_build.py (accel_cases.check_bsp_build: bsp_array,
+plane bits, primitive_ids, root box, times["nids"]); the host builder equals the oracle on
 every case here (tests/test_build_cases.py).  Meshes: tests/build_cases.py.
 
 The boundaries, and the case just below / at / just above each:
@@ -29,7 +29,7 @@ import numpy as np
 import pytest
 
 import build_cases as bc
-from test_gpu_bsp_build import _check
+from accel_cases import check_bsp_build
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +46,7 @@ def _mesh(rt, key):
 def test_size_sweep(rt, key, depth, leaf):
     """k_tri_boxes .. k_leaf_finish at n triangles around the wave, block, kSlotsPerBlock
     and kScanBlock sizes and the step of `per` (65,536 / 65,537), at the default (20, 4)."""
-    _check(rt, _mesh(rt, key), depth, leaf)
+    check_bsp_build(rt, _mesh(rt, key), depth, leaf)
 
 
 @pytest.mark.parametrize("key,depth,leaf", bc.BSP_PARAMS, ids=_id)
@@ -55,7 +55,7 @@ def test_depth_and_leaf(rt, key, depth, leaf):
     4097 triangles in two leaves; (2, 1) -- and run to max_leaf 1 and 2; the leaf sort's 1,
     2 and 3 passes ((max_depth + 7) / 8 at 8, 16, 17) and k_bsp_decide's key
     branch << (max_depth - depth)."""
-    t = _check(rt, _mesh(rt, key), depth, leaf)
+    t = check_bsp_build(rt, _mesh(rt, key), depth, leaf)
     assert t["levels"] <= depth + 1
 
 
@@ -64,7 +64,7 @@ def test_depth_24(rt):
     """max_depth 24, the layout's limit: 2^25 - 1 node slots, leaf keys of 24 bits (3 sort
     passes), leaves at heap indices past 2^24 (`deep`: bc.DEEP_LEAVES leaves, bc.DEEP_NIDS ids).
     Slow: 1.03 s beside test_soup's 0.67 s (the 65,537-triangle case took 0.14 s)."""
-    t = _check(rt, _mesh(rt, bc.BSP_DEEP[0]), 24, 4)
+    t = check_bsp_build(rt, _mesh(rt, bc.BSP_DEEP[0]), 24, 4)
     assert t["levels"] == 25 and t["leaves"] == bc.DEEP_LEAVES and t["nids"] == bc.DEEP_NIDS
 
 
@@ -73,7 +73,7 @@ def test_leaf_counts(rt, key, leaves):
     """The leaf list goes through radix_sort_pairs (kTile 2048) and scan_exclusive_u32
     (kScanBlock 4096, total written to lc[leaves]): trees with exactly 2047, 2048, 2049,
     4096 and 4097 leaves (scatter at (20, 1); the counts are pinned on the CPU too)."""
-    t = _check(rt, _mesh(rt, key), 20, 1)
+    t = check_bsp_build(rt, _mesh(rt, key), 20, 1)
     assert t["leaves"] == leaves
 
 
@@ -86,7 +86,7 @@ def test_other_cases(rt, key, depth, leaf):
     lying exactly on candidate planes, and root boxes with zero extent on one or two axes
     (zero areas: every candidate costs 0, the first must win); offset: a mesh at 1e3 whose
     boxes are a few ulp wide, 76,000 leaves."""
-    _check(rt, _mesh(rt, key), depth, leaf)
+    check_bsp_build(rt, _mesh(rt, key), depth, leaf)
 
 
 @pytest.mark.parametrize("depth,leaf", [(0, 4), (25, 4), (20, 0)])

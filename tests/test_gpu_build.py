@@ -8,45 +8,29 @@ uploaded host build."""
 import numpy as np
 import pytest
 
+from accel_cases import check_bvh_build
 from conftest import model
 from parity_util import BUNNY_CAM, CORNELL_CAM, TEAPOT_CAM
 
 pytestmark = pytest.mark.gpu
 
 
-def _check_build(rt, mesh, max_prims):
-    ctx = rt.Context(0)
-    try:
-        ctx.upload_mesh(mesh)
-        times = ctx.build_bvh_device(max_prims)
-        gn, gi = ctx.download_bvh()
-    finally:
-        ctx.close()
-    hn, hi = mesh.bvh(max_prims).arrays()
-    assert gn.shape == hn.shape, (gn.shape, hn.shape)
-    bad = np.nonzero((gn != hn).any(axis=1))[0]
-    assert bad.size == 0, f"{bad.size} nodes differ, first {bad[:5]}: gpu {gn[bad[:1]]} host {hn[bad[:1]]}"
-    assert np.array_equal(gi, hi)
-    assert times["nodes"] == hn.shape[0]
-    return times
-
-
 @pytest.mark.parametrize("name", ["test_object.obj", "plane.obj", "CornellBox.obj", "CornellBoxWithBlocks.obj",
                                   "teapot.obj"])
 @pytest.mark.parametrize("max_prims", [1, 2, 4, 8, 16])
 def test_assets(rt, name, max_prims):
-    _check_build(rt, rt.Mesh.from_obj(model(name)), max_prims)
+    check_bvh_build(rt, rt.Mesh.from_obj(model(name)), max_prims)
 
 
 @pytest.mark.parametrize("max_prims", [4, 6])
 def test_bunny_standin(rt, max_prims):
-    t = _check_build(rt, rt.Mesh.synth_bunny(), max_prims)
+    t = check_bvh_build(rt, rt.Mesh.synth_bunny(), max_prims)
     assert t["treelets"] > 1
 
 
 def test_soup_large(rt):
     # ~ the reference's dragon (871,414 triangles): uniformly spread, all 4096 treelets
-    t = _check_build(rt, rt.Mesh.synth_soup(871_414), 4)
+    t = check_bvh_build(rt, rt.Mesh.synth_soup(871_414), 4)
     assert t["treelets"] == 4096
 
 
@@ -58,13 +42,13 @@ def test_duplicates_and_flat(rt):
     idx = np.array([[3 * i, 3 * i + 1, 3 * i + 2, 0] for i in range(40)], np.uint32)
     mesh = rt.Mesh.from_arrays(verts, idx)
     for mp in (1, 2, 4):
-        _check_build(rt, mesh, mp)
+        check_bvh_build(rt, mesh, mp)
 
 
 def test_single_triangle(rt):
     mesh = rt.Mesh.from_arrays(np.array([[0, 0, 0, 1], [1, 0, 0, 1], [0, 1, 0, 1]], np.float32),
                                np.array([[0, 1, 2, 0]], np.uint32))
-    _check_build(rt, mesh, 4)
+    check_bvh_build(rt, mesh, 4)
 
 
 @pytest.mark.parametrize("mode,name,cam,W,H,region,spp", [

@@ -1,7 +1,7 @@
 """rt_build_bvh_device (csrc/rt_build.hip) at the sizes where its kernels
 change behaviour, against the host builder under the contract of
-tests/test_gpu_build.py (_check_build: the whole GpuNode array including the
-9999 filler tail, bvh_triangles, times["nodes"]); the host builder equals the
+tests/test_gpu_build.py (accel_cases.check_bvh_build: the whole GpuNode array
+including the 9999 filler tail, bvh_triangles, times["nodes"]); the host builder equals the
 oracle on every case here (tests/test_build_cases.py).  Meshes:
 tests/build_cases.py.
 
@@ -27,7 +27,7 @@ The boundaries, and the case just below / at / just above each:
 import pytest
 
 import build_cases as bc
-from test_gpu_build import _check_build
+from accel_cases import check_bvh_build
 
 pytestmark = pytest.mark.gpu
 
@@ -45,7 +45,7 @@ def test_size_sweep(rt, key, max_prims):
     """k_boxes .. k_write_nodes at n triangles around the wave, block and kTile sizes and
     the 4-tile / 5-tile step of k_rs_scan; max_prims 1 (every leaf one triangle: the deepest emit_lbvh
     recursion, most nodes), 4 (the default) and 16 (leaves cut by the count test)."""
-    t = _check_build(rt, _mesh(rt, key), max_prims)
+    t = check_bvh_build(rt, _mesh(rt, key), max_prims)
     assert 1 <= t["treelets"] <= min(4096, key[1])
 
 
@@ -57,7 +57,7 @@ def test_treelet_counts(rt, key, max_prims):
     bvh_triangles).  The sheet, the row and the full lattice tie most centroids on the
     split axis, and two or three extents of the upper tree's segments tie: the stable
     order of equal centroids and the axis chosen on a tie are what is compared."""
-    t = _check_build(rt, _mesh(rt, key), max_prims)
+    t = check_bvh_build(rt, _mesh(rt, key), max_prims)
     assert t["treelets"] == bc.LATTICE_TREELETS[key]
 
 
@@ -70,4 +70,4 @@ def test_other_cases(rt, key, max_prims):
     centroids exactly on a treelet boundary, and zero centroid extent on one or two axes
     (Bbox::offset skips the divide); offset: a mesh at 1e3 whose triangles are a few ulp
     wide."""
-    _check_build(rt, _mesh(rt, key), max_prims)
+    check_bvh_build(rt, _mesh(rt, key), max_prims)

@@ -7,60 +7,14 @@ the same arrays:
   * runs of missed boxes, which the device handles two pops per trip.
 The reference's HLBVH never gets deep enough for the first two, but the C ABI
 takes any node array, so the walk must follow the shader there too."""
-import numpy as np
 import pytest
 
 import oracle_ffi as O
+from accel_cases import chain_bvh
 from conftest import model
-from parity_util import TEAPOT_CAM, Scene, compare
+from parity_util import COUNT_KEYS, TEAPOT_CAM, Scene, compare
 
 pytestmark = pytest.mark.gpu
-
-FAR = ((1.0e6, 1.0e6, 1.0e6), (1.0e6 + 1.0, 1.0e6 + 1.0, 1.0e6 + 1.0))
-
-
-def _node(box, offset, nprims):
-    f = np.array(list(box[0]) + [0.0] + list(box[1]) + [0.0], dtype=np.float32).view(np.uint32)
-    f[3], f[7] = offset, nprims
-    return f
-
-
-def chain_bvh(ntris, depth, shape, seed, p_leaf_hit=0.6, interior_miss_at=None, scene_box=None):
-    """shape "A": interior k's left child is a leaf, its right child the next
-    interior (the stack grows by one per level); shape "B": the left child is
-    the next interior and the right child a leaf (popped first, so a missed
-    leaf is followed by an interior pop)."""
-    rng = np.random.default_rng(seed)
-    hit_box = scene_box
-    ids = []
-
-    nleaves = depth + 1
-    blk = max(1, 3 * ntris // nleaves)   # each triangle sits in about three leaves
-
-    def leaf(force_hit=False):
-        n = ntris if force_hit else int(rng.integers(1, 2 * blk + 1))
-        first = 0 if force_hit else int(rng.integers(0, ntris))
-        off = len(ids)
-        ids.extend((first + j) % ntris for j in range(n))
-        return _node(hit_box if (rng.random() < p_leaf_hit or force_hit) else FAR, off, n)
-
-    def interior(k, right):
-        return _node(FAR if k == interior_miss_at else hit_box, right, 0)
-
-    nodes = []
-    if shape == "A":
-        for k in range(depth):                    # I_k at 2k, L_k at 2k + 1
-            nodes.append(interior(k, 2 * k + 2))
-            nodes.append(leaf())
-        nodes.append(leaf(True))                  # right child of the last interior (popped again and
-                                                  # again from the clamped slot 49)
-    else:
-        for k in range(depth):                    # I_k at k; right leaf R_k at depth + 1 + k
-            nodes.append(interior(k, depth + 1 + k))
-        nodes.append(leaf())                      # left child of the last interior
-        for k in range(depth):
-            nodes.append(leaf())
-    return np.stack(nodes), np.array(ids, dtype=np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -91,6 +45,6 @@ def test_bvh_stack_clamp_and_pop_cap(rt, teapot, shape, depth, miss_at, seed, mo
     linf, bits, idm = compare(g, o)
     assert idm == 0, f"{idm} primary-hit ids differ"
     assert bits == 0, f"{bits} radiance words differ (L-inf {linf})"
-    for k in ("samples", "primary", "shadow", "bounce"):
+    for k in COUNT_KEYS:
         assert g[2][k] == o[2][k], (k, g[2][k], o[2][k])
     assert (g[1] != 0xFFFFFFFF).any()

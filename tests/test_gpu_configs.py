@@ -16,18 +16,9 @@ import importlib
 import numpy as np
 import pytest
 
-from parity_util import RADIANCE_TOL, Scene, compare
+from parity_util import Scene, check
 
 pytestmark = pytest.mark.gpu
-
-
-def check(g, o):
-    linf, bits, idm = compare(g, o)
-    assert idm == 0, f"{idm} primary-hit id mismatches"
-    assert linf <= RADIANCE_TOL, f"radiance L-inf {linf}"
-    assert bits == 0, f"{bits} radiance words differ bitwise (L-inf {linf})"
-    for k in ("samples", "primary", "shadow", "bounce"):
-        assert g[2][k] == o[2][k], (k, g[2][k], o[2][k])
 
 
 @pytest.fixture(scope="module")

@@ -19,8 +19,7 @@ import importlib
 
 import pytest
 
-from parity_util import Scene
-from test_gpu_configs import check
+from parity_util import Scene, check
 
 pytestmark = pytest.mark.gpu
 

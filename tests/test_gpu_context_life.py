@@ -31,7 +31,7 @@ def _render(ctx):
     return acc, ids
 
 
-def _bits(ctx, bufs):
+def _frame_bits(ctx, bufs):
     ctx.synchronize()
     out = bufs[0].to_numpy(np.uint32, (H, W, 4)), bufs[1].to_numpy(np.uint32, (H, W))
     for b in bufs:
@@ -59,16 +59,16 @@ def _life(rt, mesh, bsp):
         times.append(ms)
         for on in (1, 0, 1):
             ctx.set_option(F.RT_OPT_ASYNC_FOLD, on)
-            frames.append(_bits(ctx, _render(ctx)))
+            frames.append(_frame_bits(ctx, _render(ctx)))
         ctx.set_option(F.RT_OPT_EMPTY_PIXELS, 2)
         masked = _render(ctx)
         times.append(ctx.empty_pixels_in_use()[1])
-        frames.append(_bits(ctx, masked))
+        frames.append(_frame_bits(ctx, masked))
         out = ctx.alloc(W * H * 16)
         ctx.denoise(W, H, first[0].ptr, first[1].ptr, st.ptr, None, SPP, out.ptr)
         level_ms, _ = ctx.denoise_level_times()
         times += level_ms
-        frames.insert(0, _bits(ctx, first))
+        frames.insert(0, _frame_bits(ctx, first))
         t = ctx.build_bvh_device()
         times += [v for k, v in t.items() if k.endswith("_ms")]
         out.free()
@@ -82,7 +82,7 @@ def test_three_lives_of_a_context(rt, gpu):
     mesh = rt.Mesh.from_obj(model("test_object.obj"))
     bsp = mesh.bsp_tree()
     _scene(rt, gpu, mesh, bsp)
-    ref = _bits(gpu, _render(gpu))
+    ref = _frame_bits(gpu, _render(gpu))
     assert ref[0].any(), "the frame is empty: the camera misses the scene"
     for life in range(3):
         frames, times = _life(rt, mesh, bsp)

@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import model
-from parity_util import BUNNY_CAM, CORNELL_CAM, TEAPOT_CAM, Scene
+from parity_util import BUNNY_CAM, CORNELL_CAM, TEAPOT_CAM, Scene, assert_same_render
 
 pytestmark = pytest.mark.gpu
 
@@ -38,10 +38,7 @@ def _frames(rt, s, mode, cam, W, H, region, spp, selection1=0, jitter=None):
 
 
 def _same(a, b, culled=True):
-    assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)), "radiance differs"
-    assert np.array_equal(a[1], b[1]), "primary-hit ids differ"
-    for k in ("samples", "primary", "shadow", "bounce"):
-        assert a[2][k] == b[2][k], k
+    assert_same_render(a, b)
     assert a[2]["subtree_culls"] == 0
     if culled:
         assert b[2]["subtree_culls"] > 0

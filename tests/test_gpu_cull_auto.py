@@ -13,20 +13,13 @@ import numpy as np
 import pytest
 
 from conftest import model
-from parity_util import BUNNY_CAM, CORNELL_CAM, Scene
+from parity_util import BUNNY_CAM, CORNELL_CAM, Scene, assert_same_render
 
 pytestmark = pytest.mark.gpu
 
 REGION = (0, 0, 640, 360)   # 230,400 px: a probe launch takes 5 iterations (>= 2^20 samples)
 CAM2 = ((0.25, 0.18, 0.45), (-0.02, 0.09, 0.0), (0.0, 1.0, 0.0), 2.5)
 FAR = ((-0.02, 0.11, 3.0), (-0.02, 0.11, 0.0), (0.0, 1.0, 0.0), 3.5)   # reach > 2x the bunny cam's
-
-
-def _same(a, b):
-    assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)), "radiance differs"
-    assert np.array_equal(a[1], b[1]), "primary-hit ids differ"
-    for k in ("samples", "primary", "shadow", "bounce"):
-        assert a[2][k] == b[2][k], k
 
 
 def _render(s, cam, spp=32, first_iter=0, accum_in=None):
@@ -46,18 +39,18 @@ def test_auto_probes_inside_the_render_and_matches_certified(rt):
     assert ctx.bsp_cull_probes() == (0, 0)
     # a counting render (RT_OPT_DETAIL_COUNTERS: other kernels) does not probe
     ctx.set_option(F.RT_OPT_DETAIL_COUNTERS, 1)
-    _same(ref[BUNNY_CAM], _render(s, BUNNY_CAM))
+    assert_same_render(ref[BUNNY_CAM], _render(s, BUNNY_CAM))
     ctx.set_option(F.RT_OPT_DETAIL_COUNTERS, 0)
     assert ctx.bsp_cull_probes() == (0, 0)
     # a render too small for a timed launch (4 iterations x 230,400 < 2^20 samples) does not probe
     small = _render(s, BUNNY_CAM, spp=4)
     assert ctx.bsp_cull_probes() == (0, 0)
     ctx.set_option(F.RT_OPT_BSP_CULL, F.RT_BSP_CULL_CERTIFIED)
-    _same(_render(s, BUNNY_CAM, spp=4), small)
+    assert_same_render(_render(s, BUNNY_CAM, spp=4), small)
     ctx.set_option(F.RT_OPT_BSP_CULL, F.RT_BSP_CULL_AUTO)
     # 32 iterations: four probe launches of 5 iterations, then 12 on the certified kernel
     got = _render(s, BUNNY_CAM)
-    _same(ref[BUNNY_CAM], got)
+    assert_same_render(ref[BUNNY_CAM], got)
     assert ctx.bsp_cull_probes() == (1, 4)
     mode, mc, ms = ctx.bsp_cull_in_use()   # (the render's results were read: its events are done)
     print(f"probe: certified {mc:.4f}, silhouette {ms:.4f} ms per 2^20 samples -> mode {mode}")
@@ -65,18 +58,18 @@ def test_auto_probes_inside_the_render_and_matches_certified(rt):
     assert mode == (F.RT_BSP_CULL_SILHOUETTE if ms < 0.95 * mc else F.RT_BSP_CULL_CERTIFIED)
     # the choice holds: the same eye again, a progressive continuation, and a new eye at
     # a similar reach -- no second probe, the same frames
-    _same(ref[BUNNY_CAM], _render(s, BUNNY_CAM))
+    assert_same_render(ref[BUNNY_CAM], _render(s, BUNNY_CAM))
     ctx.set_option(F.RT_OPT_BSP_CULL, F.RT_BSP_CULL_CERTIFIED)
     cont_ref = _render(s, BUNNY_CAM, first_iter=32, accum_in=ref[BUNNY_CAM][0])
     ctx.set_option(F.RT_OPT_BSP_CULL, F.RT_BSP_CULL_AUTO)
     _render(s, BUNNY_CAM)   # (the option change started over: a second probe)
     assert ctx.bsp_cull_probes() == (2, 8)
-    _same(cont_ref, _render(s, BUNNY_CAM, first_iter=32, accum_in=got[0]))
-    _same(ref[CAM2], _render(s, CAM2))
+    assert_same_render(cont_ref, _render(s, BUNNY_CAM, first_iter=32, accum_in=got[0]))
+    assert_same_render(ref[CAM2], _render(s, CAM2))
     assert ctx.bsp_cull_probes() == (2, 8)
     assert ctx.bsp_cull_in_use()[1:] != (0.0, 0.0)
     # an eye five times as far: a new probe
-    _same(ref[FAR], _render(s, FAR))
+    assert_same_render(ref[FAR], _render(s, FAR))
     assert ctx.bsp_cull_probes() == (3, 12)
     m2, mc2, ms2 = ctx.bsp_cull_in_use()
     assert mc2 > 0 and ms2 > 0
@@ -108,7 +101,7 @@ def test_auto_with_async_fold(rt):
     got = [_render(s, BUNNY_CAM), _render(s, CAM2)]
     ctx.set_option(F.RT_OPT_ASYNC_FOLD, 0)
     for a, b in zip(ref, got):
-        _same(a, b)
+        assert_same_render(a, b)
     assert ctx.bsp_cull_probes() == (1, 4)
     ctx.close()
 
@@ -137,7 +130,7 @@ def test_auto_other_modes_do_not_probe(rt):
     ref = s.render_gpu("W7E3", CORNELL_CAM, 1024, 1024, (0, 0, 1024, 1024), 0, 4)
     ctx.set_option(F.RT_OPT_BSP_CULL, F.RT_BSP_CULL_AUTO)
     got = s.render_gpu("W7E3", CORNELL_CAM, 1024, 1024, (0, 0, 1024, 1024), 0, 4)
-    _same(ref, got)
+    assert_same_render(ref, got)
     assert ctx.bsp_cull_in_use() == (F.RT_BSP_CULL_CERTIFIED, 0.0, 0.0)
     assert ctx.bsp_cull_probes() == (0, 0)
     ctx.close()

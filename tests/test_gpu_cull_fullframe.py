@@ -15,6 +15,8 @@ import importlib
 import numpy as np
 import pytest
 
+from parity_util import COUNT_KEYS
+
 pytestmark = pytest.mark.gpu
 
 
@@ -58,7 +60,7 @@ def test_full_frame_cull_equals_reference_walk(rt, gpu, configs, config, spp):
         diff = int((off[0] != on[0]).any(axis=2).sum())
         assert diff == 0, f"config {config}: {diff} pixels' radiance differs with {name} culling"
         assert np.array_equal(off[1], on[1]), f"primary-hit ids differ with {name} culling"
-        for k in ("samples", "primary", "shadow", "bounce"):
+        for k in COUNT_KEYS:
             assert off[2][k] == on[2][k], (name, k, off[2][k], on[2][k])
         # the work culling saves (printed for the log; the bench reports it too)
         print(f"config {config} {name}: culls {on[2]['subtree_culls']}, interior nodes "

@@ -2,58 +2,21 @@
 and the level kernel in its three forms against the numpy float32 restatement
 (tests/denoise_ref.py) bit for bit; rt_denoise behind the Python and the C++ RenderState; the
 argument checks; and that a render's own outputs do not move."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import denoise_ref as DR
-from conftest import ROOT, model
+import driver
+from array_util import Dev, u32
+from conftest import model
 from parity_util import CORNELL_CAM, TEAPOT_CAM, Scene
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-SENTINEL = 0xA5A5A5A5
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
+SENTINEL = Dev.SENTINEL
 QNAN = np.uint32(DR.QNAN_BITS).view(f32)
 SIZES = [(1, 1), (1, 7), (5, 3), (16, 16), (17, 16), (33, 19), (64, 64)]   # width x height
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
-
-
-class Dev:
-    """numpy arrays on the device, with a sentinel tail that must survive"""
-
-    def __init__(self, ctx):
-        self.ctx, self.bufs = ctx, []
-
-    def put(self, arr):
-        arr = np.ascontiguousarray(arr)
-        b = self.ctx.alloc(max(16, arr.nbytes))
-        if arr.nbytes:
-            b.from_numpy(arr)
-        self.bufs.append(b)
-        return b
-
-    def out(self, nwords, tail=64):
-        b = self.ctx.alloc((nwords + tail) * 4)
-        b.from_numpy(np.full(nwords + tail, SENTINEL, np.uint32))
-        self.bufs.append(b)
-        return b
-
-    @staticmethod
-    def get(b, nwords, tail=64):
-        a = b.to_numpy(np.uint32, (nwords + tail,))
-        assert np.all(a[nwords:] == SENTINEL)
-        return a[:nwords]
-
-    def close(self):
-        for b in self.bufs:
-            b.free()
 
 
 def synth(w, h, seed=11):
@@ -265,13 +228,10 @@ def restated(rs, counts=None, **kw):
 
 
 def run_rt_render(tmp_path, *flags):
-    out = str(tmp_path / "frame")
-    r = subprocess.run([BIN, "--scene", SCENE, "--res", f"{W}x{H}", "--out", out, "--denoise", *flags],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    return (np.fromfile(out + ".denoised.f32", np.uint32).reshape(H, W, 4),
-            np.fromfile(out + ".denoised.rgba8", np.uint8).reshape(H, W, 4),
-            np.fromfile(out + ".accum.f32", np.uint32).reshape(H, W, 4))
+    out, _ = driver.render(tmp_path, SCENE, W, H, "--denoise", *flags)
+    return (driver.read_file(out, ".denoised.f32", np.uint32, H, W, 4),
+            driver.read_file(out, ".denoised.rgba8", np.uint8, H, W, 4),
+            driver.read_file(out, ".accum.f32", np.uint32, H, W, 4))
 
 
 def test_render_state_denoise_python_and_cpp(rt, rstate, tmp_path):

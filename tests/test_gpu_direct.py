@@ -8,8 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import model
-from parity_util import CORNELL_CAM, Scene
-from test_gpu_parity import check
+from parity_util import CORNELL_CAM, Scene, check
 
 pytestmark = pytest.mark.gpu
 

@@ -15,8 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import model
-from parity_util import Scene
-from test_gpu_parity import check
+from parity_util import COUNT_KEYS, Scene, check
 
 pytestmark = pytest.mark.gpu
 
@@ -73,7 +72,7 @@ def test_elephant_every_culling_mode_equals_the_unculled_walk(rt, gpu, mesh):
         for mode, g in out.items():
             assert np.array_equal(ref[0].view(np.uint32), g[0].view(np.uint32)), mode
             assert np.array_equal(ref[1], g[1]), mode
-            for k in ("samples", "primary", "shadow", "bounce"):
+            for k in COUNT_KEYS:
                 assert ref[2][k] == g[2][k], (mode, k)
     finally:
         s.ctx.close()

@@ -10,8 +10,8 @@ for 96 iterations of one camera, which the last test covers)."""
 import numpy as np
 import pytest
 
-from parity_util import BUNNY_CAM, Scene
-from test_gpu_parity import check
+from array_util import bits
+from parity_util import BUNNY_CAM, COUNT_KEYS, Scene, assert_same_render, check
 
 pytestmark = pytest.mark.gpu
 
@@ -19,18 +19,6 @@ W, H, SPP = 203, 117, 12
 FULL = (0, 0, W, H)
 ENV = (0.7, 0.8, 0.9)
 AWAY_CAM = ((-0.02, 0.11, 0.6), (-0.02, 0.11, 1.2), (0.0, 1.0, 0.0), 3.5)   # the mesh behind the eye
-COUNTS = ("samples", "primary", "shadow", "bounce")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b, counts=True):
-    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(a[1], b[1])
-    if counts:
-        for k in COUNTS:
-            assert a[2][k] == b[2][k], (k, a[2][k], b[2][k])
 
 
 @pytest.fixture(scope="module")
@@ -65,7 +53,7 @@ def frames(scene):
 
 def test_on_equals_off_equals_oracle(frames):
     on, off, ora, flagged, elided, mask = frames
-    _same(on, off)
+    assert_same_render(on, off)
     check(on, ora)
     assert flagged == mask.sum() > 0.25 * W * H and elided == flagged * SPP
 
@@ -85,8 +73,8 @@ def test_counting_instantiation_elides_too(rt, scene, frames):
     finally:
         scene.ctx.set_option(scene.opt, 2)
         scene.ctx.set_option(rt._ffi.RT_OPT_DETAIL_COUNTERS, 0)
-    _same(g, frames[0])
-    _same(g0, frames[0])
+    assert_same_render(g, frames[0])
+    assert_same_render(g0, frames[0])
     assert 0 < g[2]["trips"] < g0[2]["trips"]
 
 
@@ -100,14 +88,14 @@ def test_tiles_three_ways(rt, scene, frames):
     ctx = scene.ctx
     ctx.set_uniforms(rt.make_uniform(*BUNNY_CAM, W, H))
     n = rt.local_tiles(W, H, 3) * 64
-    total = dict.fromkeys(COUNTS, 0)
+    total = dict.fromkeys(COUNT_KEYS, 0)
     for rank in range(3):
         pa, pi = ctx.alloc(n * 16), ctx.alloc(n * 4)
         pa.zero()
         pi.zero()
         c = ctx.render_tiles("W9E1", "BSP", rank, 3, 0, SPP, pa.ptr, pi.ptr, counts=True)
         assert ctx.empty_pixels_in_use()[0] == frames[3]
-        for k in COUNTS:
+        for k in COUNT_KEYS:
             total[k] += c[k]
         # each rank's packed tiles go to their place in the frame (rank r's share of a 3-way split)
         fr = _unpack_rank(rt, pa.to_numpy(np.float32, (n, 4)), pi.to_numpy(np.uint32, (n,)), rank, 3)
@@ -119,7 +107,7 @@ def test_tiles_three_ways(rt, scene, frames):
         pa.free()
         pi.free()
     assert seen.all()
-    _same((acc, ids, total), frames[0])
+    assert_same_render((acc, ids, total), frames[0])
 
 
 def _unpack_rank(rt, pa, pi, rank, nranks):
@@ -143,8 +131,8 @@ def test_three_calls_of_four(scene, frames):
     a = scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, 4)
     b = scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 4, 4, accum_in=a[0])
     c = scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 8, 4, accum_in=b[0])
-    _same(c, frames[0], counts=False)
-    for k in COUNTS:
+    assert_same_render(c, frames[0], counts=())
+    for k in COUNT_KEYS:
         assert a[2][k] + b[2][k] + c[2][k] == frames[0][2][k], k
 
 
@@ -152,7 +140,7 @@ def test_region_of_the_frame(scene, frames):
     reg = (37, 19, 101, 70)
     g = scene.render_gpu("W9E1", BUNNY_CAM, W, H, reg, 0, SPP)
     x0, y0, w, h = reg
-    assert np.array_equal(_bits(g[0]), _bits(frames[0][0][y0:y0 + h, x0:x0 + w]))
+    assert np.array_equal(bits(g[0]), bits(frames[0][0][y0:y0 + h, x0:x0 + w]))
     assert np.array_equal(g[1], frames[0][1][y0:y0 + h, x0:x0 + w])
 
 
@@ -167,7 +155,7 @@ def test_moved_eye_gives_a_fresh_contexts_frame(rt, scene):
         assert np.array_equal(fresh.ctx.download_empty_mask(W, H), scene.ctx.download_empty_mask(W, H))
     finally:
         fresh.ctx.close()
-    _same(g, f)
+    assert_same_render(g, f)
     check(g, scene.render_oracle("W9E1", moved, W, H, FULL, 0, SPP))
 
 
@@ -201,7 +189,7 @@ def test_environment_map_turns_it_off(scene, frames):
     finally:
         scene.ctx.set_option(scene.opt, 2)
         scene.ctx.set_environment_map(None)
-    _same(g, g0)
+    assert_same_render(g, g0)
     assert np.array_equal(g[1], frames[0][1])
 
 
@@ -229,13 +217,13 @@ def test_small_sample_budget_and_unit_orders(rt, scene, frames):
     ctx = scene.ctx
     try:
         ctx.set_option(F.RT_OPT_SAMPLE_BUDGET_MB, 1)   # 203 x 117 x 16 B x 12 iterations = 4.3 MiB: five passes
-        _same(scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, SPP), frames[0])
+        assert_same_render(scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, SPP), frames[0])
         ctx.set_option(F.RT_OPT_UNIT_ORDER, 0)
         ctx.set_option(F.RT_OPT_SAMPLE_CHUNK, 5)
-        _same(scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, SPP), frames[0])
+        assert_same_render(scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, SPP), frames[0])
         ctx.set_option(F.RT_OPT_SAMPLE_BUDGET_MB, 16384)
         ctx.set_option(F.RT_OPT_ASYNC_FOLD, 1)
-        _same(scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, SPP), frames[0])
+        assert_same_render(scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, SPP), frames[0])
     finally:
         ctx.set_option(F.RT_OPT_ASYNC_FOLD, 0)
         ctx.set_option(F.RT_OPT_SAMPLE_BUDGET_MB, 16384)
@@ -248,13 +236,13 @@ def test_default_builds_after_96_iterations(rt, frames, scene):
     try:
         a = s.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, SPP)
         assert s.ctx.empty_pixels_in_use()[0] == 0   # 12 iterations: no mask yet
-        _same(a, frames[0])
+        assert_same_render(a, frames[0])
         b = s.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, SPP, 83, accum_in=a[0])   # 95 with this call's: not yet
         assert s.ctx.empty_pixels_in_use()[0] == 0
         b = s.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, SPP, 52, accum_in=a[0])   # 147
         assert s.ctx.empty_pixels_in_use()[0] == frames[3] and s.ctx.last_elided_primaries() == frames[3] * 52
         s.ctx.set_option(scene.opt, 0)
         b0 = s.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, SPP, 52, accum_in=a[0])
-        _same(b, b0)
+        assert_same_render(b, b0)
     finally:
         s.ctx.close()

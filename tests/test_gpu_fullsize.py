@@ -18,8 +18,8 @@ not depend on size, plus the oracle where it finishes in seconds:
 import numpy as np
 import pytest
 
-from parity_util import BUNNY_CAM, Scene
-from test_gpu_parity import check
+from array_util import bits
+from parity_util import BUNNY_CAM, Scene, check
 
 pytestmark = pytest.mark.gpu
 
@@ -29,10 +29,6 @@ W, H = 1920, 1080
 @pytest.fixture(scope="module")
 def bunny(rt, gpu):
     return Scene(rt, rt.Mesh.synth_bunny(), "BSP")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def test_config3_full_frame_1spp_equals_oracle(bunny):
@@ -45,16 +41,16 @@ def test_config3_full_frame_1spp_equals_oracle(bunny):
 def test_config3_256spp_split_and_rerun_identity(bunny):
     full = bunny.render_gpu("W9E1", BUNNY_CAM, W, H, (0, 0, W, H), 0, 256)
     again = bunny.render_gpu("W9E1", BUNNY_CAM, W, H, (0, 0, W, H), 0, 256)
-    assert np.array_equal(_bits(full[0]), _bits(again[0])) and np.array_equal(full[1], again[1])
+    assert np.array_equal(bits(full[0]), bits(again[0])) and np.array_equal(full[1], again[1])
     half = bunny.render_gpu("W9E1", BUNNY_CAM, W, H, (0, 0, W, H), 0, 128)
     rest = bunny.render_gpu("W9E1", BUNNY_CAM, W, H, (0, 0, W, H), 128, 128, accum_in=half[0])
-    assert np.array_equal(_bits(full[0]), _bits(rest[0])) and np.array_equal(full[1], rest[1])
+    assert np.array_equal(bits(full[0]), bits(rest[0])) and np.array_equal(full[1], rest[1])
     assert full[2]["samples"] == W * H * 256
     # 24 pixels across the frame, all 256 iterations, against the oracle
     rng = np.random.default_rng(3)
     for x, y in zip(rng.integers(0, W, 24), rng.integers(0, H, 24)):
         o = bunny.render_oracle("W9E1", BUNNY_CAM, W, H, (int(x), int(y), 1, 1), 0, 256)
-        assert np.array_equal(_bits(full[0][y, x]), _bits(o[0][0, 0])), (x, y, full[0][y, x], o[0][0, 0])
+        assert np.array_equal(bits(full[0][y, x]), bits(o[0][0, 0])), (x, y, full[0][y, x], o[0][0, 0])
         assert full[1][y, x] == o[1][0, 0]
 
 
@@ -93,7 +89,7 @@ def test_config3_eight_rank_tiles_equal_frame(rt, bunny):
     for b in (pa, pi, fa, fi):
         b.free()
     assert total == W * H * spp   # every pixel-sample on exactly one rank
-    assert np.array_equal(_bits(a), _bits(ref[0])) and np.array_equal(i, ref[1])
+    assert np.array_equal(bits(a), bits(ref[0])) and np.array_equal(i, ref[1])
 
 
 @pytest.mark.slow
@@ -116,7 +112,7 @@ def test_config5_full_frame_split_identity(rt):
             ctx.render("W9E1", "BSP", (0, 0, W5, H5), parts[0], parts[1], acc.ptr, None)
             out.append(acc.to_numpy(np.float32, (H5, W5, 4)))
             acc.free()
-        assert np.array_equal(_bits(out[0]), _bits(out[2]))
+        assert np.array_equal(bits(out[0]), bits(out[2]))
         assert np.isfinite(out[0]).all() and (out[0][..., 3] == 1.0).all()
     finally:
         ctx.close()

@@ -3,23 +3,22 @@ k_denoise_guide_objects against the numpy float32 restatement (tests/guide_objec
 for bit, objects = 0 against rt_denoise_guide byte for byte, the argument rules, and
 set_guide_objects / --guide-objects behind the Python and the C++ RenderState."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import denoise_ref as DR
+import driver
 import guide_objects_ref as GR
 import temporal_ref as TR
+from array_util import Dev, u32
 from conftest import ROOT, model
 from parity_util import CORNELL_CAM, TEAPOT_CAM, Scene
-from test_gpu_denoise import Dev, u32
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
 NONE = 0xFFFFFFFF
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 UP = (0.0, 1.0, 0.0)
 # name: (scene, the mode whose render gives the ids, camera)
 CAMERAS = {
@@ -161,11 +160,7 @@ def env_flags(rt, scene, tmp_path):
 
 
 def rt_render(tmp_path, scene, *flags):
-    out = str(tmp_path / "frame")
-    r = subprocess.run([BIN, "--scene", scene, "--res", f"{W}x{H}", "--out", out, *flags], capture_output=True, text=True,
-                       timeout=120)
-    assert r.returncode == 0, r.stderr
-    return out
+    return driver.render(tmp_path, scene, W, H, *flags)[0]
 
 
 def test_render_state_denoise_w8e1_python_and_cpp(rt, tmp_path):
@@ -199,11 +194,11 @@ def test_render_state_denoise_w8e1_python_and_cpp(rt, tmp_path):
     finally:
         rs.ctx.close()
     out = rt_render(tmp_path, BALLS_SCENE, "--spp", "4", "--denoise", "--guide-objects")
-    assert np.array_equal(np.fromfile(out + ".denoised.f32", np.uint32).reshape(H, W, 4), u32(on))
-    assert np.array_equal(np.fromfile(out + ".denoised.rgba8", np.uint8).reshape(H, W, 4), rgba_on)
+    assert np.array_equal(driver.read_file(out, ".denoised.f32", np.uint32, H, W, 4), u32(on))
+    assert np.array_equal(driver.read_file(out, ".denoised.rgba8", np.uint8, H, W, 4), rgba_on)
     out = rt_render(tmp_path, BALLS_SCENE, "--spp", "4", "--denoise")
-    assert np.array_equal(np.fromfile(out + ".denoised.f32", np.uint32).reshape(H, W, 4), u32(off))
-    assert np.array_equal(np.fromfile(out + ".denoised.rgba8", np.uint8).reshape(H, W, 4), rgba_off)
+    assert np.array_equal(driver.read_file(out, ".denoised.f32", np.uint32, H, W, 4), u32(off))
+    assert np.array_equal(driver.read_file(out, ".denoised.rgba8", np.uint8, H, W, 4), rgba_off)
 
 
 def test_render_state_temporal_w9e2_python_and_cpp(rt, tmp_path):
@@ -235,7 +230,7 @@ def test_render_state_temporal_w9e2_python_and_cpp(rt, tmp_path):
         rs.ctx.close()
     out = rt_render(tmp_path, PLANE_SCENE, "--temporal-frames", "3", "--keys", "Left", "--guide-objects",
                     *env_flags(rt, PLANE_SCENE, tmp_path))
-    assert np.array_equal(np.fromfile(out + ".temporal.f32", np.uint32).reshape(H, W, 4), u32(color))
-    assert np.array_equal(np.fromfile(out + ".temporal.len.u32", np.uint32).reshape(H, W), length)
-    assert np.array_equal(np.fromfile(out + ".temporal.denoised.f32", np.uint32).reshape(H, W, 4), u32(got))
-    assert np.array_equal(np.fromfile(out + ".temporal.denoised.rgba8", np.uint8).reshape(H, W, 4), rgba)
+    assert np.array_equal(driver.read_file(out, ".temporal.f32", np.uint32, H, W, 4), u32(color))
+    assert np.array_equal(driver.read_file(out, ".temporal.len.u32", np.uint32, H, W), length)
+    assert np.array_equal(driver.read_file(out, ".temporal.denoised.f32", np.uint32, H, W, 4), u32(got))
+    assert np.array_equal(driver.read_file(out, ".temporal.denoised.rgba8", np.uint8, H, W, 4), rgba)

@@ -2,32 +2,22 @@
 ABI) renders the reference's scenes, and its frames equal the Python
 RenderState's and the CPU oracle's bit for bit -- the two host mirrors drive
 the same kernels with the same uniforms, jitter tables and iteration order."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from parity_util import Scene
-from test_gpu_parity import check
+import driver
+from parity_util import Scene, check
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 
 
 def cpp_render(tmp_path, scene, W, H, *args):
-    out = str(tmp_path / "frame")
-    r = subprocess.run([BIN, "--scene", scene, "--res", f"{W}x{H}", "--out", out, *args], capture_output=True,
-                       text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    info = json.loads(r.stdout.strip().splitlines()[-1])
-    acc = np.fromfile(out + ".accum.f32", np.float32).reshape(H, W, 4)
-    ids = np.fromfile(out + ".ids.u32", np.uint32).reshape(H, W)
-    rgba = np.fromfile(out + ".rgba8", np.uint8).reshape(H, W, 4)
-    return acc, ids, rgba, info
+    out, info = driver.render(tmp_path, scene, W, H, *args)
+    return (*driver.read_frame(out, W, H), info)
 
 
 def test_cornell_progressive_samples(rt, tmp_path):

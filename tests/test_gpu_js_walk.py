@@ -10,8 +10,8 @@ import numpy as np
 import pytest
 
 from conftest import model
+from js_walk_golden import EXCEPTIONS, SCENES, load_fixture
 from parity_util import compare
-from test_js_walk import EXCEPTIONS, SCENES, load_fixture
 
 pytestmark = pytest.mark.gpu
 

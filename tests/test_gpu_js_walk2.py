@@ -15,17 +15,13 @@ on the oracle's HLBVH and equals the oracle's walk bit for bit."""
 import numpy as np
 import pytest
 
+from array_util import u32
 from conftest import model
-from test_js_walk import fnv
-from test_js_walk2 import EXCEPTIONS, SCENES, load_fixture
+from js_walk_golden import EXCEPTIONS2 as EXCEPTIONS, SCENES2 as SCENES, fnv, load_fixture
 
 pytestmark = pytest.mark.gpu
 
 MISS = 0xFFFFFFFF
-
-
-def _bits(x):
-    return np.float32(x).view(np.uint32)
 
 
 def _scene(rt, oracle, name, trav):
@@ -52,7 +48,7 @@ def _rays(z):
 
 @pytest.mark.parametrize("name", SCENES)
 def test_secondary_rays_match_reference_js_walk(rt, oracle, name):
-    meta, z = load_fixture(name)
+    meta, z = load_fixture(name, "js_walk2")
     ctx, sc = _scene(rt, oracle, name, "BSP")
     try:
         shadow = z["kind"] == 1
@@ -70,9 +66,9 @@ def test_secondary_rays_match_reference_js_walk(rt, oracle, name):
             assert h["tri"][i] == (q["tri"] if q["status"] == 1 else MISS), i
             assert (h["ntested"][i], h["tested_fnv"][i]) == (len(q["tested"]), fnv(q["tested"])), i
             for k in ("tmin", "tmax"):
-                assert _bits(h[k][i]) == _bits(q[k]), (i, k)
+                assert u32(h[k][i]) == u32(q[k]), (i, k)
             if q["status"] == 1:
-                assert _bits(h["dist"][i]) == _bits(q["dist"]), i
+                assert u32(h["dist"][i]) == u32(q["dist"]), i
             # ... and the reference's walk
             same = (h["tri"][i] == (z["tri"][i] if js_hit else MISS) and h["ntested"][i] == z["ntested"][i]
                     and h["tested_fnv"][i] == z["seq_fnv"][i])
@@ -91,7 +87,7 @@ def test_secondary_rays_match_reference_js_walk(rt, oracle, name):
 
 @pytest.mark.parametrize("name", SCENES)
 def test_secondary_rays_bvh_walk_matches_oracle(rt, oracle, name):
-    meta, z = load_fixture(name)
+    meta, z = load_fixture(name, "js_walk2")
     ctx, sc = _scene(rt, oracle, name, "BVH")
     try:
         shadow = z["kind"] == 1
@@ -106,7 +102,7 @@ def test_secondary_rays_bvh_walk_matches_oracle(rt, oracle, name):
         assert hc["tri"][i] == tri, i
         assert (hc["ntested"][i], hc["tested_fnv"][i]) == (len(q["tested"]), fnv(q["tested"])), i
         if q["status"] == 1:
-            assert _bits(hc["dist"][i]) == _bits(q["dist"]), i
+            assert u32(hc["dist"][i]) == u32(q["dist"]), i
         # the any-hit walk: same boolean, a prefix of the closest-hit's tests
         assert (h["tri"][i] != MISS) == (tri != MISS), i
         k = int(h["ntested"][i])
@@ -121,7 +117,7 @@ def test_secondary_rays_culled_walk_same_hits(rt, oracle, name):
     # whose content box the ray interval misses: fewer triangles are tested (a
     # subsequence of the reference's), and every ray's hit -- triangle, distance,
     # barycentrics, the any-hit boolean -- is the same bit for bit
-    meta, z = load_fixture(name)
+    meta, z = load_fixture(name, "js_walk2")
     ctx, sc = _scene(rt, oracle, name, "BSP")
     try:
         shadow = z["kind"] == 1

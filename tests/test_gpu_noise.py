@@ -3,28 +3,21 @@ k_noise_summary against the numpy float32 restatement (tests/noise_ref.py) bit f
 state a render keeps from its own records; its invariance under every way a render is
 split; the packed tile layout; the modes that must not touch the buffer; and the
 render-until-converged loops of the Python and C++ hosts."""
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import driver
 import noise_ref as NR
 import tile_layout as TL
-from conftest import ROOT, model
+from array_util import u32
+from conftest import model
 from parity_util import CORNELL_CAM, Scene
 
 pytestmark = pytest.mark.gpu
 
 NPIX = 197            # three waves plus 5
 SENTINEL = TL.SENTINEL
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 W, H = 36, 20         # 5 x 3 tiles, ragged right column and bottom row
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 def assert_state_matches(g, r):
@@ -446,17 +439,11 @@ def test_rt_render_noise_target_equals_python_loop(rt, rstate, tmp_path):
     assert its in (4, 8)
     rel = rs.noise_map().view(np.uint32)
     frame = rs.frame().view(np.uint32)
-    out = str(tmp_path / "frame")
-    r = subprocess.run([BIN, "--scene", SCENE, "--res", f"{W}x{H}", "--out", out, "--noise-target",
-                        f"{float(target):.9g}", "--noise-batch", "4", "--samples", "12"],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == 1
-    info = json.loads(lines[0])
+    out, info = driver.render(tmp_path, SCENE, W, H, "--noise-target", f"{float(target):.9g}", "--noise-batch", "4",
+                              "--samples", "12", stdout_lines=1)
     n = info["noise"]
     assert info["iteration"] == its == n["iterations"]
     assert (n["pixels"], n["above"], n["nonfinite"]) == (s["pixels"], s["above"], s["nonfinite"])
     assert np.float32(float.fromhex(n["max_rel_err"])) == np.float32(s["max_rel_err"])
-    assert np.array_equal(np.fromfile(out + ".noise.f32", np.uint32).reshape(H, W), rel)
-    assert np.array_equal(np.fromfile(out + ".accum.f32", np.uint32).reshape(H, W, 4), frame)
+    assert np.array_equal(driver.read_file(out, ".noise.f32", np.uint32, H, W), rel)
+    assert np.array_equal(driver.read_file(out, ".accum.f32", np.uint32, H, W, 4), frame)

@@ -6,20 +6,9 @@ import numpy as np
 import pytest
 
 from conftest import model
-from parity_util import (BASIC_CAM, BUNNY_CAM, CORNELL_CAM, RADIANCE_TOL, TEAPOT_CAM, Scene, compare)
+from parity_util import BASIC_CAM, BUNNY_CAM, CORNELL_CAM, TEAPOT_CAM, Scene, check, frame_reference
 
 pytestmark = pytest.mark.gpu
-
-
-def check(gpu, ora, exact=True, counts=True):
-    linf, bits, idm = compare(gpu, ora)
-    assert idm == 0, f"{idm} primary-hit ids differ"
-    assert linf <= RADIANCE_TOL, f"L-inf {linf}"
-    if exact:
-        assert bits == 0, f"{bits} radiance words differ bitwise (L-inf {linf})"
-    if counts:
-        for k in ("samples", "primary", "shadow", "bounce"):
-            assert gpu[2][k] == ora[2][k], (k, gpu[2][k], ora[2][k])
 
 
 def test_math_selftest(gpu):
@@ -303,7 +292,6 @@ def test_display_frame_rgba8(rt):
     # of the same pinned definition (tests/test_gpu_tiles.py holds the kernel to
     # it value by value): the exact 8-bit rounding, but for a value within 1e-10
     # of a rounding midpoint, where two float64 pow may disagree
-    from test_gpu_tiles import frame_reference
     rs = rt.RenderState(rt.find_scene("W7 E3 Cornell Box"), resolution=(64, 48))
     rs.render(spp=4)
     acc = rs.frame()

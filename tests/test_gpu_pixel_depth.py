@@ -10,27 +10,16 @@ clip is a form of culling); and with the certified walk the clip does skip work.
 import numpy as np
 import pytest
 
-from parity_util import BUNNY_CAM, Scene
-from test_gpu_parity import check
+from array_util import bits
+from parity_util import BUNNY_CAM, COUNT_KEYS, Scene, assert_same_render, check
 
 pytestmark = pytest.mark.gpu
 
 W, H, SPP = 160, 90, 12
 FULL = (0, 0, W, H)
 ENV = (0.7, 0.8, 0.9)
-COUNTS = ("samples", "primary", "shadow", "bounce")
 DETAIL = ("node_interior", "node_leaf", "ids_read", "tri_tests", "tri_accepts")
 MOVED = ((0.05, 0.13, 0.55), BUNNY_CAM[1], BUNNY_CAM[2], BUNNY_CAM[3])
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _same(a, b, counts=COUNTS):
-    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(a[1], b[1])
-    for k in counts:
-        assert a[2][k] == b[2][k], (k, a[2][k], b[2][k])
 
 
 @pytest.fixture(scope="module")
@@ -67,7 +56,7 @@ def oracle_frames(scene):
 def test_on_equals_off_equals_oracle(scene, oracle_frames, sel):
     on, off, used = _on_off(scene, lambda: scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, SPP, selection1=sel))
     assert used and scene.ctx.empty_pixels_in_use()[0] > 0
-    _same(on, off)
+    assert_same_render(on, off)
     check(on, oracle_frames[sel])
 
 
@@ -80,7 +69,7 @@ def test_culling_modes(rt, scene, oracle_frames, cull):
     finally:
         scene.ctx.set_option(F.RT_OPT_BSP_CULL, F.RT_BSP_CULL_AUTO)
     assert used
-    _same(on, off)
+    assert_same_render(on, off)
     check(on, oracle_frames[0])
 
 
@@ -91,14 +80,14 @@ def test_unit_orders_and_async_fold(scene, oracle_frames):
         ctx.set_option(F.RT_OPT_SAMPLE_CHUNK, 5)
         on, off, used = _on_off(scene, lambda: scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, SPP))
         assert used
-        _same(on, off)
+        assert_same_render(on, off)
         check(on, oracle_frames[0])
         ctx.set_option(F.RT_OPT_UNIT_ORDER, 1)
         ctx.set_option(F.RT_OPT_SAMPLE_CHUNK, 1)
         ctx.set_option(F.RT_OPT_ASYNC_FOLD, 1)
         on, off, used = _on_off(scene, lambda: scene.render_gpu("W9E1", BUNNY_CAM, W, H, FULL, 0, SPP))
         assert used
-        _same(on, off)
+        assert_same_render(on, off)
         check(on, oracle_frames[0])
     finally:
         ctx.set_option(F.RT_OPT_ASYNC_FOLD, 0)
@@ -112,13 +101,13 @@ def _tiles(rt, ctx, nranks):
     n = rt.local_tiles(W, H, nranks) * 64
     tiles_x, tiles_y = (W + 7) // 8, (H + 7) // 8
     acc, ids = np.zeros((H, W, 4), np.float32), np.zeros((H, W), np.uint32)
-    total = dict.fromkeys(COUNTS, 0)
+    total = dict.fromkeys(COUNT_KEYS, 0)
     for rank in range(nranks):
         pa, pi = ctx.alloc(n * 16), ctx.alloc(n * 4)
         pa.zero()
         pi.zero()
         c = ctx.render_tiles("W9E1", "BSP", rank, nranks, 0, SPP, pa.ptr, pi.ptr, counts=True)
-        for k in COUNTS:
+        for k in COUNT_KEYS:
             total[k] += c[k]
         a, i = pa.to_numpy(np.float32, (n, 4)), pi.to_numpy(np.uint32, (n,))
         pa.free()
@@ -139,7 +128,7 @@ def _tiles(rt, ctx, nranks):
 def test_tile_set_of_three_ranks(rt, scene, oracle_frames):
     on, off, used = _on_off(scene, lambda: _tiles(rt, scene.ctx, 3))
     assert used
-    _same(on, off)
+    assert_same_render(on, off)
     check(on, oracle_frames[0])
 
 
@@ -147,9 +136,9 @@ def test_region_of_the_frame(scene, oracle_frames):
     reg = (37, 19, 101, 60)
     on, off, used = _on_off(scene, lambda: scene.render_gpu("W9E1", BUNNY_CAM, W, H, reg, 0, SPP))
     assert used
-    _same(on, off)
+    assert_same_render(on, off)
     x0, y0, w, h = reg
-    assert np.array_equal(_bits(on[0]), _bits(oracle_frames[0][0][y0:y0 + h, x0:x0 + w]))
+    assert np.array_equal(bits(on[0]), bits(oracle_frames[0][0][y0:y0 + h, x0:x0 + w]))
     assert np.array_equal(on[1], oracle_frames[0][1][y0:y0 + h, x0:x0 + w])
 
 
@@ -169,11 +158,11 @@ def test_two_calls_and_the_noise_state(scene, oracle_frames):
         finally:
             ctx.set_noise_buffer(None)
             nb.free()
-        return b[0], b[1], {k: a[2][k] + b[2][k] for k in COUNTS}, state
+        return b[0], b[1], {k: a[2][k] + b[2][k] for k in COUNT_KEYS}, state
 
     on, off, used = _on_off(scene, render)
     assert used
-    _same(on, off)
+    assert_same_render(on, off)
     assert np.array_equal(on[3], off[3])
     check(on[:3], oracle_frames[0])
 
@@ -186,7 +175,7 @@ def test_moved_eye_rebuilds_the_ranges(rt, scene):
     n1, f1, used1 = ctx.last_pixel_depth(W, H)
     assert used0 and used1 and not np.array_equal(n0, n1)
     hn, hf = rt.pixel_depth_host(scene.mesh, rt.make_uniform(*MOVED, W, H))
-    assert np.array_equal(_bits(n1), _bits(hn)) and np.array_equal(_bits(f1), _bits(hf))
+    assert np.array_equal(bits(n1), bits(hn)) and np.array_equal(bits(f1), bits(hf))
     check(g, scene.render_oracle("W9E1", MOVED, W, H, FULL, 0, SPP))
 
 
@@ -195,7 +184,7 @@ def test_device_ranges_are_the_host_ranges(rt, scene):
     near, far, used = scene.ctx.last_pixel_depth(W, H)
     assert used
     hn, hf = rt.pixel_depth_host(scene.mesh, rt.make_uniform(*BUNNY_CAM, W, H))
-    assert np.array_equal(_bits(near), _bits(hn)) and np.array_equal(_bits(far), _bits(hf))
+    assert np.array_equal(bits(near), bits(hn)) and np.array_equal(bits(far), bits(hf))
     mask = scene.ctx.download_empty_mask(W, H)
     assert np.all(near[mask] == np.inf) and np.all(far[mask] == 0.0) and np.all(near[~mask] < np.inf)
 
@@ -246,14 +235,14 @@ def _counting(scene, cull):
 def test_culling_off_keeps_the_reference_walk(scene, oracle_frames):
     on, off, used = _counting(scene, scene.F.RT_BSP_CULL_OFF)
     assert not used   # the clip is a form of culling
-    _same(on, off, COUNTS + DETAIL)
+    assert_same_render(on, off, COUNT_KEYS + DETAIL)
     check(on, oracle_frames[0])
 
 
 def test_the_clip_skips_work(scene, oracle_frames):
     on, off, used = _counting(scene, scene.F.RT_BSP_CULL_CERTIFIED)
     assert used
-    _same(on, off)
+    assert_same_render(on, off)
     check(on, oracle_frames[0])
     work_on = on[2]["node_interior"] + on[2]["tri_tests"]
     work_off = off[2]["node_interior"] + off[2]["tri_tests"]

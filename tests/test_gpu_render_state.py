@@ -6,8 +6,7 @@ direct rt_render calls and with the CPU oracle."""
 import numpy as np
 import pytest
 
-from parity_util import Scene
-from test_gpu_parity import check
+from parity_util import Scene, check
 
 pytestmark = pytest.mark.gpu
 

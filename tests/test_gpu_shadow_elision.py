@@ -12,8 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import model
-from parity_util import CORNELL_CAM, TEAPOT_CAM, Scene
-from test_gpu_parity import check
+from parity_util import CORNELL_CAM, COUNT_KEYS, TEAPOT_CAM, Scene, check
 
 pytestmark = pytest.mark.gpu
 
@@ -78,7 +77,7 @@ def test_w9e1_elides_every_shadow_ray(rt, teapot, w9e1_frame):
     try:
         gw, ew = _render(s, "W9E1", TEAPOT_CAM)
         ow = s.render_oracle("W9E1", TEAPOT_CAM, W, H, FULL, 0, SPP)
-        for k in ("samples", "primary", "shadow", "bounce"):   # (the frame is NaN where the teapot is)
+        for k in COUNT_KEYS:   # (the frame is NaN where the teapot is)
             assert gw[2][k] == ow[2][k], (k, gw[2][k], ow[2][k])
         assert np.array_equal(gw[1], ow[1])
         # at least the last iteration's first hits walked their shadow ray
@@ -165,6 +164,6 @@ def test_w9e1_one_spp_and_split_iterations(teapot, w9e1_frame):
     a, ea = _render(teapot, "W9E1", TEAPOT_CAM, 0, 2)
     b, eb = _render(teapot, "W9E1", TEAPOT_CAM, 2, 2, accum_in=a[0])
     assert np.array_equal(b[0].view(np.uint32), g[0].view(np.uint32)) and np.array_equal(b[1], g[1])
-    for k in ("samples", "primary", "shadow", "bounce"):
+    for k in COUNT_KEYS:
         assert a[2][k] + b[2][k] == g[2][k], k
     assert ea + eb == elided

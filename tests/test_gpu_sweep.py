@@ -9,21 +9,19 @@ all background, so the teapot modes also render SILHOUETTE, a region of the
 same shape and the same offset modulo 8 on the teapot's outline, where W5E2
 has blocked and unblocked shadow rays (10 and 70) next to 160 misses; the
 Cornell corner has both for W5E5 (4 blocked, 248 unblocked at one sample)."""
-import json
 import os
-import subprocess
 from importlib import import_module
 
 import numpy as np
 import pytest
 
+import driver
 import sweep_ffi
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODELS = os.path.join(ROOT, "assets", "models")
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 CORNER = (3, 5, 20, 12)
 SILHOUETTE = (179, 133, 20, 12)
 SCENES = {"W5E2": "W5 E2 Teapot", "W5E3": "W5 E3 Teapot", "W5E4": "W5 E4 Cornell Box", "W5E5": "W5 E5 Cornell Box"}
@@ -206,14 +204,9 @@ def test_tiles_of_three_ranks_equal_the_frame(rt, ctx, ref):
 
 def test_cpp_driver_writes_the_same_frame(rt, ref, tmp_path):
     W = H = 64
-    out = str(tmp_path / "frame")
-    r = subprocess.run([BIN, "--scene", "W5 E5 Cornell Box", "--res", f"{W}x{H}", "--out", out], capture_output=True,
-                       text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    info = json.loads(r.stdout.strip().splitlines()[-1])
+    out, info = driver.render(tmp_path, "W5 E5 Cornell Box", W, H)
     assert info["mode"] == "W5E5"
-    acc = np.fromfile(out + ".accum.f32", np.float32).reshape(H, W, 4)
-    ids = np.fromfile(out + ".ids.u32", np.uint32).reshape(H, W)
+    acc, ids, _ = driver.read_frame(out, W, H)
     u = rt.make_uniform(*cam_of(rt, "W5 E5 Cornell Box"), W, H)
     wa, wi, _ = sweep_ffi.render(ref, arrays_of(rt, "CornellBoxWithBlocks.obj"), u, None, (0, 0, W, H), "W5E5")
     assert np.array_equal(ids, wi)

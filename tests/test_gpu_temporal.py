@@ -4,19 +4,17 @@ restatement (tests/temporal_ref.py) bit for bit; temporal_step / temporal_frame 
 Python and the C++ RenderState; the argument checks; and that a state which turned the feature
 off renders what a fresh one renders."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import driver
 import temporal_ref as TR
-from conftest import ROOT
-from test_gpu_denoise import Dev, u32
+from array_util import Dev, u32
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 SIZES = [(1, 1), (7, 5), (16, 16), (17, 16), (33, 31), (65, 64)]   # width x height
 
 
@@ -348,20 +346,18 @@ def test_render_state_cornell_python_and_cpp(rt, tmp_path):
     finally:
         rs.ctx.close()
     # the C++ host and its driver write the Python host's bits, with the default filter and with --denoise's parameters
-    out = str(tmp_path / "frame")
-    cmd = [BIN, "--scene", scene, "--res", f"{W}x{H}", "--temporal-frames", "8", "--keys", "Left"]
-    r = subprocess.run([*cmd, "--out", out + "3", "--denoise", "--denoise-levels", "3", "--denoise-sigma-l", "2",
-                        "--denoise-sigma-z", "0.5"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    assert np.array_equal(np.fromfile(out + "3.temporal.denoised.f32", np.uint32).reshape(H, W, 4), u32(g3))
-    assert np.array_equal(np.fromfile(out + "3.temporal.denoised.rgba8", np.uint8).reshape(H, W, 4), rgba3)
-    assert not os.path.exists(out + "3.denoised.f32")      # no progressive frame was rendered
-    r = subprocess.run([*cmd, "--out", out], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    assert np.array_equal(np.fromfile(out + ".temporal.f32", np.uint32).reshape(H, W, 4), u32(color))
-    assert np.array_equal(np.fromfile(out + ".temporal.len.u32", np.uint32).reshape(H, W), length)
-    assert np.array_equal(np.fromfile(out + ".temporal.denoised.f32", np.uint32).reshape(H, W, 4), u32(got))
-    assert np.array_equal(np.fromfile(out + ".temporal.denoised.rgba8", np.uint8).reshape(H, W, 4), rgba)
+    flags = ("--temporal-frames", "8", "--keys", "Left")
+    (tmp_path / "levels3").mkdir()
+    out, _ = driver.render(tmp_path / "levels3", scene, W, H, *flags, "--denoise", "--denoise-levels", "3",
+                           "--denoise-sigma-l", "2", "--denoise-sigma-z", "0.5")
+    assert np.array_equal(driver.read_file(out, ".temporal.denoised.f32", np.uint32, H, W, 4), u32(g3))
+    assert np.array_equal(driver.read_file(out, ".temporal.denoised.rgba8", np.uint8, H, W, 4), rgba3)
+    assert not os.path.exists(out + ".denoised.f32")      # no progressive frame was rendered
+    out, _ = driver.render(tmp_path, scene, W, H, *flags)
+    assert np.array_equal(driver.read_file(out, ".temporal.f32", np.uint32, H, W, 4), u32(color))
+    assert np.array_equal(driver.read_file(out, ".temporal.len.u32", np.uint32, H, W), length)
+    assert np.array_equal(driver.read_file(out, ".temporal.denoised.f32", np.uint32, H, W, 4), u32(got))
+    assert np.array_equal(driver.read_file(out, ".temporal.denoised.rgba8", np.uint8, H, W, 4), rgba)
 
 
 def test_render_state_w9e1_bunny_standin(rt):

@@ -25,13 +25,12 @@ import pytest
 
 import tile_layout as T
 from conftest import model
-from parity_util import BASIC_CAM, CORNELL_CAM, Scene
+from parity_util import BASIC_CAM, CORNELL_CAM, COUNT_KEYS, Scene, frame_reference
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = T.SENTINEL
 GUARD = 4096   # bytes behind a frame buffer that no kernel may touch
-COUNTS = ("samples", "primary", "shadow", "bounce")
 
 # (W, H, nranks): under / at / over 8 tiles wide, tile rows past 8, a rank without a tile, one pixel
 FRAMES = [(42, 26, 2), (42, 26, 5), (58, 20, 3), (70, 77, 8), (16, 8, 3), (1, 1, 2)]
@@ -82,12 +81,12 @@ def render_packed(s, mode, W, H, nranks, passes):
     try:
         pa.from_numpy(np.full(n * 4, SENTINEL, np.uint32))
         pi.from_numpy(np.full(n, SENTINEL, np.uint32))
-        total = dict.fromkeys(COUNTS, 0)
+        total = dict.fromkeys(COUNT_KEYS, 0)
         for r in range(nranks):
             for first, spp in passes:
                 c = ctx.render_tiles(mode, s.trav, r, nranks, first, spp, pa.ptr + r * lt * 64 * 16,
                                      pi.ptr + r * lt * 64 * 4, counts=True)
-                for k in COUNTS:
+                for k in COUNT_KEYS:
                     total[k] += c[k]
         return pa.to_numpy(np.uint32, (n, 4)), pi.to_numpy(np.uint32, (n,)), total
     finally:
@@ -121,7 +120,7 @@ def test_packed_layout(scenes, mode, trav, W, H, nranks):
     assert np.all(frame[0][..., 3] == 1.0)   # (so no rendered word is the sentinel by value)
     packed = render_packed(s, mode, W, H, nranks, [(0, spp)])
     check_packed(W, H, nranks, packed, frame)
-    assert packed[2] == {k: frame[2][k] for k in COUNTS}
+    assert packed[2] == {k: frame[2][k] for k in COUNT_KEYS}
     assert frame[2]["primary"] >= W * H
 
 
@@ -145,7 +144,7 @@ def test_packed_progressive_continuation(rt, scenes, mode, options):
     check_packed(W, H, nranks, once, frame)
     check_packed(W, H, nranks, twice, frame)
     assert np.array_equal(once[0], twice[0]) and np.array_equal(once[1], twice[1])
-    assert once[2] == twice[2] == {k: frame[2][k] for k in COUNTS}
+    assert once[2] == twice[2] == {k: frame[2][k] for k in COUNT_KEYS}
 
 
 # ---- c. rt_unpack_tiles alone ----------------------------------------------------------------
@@ -234,24 +233,7 @@ def test_unpack_null_pointers(gpu, W, H, nranks, given):
 
 
 # ---- d. rt_frame_rgba8 exactly ---------------------------------------------------------------
-MIDPOINT_REACH = 1e-10   # |255 * oetf(v) - (k + 0.5)| under which two float64 pow may round a code differently
 NSPECIAL, NWINDOW, NRANDOM = 12, 255 * 17, 1 << 16
-
-
-def oetf(v):
-    return np.where(v <= 0.0031308, 12.92 * v, 1.055 * np.power(v, 1.0 / 2.4) - 0.055)
-
-
-def frame_reference(c):
-    """The pinned definition (k_frame's comment) in float64: (code u8, near a rounding midpoint)."""
-    c = np.asarray(c, np.float32)
-    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
-        x = np.where(c > 0, c, np.float32(0))           # NaN, negatives, -0: 0
-        v = (x * np.sqrt(x)).astype(np.float32)         # pow(x, 1.5) = x * sqrt(x), both rounded to float32
-        v = np.where(v < 1, v, np.float32(1))
-    e = 255.0 * oetf(v.astype(np.float64))
-    near = np.abs(e - np.floor(e) - 0.5) < MIDPOINT_REACH
-    return np.floor(e + 0.5).astype(np.uint8), near
 
 
 @lru_cache(maxsize=None)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import w1_ffi as W1
+from parity_util import COUNT_KEYS
 
 pytestmark = pytest.mark.gpu
 
@@ -50,7 +51,7 @@ def compare(got, want):
     wa, wi, wc = want
     assert np.array_equal(gi, wi), f"{int((gi != wi).sum())} ids differ"
     assert W1.same_bits(ga, wa), "accumulation differs"
-    for k in ("samples", "primary", "shadow", "bounce"):
+    for k in COUNT_KEYS:
         assert gc[k] == wc[k], (k, gc[k], wc[k])
 
 

@@ -2,32 +2,20 @@
 the C ABI) renders W1 E2 .. W1 E5, and its accumulation, ids and sRGB frame equal the
 Python RenderState's bit for bit -- both mirrors map the shader to the same mode and
 display it through rt_frame_rgba8_mode."""
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import driver
 import w1_ffi as W1
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 W, H = 24, 16
 
 
 def cpp_render(tmp_path, scene, *args):
-    out = str(tmp_path / "frame")
-    r = subprocess.run([BIN, "--scene", scene, "--res", f"{W}x{H}", "--out", out, *args], capture_output=True,
-                       text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    info = json.loads(r.stdout.strip().splitlines()[-1])
-    acc = np.fromfile(out + ".accum.f32", np.float32).reshape(H, W, 4)
-    ids = np.fromfile(out + ".ids.u32", np.uint32).reshape(H, W)
-    rgba = np.fromfile(out + ".rgba8", np.uint8).reshape(H, W, 4)
-    return acc, ids, rgba, info
+    out, info = driver.render(tmp_path, scene, W, H, *args)
+    return (*driver.read_frame(out, W, H), info)
 
 
 @pytest.mark.parametrize("mode", ["W1E3", "W1E2", "W1E5"])

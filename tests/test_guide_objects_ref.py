@@ -3,18 +3,19 @@ on hand-made cameras, its effect on the oracle's W8E1 and W9E2 frames through th
 through temporal accumulation, the entry points at the ABI boundary (include/rt.h "denoise /
 Guide with objects") and the hosts' refusals."""
 import ctypes as C
-import os
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
+import abi_util
 import denoise_ref as DR
+import driver
 import guide_objects_ref as GR
 import noise_ref as NR
 import temporal_ref as TR
-from conftest import ROOT, model
+from array_util import rms, u32
+from conftest import model
 from parity_util import CORNELL_CAM, TEAPOT_CAM
 
 f32 = np.float32
@@ -23,10 +24,6 @@ BALLS, PLANE = GR.RT_GUIDE_BALLS, GR.RT_GUIDE_PLANE
 # one triangle far from every camera below, so that "a valid id" exists
 VERTS = np.array([[1000.0, 1000.0, 1000.0], [1001.0, 1000.0, 1000.0], [1000.0, 1001.0, 1000.0]], f32)
 TRIS = np.array([[0, 1, 2, 0]], np.uint32)
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
 
 
 def uniform(eye, at, up=(0.0, 1.0, 0.0), cc=1.0, aspect=1.0):
@@ -41,11 +38,6 @@ def rays(u, w, h):
 
 def none_ids(h, w):
     return np.full((h, w), NONE, np.uint32)
-
-
-def rms(a, b, mask=None):
-    d = (a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)) ** 2
-    return float(np.sqrt(np.mean(d if mask is None else d[mask])))
 
 
 # ---- the restatement on hand-made cameras ------------------------------------------
@@ -319,21 +311,15 @@ NAMES = ("rt_guide_objects", "rt_denoise_guide_objects", "rt_denoise_objects")
 
 
 def test_symbols_exported(rt):
-    so = os.path.join(ROOT, "02562_raytracer_amd", "lib02562rt.so")
-    out = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    assert set(NAMES) <= exported, set(NAMES) - exported
-    assert set(NAMES) <= set(rt._ffi.SIGNATURES)
+    abi_util.assert_exported(rt, NAMES)
     assert (rt._ffi.RT_GUIDE_BALLS, rt._ffi.RT_GUIDE_PLANE) == (1, 2)
 
 
 def test_null_context_is_invalid(rt):
-    L, F = rt.lib(), rt._ffi
+    L = rt.lib()
     calls = [lambda: L.rt_denoise_guide_objects(None, 1, 4, 4, None, None, None),
              lambda: L.rt_denoise_objects(None, 1, 4, 4, None, None, None, None, 2, 5, 4.0, 1.0, None)]
-    for name, call in zip(NAMES[1:], calls):
-        assert call() == F.RT_E_INVALID, name
-        assert name.encode() in L.rt_last_error(None), name
+    abi_util.assert_null_context_invalid(rt, dict(zip(NAMES[1:], calls)))
 
 
 def test_guide_objects_of_every_mode(rt):
@@ -357,13 +343,10 @@ def test_guide_objects_of_every_mode(rt):
 @pytest.mark.parametrize("flags", [[], ["--spp", "4"], ["--noise-target", "0.05"], ["--denoise-levels", "3"]])
 def test_rt_render_refuses_guide_objects_without_a_filter(tmp_path, flags):
     # before it touches a device or a file
-    exe = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
-    r = subprocess.run([exe, "--scene", "W8 E1 Cornell Box Balls", "--res", "36x20", "--guide-objects", *flags,
-                        "--out", str(tmp_path / "frame")], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 1 and ("--guide-objects" in r.stderr or "--denoise" in r.stderr), r.stderr
+    r = driver.refused(tmp_path, "W8 E1 Cornell Box Balls", ["--guide-objects", *flags])
+    assert "--guide-objects" in r.stderr or "--denoise" in r.stderr, r.stderr
     if flags != ["--denoise-levels", "3"]:
         assert "--guide-objects" in r.stderr, r.stderr
-    assert r.stdout == "" and os.listdir(tmp_path) == []
 
 
 def test_render_state_set_guide_objects(rt):

@@ -6,19 +6,18 @@ import importlib
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
+import driver
+from conftest import ROOT
 
-pytestmark = pytest.mark.skipif(not os.path.exists(BIN), reason="bin/rt_render not built (make -C 02562_raytracer_amd)")
+pytestmark = pytest.mark.skipif(not os.path.exists(driver.BIN), reason="bin/rt_render not built (make -C 02562_raytracer_amd)")
 
 
 def run(*args):
-    r = subprocess.run([BIN, *args], capture_output=True, text=True, timeout=60)
+    r = driver.run(*args)
     assert r.returncode == 0, r.stderr
     return r.stdout
 
@@ -28,7 +27,7 @@ def f32(x):
 
 
 def test_scene_table_equals_python(rt):
-    cpp = [json.loads(l) for l in run("--list-scenes").splitlines()]
+    cpp = driver.list_scenes()
     py = rt.get_scenes()
     assert len(cpp) == len(py) == 44
     for c, p in zip(cpp, py):
@@ -64,7 +63,7 @@ def test_jitter_table_equals_python(subdiv, h):
 
 
 def test_scene_errors():
-    r = subprocess.run([BIN, "--scene", "W1 E1"], capture_output=True, text=True, timeout=60)
+    r = driver.run("--scene", "W1 E1")
     assert r.returncode != 0
 
 
@@ -105,8 +104,7 @@ def test_refusals_before_a_device_is_opened(options, scene, code, tmp_path):
     """Every option check of rt_render that comes before GpuHandles: exit status 1, nothing on stdout,
     the RT_E_* value of include/rt.h on stderr.  (--env-rgba without --env-size is checked after
     the device is opened, so it has no row here.)"""
-    r = subprocess.run([BIN, *options.split(), "--scene", scene], capture_output=True, text=True, timeout=60,
-                       cwd=tmp_path)
+    r = driver.run(*options.split(), "--scene", scene, cwd=tmp_path)
     assert r.returncode == 1 and r.stdout == "", (r.returncode, r.stdout, r.stderr)
     assert r.stderr.startswith(f"rt_render: error {rt_codes()[code]}: "), r.stderr
     # the text names what it refuses: the row's first option, but for the two rows that refuse a later word

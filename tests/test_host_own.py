@@ -1,8 +1,8 @@
 """The C++ host's device buffers and their owner (include/raytracer.hpp DeviceArray), on the host alone (no GPU)."""
 import os
 import re
-import subprocess
 
+import native_build
 from conftest import ROOT
 
 HOST = os.path.join(ROOT, "02562_raytracer_amd", "host")
@@ -14,14 +14,12 @@ def test_host_check_native(tmp_path):
     never one the context still has registered; so does the lifecycle with any one of its calls of the
     library failing, the constructor's included, and it ends in an Error with that call's code; a failed
     clear or tile allocation leaves the feature off; every refusal comes before a call of the library."""
-    exe = str(tmp_path / "host_check")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                    "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(HOST, "raytracer.cpp"),
-                    os.path.join(ROOT, "02562_raytracer_amd", "csrc", "rt_modes.cpp"),
-                    os.path.join(ROOT, "tests", "native", "host_check.cpp")], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "host_check: 0 mismatches" in out.stdout
+    out = native_build.run_checker(tmp_path, [os.path.join(ROOT, "tests", "native", "host_check.cpp"),
+                                              os.path.join(HOST, "raytracer.cpp"),
+                                              os.path.join(ROOT, "02562_raytracer_amd", "csrc", "rt_modes.cpp")],
+                                   [os.path.join(ROOT, "include")],
+                                   ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined"], timeout=120)
+    assert "host_check: 0 mismatches" in out
 
 
 def test_device_memory_is_freed_by_its_owner_only():

@@ -20,37 +20,12 @@ Distances and the ray interval the walk leaves behind (bsp.wgsl mutates it in
 place) agree to f32 rounding.
 """
 import hashlib
-import json
-import os
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, model
-
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-SCENES = ["test_object", "CornellBox", "CornellBoxWithBlocks", "teapot"]
-# ray index -> cause, for every ray whose walk differs from the reference's
-EXCEPTIONS = {
-    "test_object": {2148: "edge", 2416: "edge", 2483: "edge", 2550: "edge"},
-    "CornellBox": {},
-    "CornellBoxWithBlocks": {4194: "tie", 4655: "tie", 4694: "tie", 4762: "tie", 5008: "tie"},
-    "teapot": {1537: "plane", 1593: "plane", 1594: "plane", 3270: "plane"},
-}
-
-
-def load_fixture(name):
-    with np.load(os.path.join(GOLDEN, f"js_walk_{name}.npz")) as f:
-        z = {k: f[k] for k in f.files}   # decompressed once (NpzFile reads on every access)
-    return json.loads(str(z["meta"])), z
-
-
-def fnv(ids):
-    h = 0x811c9dc5
-    for b in np.asarray(ids, dtype="<u4").tobytes():
-        h ^= b
-        h = (h * 0x01000193) & 0xFFFFFFFF
-    return h
+from conftest import model
+from js_walk_golden import EXCEPTIONS, SCENES, fnv, load_fixture
 
 
 def js_triangle_f64(mesh, tri, o, d):

@@ -17,34 +17,17 @@ triangles (order included) -- except a listed set, each checked for its cause:
     the oracle visits one more leaf and reaches the same result.
 Distances agree to f32 rounding.
 """
-import json
-import os
-
 import numpy as np
 import pytest
 
-from conftest import ROOT, model
-from test_js_walk import fnv
-
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-SCENES = ["CornellBoxWithBlocks", "teapot"]
-# ray index -> cause, for every ray whose walk differs from the reference's
-EXCEPTIONS = {
-    "CornellBoxWithBlocks": {},
-    "teapot": {0: "deps", 6: "deps", 1281: "deps", 1439: "deps", 2029: "deps"},
-}
-
-
-def load_fixture(name):
-    with np.load(os.path.join(GOLDEN, f"js_walk2_{name}.npz")) as f:
-        z = {k: f[k] for k in f.files}
-    return json.loads(str(z["meta"])), z
+from conftest import model
+from js_walk_golden import EXCEPTIONS2 as EXCEPTIONS, SCENES2 as SCENES, fnv, load_fixture
 
 
 @pytest.fixture(scope="module", params=SCENES)
 def js2_scene(request, oracle):
     name = request.param
-    meta, z = load_fixture(name)
+    meta, z = load_fixture(name, "js_walk2")
     m = oracle.load_obj(model(f"{name}.obj"))
     b = oracle.build_bsp(m, 20, 4, js64=True)
     return name, meta, z, m, b

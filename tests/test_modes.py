@@ -4,16 +4,14 @@ _ffi.py, the shader dicts and the properties of scenes.py, the C++ host's scene 
 against literal values (no GPU).  The literals are the lists as they stood before the
 table; none is computed from the table under test."""
 import ctypes as C
-import json
 import os
-import subprocess
 from importlib import import_module
 
-import pytest
 
+import driver
+import native_build
 from conftest import ROOT
 
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 
 W1, AN, SW, PR, DI, PA = range(6)   # RT_FAMILY_WORKSHEET1 .. RT_FAMILY_PATH
 PROG, TEX0, LINEAR, AREA = 1, 2, 4, 8
@@ -157,9 +155,7 @@ def test_scene_properties(rt):
 
 
 def test_cpp_list_scenes_agrees_on_all_five_keys():
-    r = subprocess.run([BIN, "--list-scenes"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr
-    rows = list(map(json.loads, r.stdout.splitlines()))
+    rows = driver.list_scenes()
     assert [d["name"] for d in rows] == [s[0] for s in SCENES]
     for d, (_, mode, render, analytic, w1, kernel) in zip(rows, SCENES):
         assert (d["mode"], d["render_mode"], d["analytic_mode"], d["worksheet1_mode"], d["kernel_mode"]) == (
@@ -169,10 +165,7 @@ def test_cpp_list_scenes_agrees_on_all_five_keys():
 def test_modes_check_native(tmp_path):
     """tests/native/modes_check.cpp: rt_mode_describe past both ends of the enum and the C++
     host's shader lookup, linked with the table's translation unit alone."""
-    exe = str(tmp_path / "modes_check")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", exe,
-                    os.path.join(ROOT, "tests", "native", "modes_check.cpp"),
-                    os.path.join(ROOT, "02562_raytracer_amd", "csrc", "rt_modes.cpp")], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout
-    assert "modes_check: 0 mismatches" in out.stdout
+    out = native_build.run_checker(tmp_path, [os.path.join(ROOT, "tests", "native", "modes_check.cpp"),
+                                              os.path.join(ROOT, "02562_raytracer_amd", "csrc", "rt_modes.cpp")],
+                                   [os.path.join(ROOT, "include")], ["-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror"])
+    assert "modes_check: 0 mismatches" in out

@@ -2,14 +2,13 @@
 against a float64 two-pass variance, and the four entry points at the ABI boundary
 (include/rt.h "noise estimate")."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import abi_util
+import driver
 import noise_ref as NR
-from conftest import ROOT
 
 ROWS = 20_000
 NS = (2, 3, 8, 17, 64)
@@ -80,11 +79,7 @@ NAMES = ("rt_set_noise_buffer", "rt_noise_accumulate", "rt_noise_map", "rt_noise
 
 
 def test_symbols_exported(rt):
-    so = os.path.join(ROOT, "02562_raytracer_amd", "lib02562rt.so")
-    out = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    assert set(NAMES) <= exported, set(NAMES) - exported
-    assert set(NAMES) <= set(rt._ffi.SIGNATURES)
+    abi_util.assert_exported(rt, NAMES)
 
 
 def test_struct_sizes(rt, tmp_path):
@@ -92,27 +87,20 @@ def test_struct_sizes(rt, tmp_path):
     assert C.sizeof(F.NoiseState) == 8
     assert C.sizeof(F.NoiseSummary) == 32
     # and the header's own structs, through the C compiler
-    src = tmp_path / "sizes.c"
-    src.write_text('#include "rt.h"\n'
-                   "_Static_assert(sizeof(rt_noise_state) == 8, \"rt_noise_state\");\n"
-                   "_Static_assert(sizeof(rt_noise_summary) == 32, \"rt_noise_summary\");\n"
-                   "_Static_assert(__builtin_offsetof(rt_noise_summary, max_rel_err) == 24, \"max_rel_err\");\n")
-    r = subprocess.run(["cc", "-std=c11", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    abi_util.assert_header_compiles(tmp_path, [
+        '_Static_assert(sizeof(rt_noise_state) == 8, "rt_noise_state");',
+        '_Static_assert(sizeof(rt_noise_summary) == 32, "rt_noise_summary");',
+        '_Static_assert(__builtin_offsetof(rt_noise_summary, max_rel_err) == 24, "max_rel_err");'])
 
 
 def test_null_context_is_invalid(rt):
     L = rt.lib()
-    F = rt._ffi
-    s = F.NoiseSummary()
+    s = rt._ffi.NoiseSummary()
     calls = [lambda: L.rt_set_noise_buffer(None, None),
              lambda: L.rt_noise_accumulate(None, None, 4, 2, 1, 0, None),
              lambda: L.rt_noise_map(None, None, 4, 2, 1e-3, None),
              lambda: L.rt_noise_summarize(None, None, 4, 2, 0.0, 1e-3, C.byref(s))]
-    for name, call in zip(NAMES, calls):
-        assert call() == F.RT_E_INVALID, name
-        assert name.encode() in L.rt_last_error(None), name
+    abi_util.assert_null_context_invalid(rt, dict(zip(NAMES, calls)))
 
 
 @pytest.mark.parametrize("extra", [["--comm-file", "ID"], ["--comm-file", "ID", "--nranks", "1", "--rank", "0"],
@@ -121,12 +109,8 @@ def test_rt_render_refuses_noise_target_on_a_tiled_render(tmp_path, extra):
     # --comm-file tiles the render for any rank count, 1 included: its states would be packed per
     # tile (and more than W x H of them on a ragged frame), not the H x W map.  Refused before
     # any device or communicator file is touched.
-    exe = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
-    extra = [str(tmp_path / a) if a == "ID" else a for a in extra]
-    r = subprocess.run([exe, "--scene", "W7 E3 Cornell Box", "--res", "36x20", "--noise-target", "0.05",
-                        "--out", str(tmp_path / "frame"), *extra], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 1 and "--noise-target" in r.stderr and "--comm-file" in r.stderr, r.stderr
-    assert r.stdout == "" and os.listdir(tmp_path) == []
+    r = driver.refused(tmp_path, "W7 E3 Cornell Box", ["--noise-target", "0.05", *extra])
+    assert "--noise-target" in r.stderr and "--comm-file" in r.stderr, r.stderr
 
 
 def test_render_state_refuses_other_modes(rt):

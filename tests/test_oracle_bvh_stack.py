@@ -8,9 +8,9 @@ import numpy as np
 import pytest
 
 import oracle_ffi as O
+from accel_cases import FAR, chain_bvh
 from conftest import model
 from parity_util import TEAPOT_CAM
-from test_gpu_bvh_stack import FAR, chain_bvh
 
 
 @pytest.fixture(scope="module")

@@ -1,8 +1,8 @@
 """The owners of the context's events and streams (csrc/rt_own.h), on the host alone (no GPU)."""
 import os
 import re
-import subprocess
 
+import native_build
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "02562_raytracer_amd", "csrc")
@@ -13,12 +13,9 @@ def test_own_check_native(tmp_path):
     undefined-behaviour sanitizers -- created == destroyed at scope exit, across moves, after a
     double reset and after a pool growth that fails; an all-or-nothing set-up of six handles whose
     fourth fails leaves none alive."""
-    exe = str(tmp_path / "own_check")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-I", CSRC,
-                    "-o", exe, os.path.join(ROOT, "tests", "native", "own_check.cpp")], check=True)
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout + out.stderr
-    assert "own_check: 0 mismatches" in out.stdout
+    out = native_build.run_checker(tmp_path, [os.path.join(ROOT, "tests", "native", "own_check.cpp")], [CSRC],
+                                   ["-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined"])
+    assert "own_check: 0 mismatches" in out
 
 
 def test_handles_are_destroyed_by_their_owners_only():

@@ -11,13 +11,13 @@ marks the whole interval.  The scenes are those of tests/test_empty_mask.py.
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import native_build
 from conftest import model
-from test_empty_mask import CAM3, _frame_camera
+from parity_util import CAM3, frame_camera
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "pixel_depth_brute.c")
@@ -27,12 +27,10 @@ ITERS = 16
 
 @pytest.fixture(scope="module")
 def brute():
-    so = os.path.join(ROOT, "tests", "native", "pixel_depth_brute.so")   # (git ignores *.so)
-    if not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(SRC):
-        subprocess.run(["gcc", "-O3", "-march=native", "-ffp-contract=off", "-fno-fast-math", "-fopenmp", "-shared",
-                        "-fPIC", "-o", so, SRC], check=True)
     os.environ.setdefault("OMP_NUM_THREADS", str(min(16, os.cpu_count() or 1)))
-    return C.CDLL(so)
+    # beside its source, compiled once (git ignores *.so)
+    return native_build.shared_lib(SRC, os.path.dirname(SRC),
+                                   ["-O3", "-march=native", "-ffp-contract=off", "-fno-fast-math", "-fopenmp"])
 
 
 def _accepts(lib, mesh, rays):
@@ -139,12 +137,12 @@ def test_standin_69451(rt, oracle, brute):
 
 def test_teapot(rt, oracle, brute):
     mesh = rt.Mesh.from_obj(model("teapot.obj"))
-    _check(rt, oracle, brute, mesh, _frame_camera(mesh), 96, 64)
+    _check(rt, oracle, brute, mesh, frame_camera(mesh), 96, 64)
 
 
 def test_elephant(rt, oracle, brute):
     mesh = rt.Mesh.from_obj(model("justElephant.obj"))
-    _check(rt, oracle, brute, mesh, _frame_camera(mesh), 96, 64)
+    _check(rt, oracle, brute, mesh, frame_camera(mesh), 96, 64)
 
 
 def test_soup_20000(rt, oracle, brute):

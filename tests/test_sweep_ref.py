@@ -8,18 +8,16 @@ CornellBoxWithBlocks.obj: 93.8 % of the pixels hit, and for 16.3 % of the hit
 pixels the first-accepted triangle is not the closest accepted one;
 test_object.obj (the BASIC camera): 51.3 % hit, 77.5 % of the hits differ.  A
 closest-hit implementation therefore fails both cases."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import driver
 import sweep_ffi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODELS = os.path.join(ROOT, "assets", "models")
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 f32 = np.float32
 
 
@@ -153,8 +151,7 @@ def test_scene_tables_name_the_sweep_modes(rt):
 
 
 def test_cpp_list_scenes_agrees_on_render_mode(rt):
-    out =subprocess.run([BIN, "--list-scenes"], capture_output=True, text=True, timeout=60, check=True).stdout
-    cpp = [json.loads(l) for l in out.splitlines()]
+    cpp = driver.list_scenes()
     py = rt.get_scenes()
     assert len(cpp) == len(py) == 44
     for c, p in zip(cpp, py):

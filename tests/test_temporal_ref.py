@@ -2,27 +2,20 @@
 on hand-made frames and on the oracle's Cornell box under a moving camera, the entry points
 at the ABI boundary (include/rt.h "temporal accumulation") and the hosts' refusals."""
 import ctypes as C
-import os
-import subprocess
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
+import abi_util
+import driver
 import temporal_ref as TR
-from conftest import ROOT, model
+from array_util import rms, u32
+from conftest import model
 from parity_util import CORNELL_CAM
 
 f32 = np.float32
 QNAN = TR.QNAN_BITS
-
-
-def u32(a):
-    return np.ascontiguousarray(a, dtype=f32).view(np.uint32)
-
-
-def rms(a, b):
-    return float(np.sqrt(np.mean((a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)) ** 2)))
 
 
 def uniform(eye=(0.0, 0.0, 0.0), at=None, up=(0.0, 1.0, 0.0), cc=1.0, aspect=1.0):
@@ -390,11 +383,7 @@ NAMES = ("rt_temporal_accumulate", "rt_temporal_variance", "rt_temporal_times")
 
 
 def test_symbols_exported(rt):
-    so = os.path.join(ROOT, "02562_raytracer_amd", "lib02562rt.so")
-    out = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
-    exported = {l.split()[-1] for l in out.splitlines() if " T " in l}
-    assert set(NAMES) <= exported, set(NAMES) - exported
-    assert set(NAMES) <= set(rt._ffi.SIGNATURES)
+    abi_util.assert_exported(rt, NAMES)
     assert rt._ffi.RT_OPT_TEMPORAL_VAR_LDS == 15
 
 
@@ -405,26 +394,16 @@ def test_null_context_is_invalid(rt):
                                               None, None, None),
              lambda: L.rt_temporal_variance(None, 4, 4, None, None, None, None, 4, 0.9, 0.01, None),
              lambda: L.rt_temporal_times(None, C.byref(a), C.byref(v), None)]
-    for name, call in zip(NAMES, calls):
-        assert call() == F.RT_E_INVALID, name
-        assert name.encode() in L.rt_last_error(None), name
+    abi_util.assert_null_context_invalid(rt, dict(zip(NAMES, calls)))
 
 
 # ---- the hosts' refusals ------------------------------------------------------------
-def _rt_render(tmp_path, scene, flags):
-    exe = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
-    flags = [str(tmp_path / a) if a == "ID" else a for a in flags]
-    return subprocess.run([exe, "--scene", scene, "--res", "36x20", *flags, "--out", str(tmp_path / "frame")],
-                          capture_output=True, text=True, timeout=60)
-
-
 @pytest.mark.parametrize("extra", [["--comm-file", "ID"], ["--comm-file", "ID", "--nranks", "2", "--rank", "1"],
                                    ["--noise-target", "0.05"], ["--adaptive-target", "0.05"], ["--samples", "4"]])
 def test_rt_render_refuses_temporal_frames_with(tmp_path, extra):
     # before it touches a device or a file
-    r = _rt_render(tmp_path, "W7 E3 Cornell Box", ["--temporal-frames", "4", "--keys", "Left", *extra])
-    assert r.returncode == 1 and "--temporal-frames" in r.stderr and extra[0] in r.stderr, r.stderr
-    assert r.stdout == "" and os.listdir(tmp_path) == []
+    r = driver.refused(tmp_path, "W7 E3 Cornell Box", ["--temporal-frames", "4", "--keys", "Left", *extra])
+    assert "--temporal-frames" in r.stderr and extra[0] in r.stderr, r.stderr
 
 
 @pytest.mark.parametrize("flags", [["--temporal-frames", "0"], ["--temporal-frames", "4", "--temporal-history", "0"],
@@ -436,15 +415,13 @@ def test_rt_render_refuses_temporal_frames_with(tmp_path, extra):
                                    ["--temporal-frames", "4", "--denoise", "--denoise-levels", "6"],
                                    ["--temporal-frames", "4", "--denoise", "--denoise-sigma-l", "0"]])
 def test_rt_render_refuses_bad_temporal_flags(tmp_path, flags):
-    r = _rt_render(tmp_path, "W7 E3 Cornell Box", flags)
-    assert r.returncode == 1 and ("--temporal" in r.stderr or "--denoise" in r.stderr), r.stderr
-    assert r.stdout == "" and os.listdir(tmp_path) == []
+    r = driver.refused(tmp_path, "W7 E3 Cornell Box", flags)
+    assert "--temporal" in r.stderr or "--denoise" in r.stderr, r.stderr
 
 
 def test_rt_render_refuses_temporal_frames_for_a_mode_that_is_no_path_mode(tmp_path):
-    r = _rt_render(tmp_path, "W7 E1 Cornell Box", ["--temporal-frames", "4"])
-    assert r.returncode == 1 and "--temporal-frames" in r.stderr and "path mode" in r.stderr, r.stderr
-    assert r.stdout == "" and os.listdir(tmp_path) == []
+    r = driver.refused(tmp_path, "W7 E1 Cornell Box", ["--temporal-frames", "4"])
+    assert "--temporal-frames" in r.stderr and "path mode" in r.stderr, r.stderr
 
 
 def test_render_state_refusals(rt):

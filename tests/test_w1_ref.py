@@ -4,18 +4,16 @@ and the properties of those shaders that the GPU tests rely on, shown from the
 reference alone: the closest hit wins (not the first accepted), the plane accepts
 a NaN distance, W1E3 and W1E4 read neither the aspect ratio nor the camera
 constant, and W1E2's border follows the pinned integer rule.  No GPU needed."""
-import json
 import os
-import subprocess
 from importlib import import_module
 
 import numpy as np
 import pytest
 
+import driver
 import w1_ffi as W1
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "02562_raytracer_amd", "bin", "rt_render")
 f32 = np.float32
 RAY_MODES = ["W1E3", "W1E4", "W1E5"]
 SIZES = [(16, 16), (13, 9)]
@@ -264,9 +262,7 @@ def test_scene_tables_and_mode_values(rt):
 
 def test_cpp_scene_table_reports_the_worksheet1_mode():
     # the C++ mirror's table (no GPU): the new mode under its own key, "mode" as it was
-    r = subprocess.run([BIN, "--list-scenes"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stderr
-    rows = {d["name"]: d for d in map(json.loads, r.stdout.splitlines())}
+    rows = {d["name"]: d for d in driver.list_scenes()}
     assert len(rows) == 44
     by_scene = {v: k for k, v in W1.SCENES.items()}
     for name, d in rows.items():

@@ -3,9 +3,11 @@ modes W1E2..W1E5 (test infrastructure; shares no code with the kernel), and the
 inputs the CPU and GPU tests of those modes share."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import native_build
+from parity_util import COUNT_KEYS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "w1_ref.c")
@@ -28,10 +30,7 @@ CAMERAS = {"basic": BASIC, "occlusion-a": OCCLUSION_A, "occlusion-b": OCCLUSION_
 
 def build(out_dir):
     """Compile w1_ref.c into out_dir and load it."""
-    so = os.path.join(str(out_dir), "libw1_ref.so")
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, SRC, "-lm"], check=True,
-                   timeout=120)
-    lib = C.CDLL(so)
+    lib = native_build.shared_lib(SRC, out_dir, ["-O2", "-ffp-contract=off"], libs=["-lm"], timeout=120)
     vp = C.c_void_p
     lib.w1_ref_render.restype = C.c_int
     lib.w1_ref_render.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, vp, vp]
@@ -47,7 +46,7 @@ def render(lib, uniform, region, mode):
     rc = lib.w1_ref_render(C.addressof(uniform), x0, y0, w, h, MODES[mode], acc.ctypes.data, ids.ctypes.data,
                            cnt.ctypes.data)
     assert rc == 0, f"w1_ref_render failed ({rc})"
-    return acc, ids, {n: int(c) for n, c in zip(("samples", "primary", "shadow", "bounce"), cnt)}
+    return acc, ids, {n: int(c) for n, c in zip(COUNT_KEYS, cnt)}
 
 
 def same_bits(a, b):
